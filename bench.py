@@ -11,10 +11,16 @@ A "step" is one aggregation layer over the whole graph: C = Â·H (N = 1), or, f
 row-block SpMM followed by the exchange of the layer output over xGMI (the next layer's input) — strong
 scaling, the graph is fixed.  For N > 1 every rank builds ITS row block only (graphgen.make_graph_row_block →
 RowShardedAdjacency.from_row_block): no rank ever holds the whole CSR.  Inputs are resident in HBM when the
-timed region starts.  After the timed loop the output of the last step (N = 1) — or, on the sharded path, of one more
-layer of the same pipeline run right behind the timed ones, whose input can be kept without copying tens of GB inside
-the timed region — is checked on sampled rows against an fp64 evaluation (torch arithmetic, gcn_amd/check.py); the run
-fails above 1e-5.  Prints ONE JSON line on rank 0.
+timed region starts, and the same arguments give the same inputs on every run.  A plain run sets up, warms up,
+times --steps steps and prints ONE JSON line on rank 0 (metric, value, unit, ms_per_step, ...);
+`--dump-outputs DIR` first writes the last timed step's output there (dump_output).
+
+`--full` adds what the headline figure does not need: after the timed loop the output of the last step (N = 1) — or,
+on the sharded path, of one more layer of the same pipeline run right behind the timed ones, whose input can be kept
+without copying tens of GB inside the timed region — is checked on sampled rows against an fp64 evaluation (torch
+arithmetic, gcn_amd/check.py; the run fails above 1e-5), the main kernel is timed live inside the timed steps for the
+`roofline` figures, the weighted leg times a plan of its own, and the CPU baseline (`--no-cpu-baseline` skips it)
+times torch.spmm on the host.
 
 The other BASELINE configs run through the same code and print the same line (not the headline metric; the
 driver only runs the default):
@@ -171,6 +177,24 @@ def renumber(rowptr, col, val, order, dev, offline=0):
     return rp, ci, va, secs, where
 
 
+DUMP_BYTES = 48 << 20       # all ranks' dumped outputs together
+
+
+def dump_output(path, C, world, rank):
+    """this rank's [rows, k] output of the last timed step -> path/C.npy (C_rank<r>.npy for N > 1) as float32: every
+    row if they fit this rank's share of DUMP_BYTES, else a fixed sample of rows (seeded, ascending), the same from run
+    to run"""
+    import numpy as np
+    rows, k = C.shape
+    keep = max(1, (DUMP_BYTES // world) // (4 * max(k, 1)))
+    if rows > keep:
+        g = torch.Generator(device="cpu")
+        g.manual_seed(4321 + rank)
+        C = C.index_select(0, torch.randperm(rows, generator=g)[:keep].sort().values.to(C.device))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "C.npy" if world == 1 else f"C_rank{rank}.npy"), C.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -195,7 +219,13 @@ def main():
     ap.add_argument("--exchange", default="all_gather", choices=["all_gather", "direct", "push"],
                     help="N > 1: one RCCL all-gather per plane and layer, a grouped send/recv to every peer, or shards pushed "
                          "into the peers' IPC-mapped buffers by the copy engines (no collective kernel)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the fp64 check of the timed output, "
+                         "the live kernel timing and roofline, the weighted leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write the last timed step's output as DIR/C.npy (float32; C_rank<r>.npy per "
+                         "rank for N > 1), all rows if they fit 48 MiB, else a fixed seeded sample of rows in ascending order")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--force-shard", action="store_true",
                     help="debug: run the row-sharded pipelined path even with one rank (no collective)")
     ap.add_argument("--chunk", type=int, default=0, help="debug: chunk size in non-zeros (0 = automatic)")
@@ -214,6 +244,8 @@ def main():
                     help="debug: on ONE GPU, time rank 0's row block of a W-way partition (compute only, "
                          "no collective) — a rehearsal of the per-rank work at N = W, not a metric")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -360,7 +392,8 @@ def main():
     barrier()
     if sharded:
         pipe.finish()
-    local_adj.profile_begin(args.steps * launches_per_step)
+    if args.full:
+        local_adj.profile_begin(args.steps * launches_per_step)
     t0 = time.perf_counter()
     for i in range(args.steps):
         step()
@@ -368,9 +401,12 @@ def main():
         pipe.finish()
     barrier()
     elapsed = time.perf_counter() - t0
-    kernel_ms = local_adj.profile_end()
+    kernel_ms = local_adj.profile_end() if args.full else []
     if sharded:
         shard.check_exchange()                            # (push form: did a wait for a peer's flag give up?)
+    if args.dump_outputs:
+        dump_output(args.dump_outputs, pipe.local_rows() if sharded else out, world, rank)
+    if args.full and sharded:
         # The check of the sharded path needs a layer's INPUT beside its output, i.e. a copy of the exchange buffers — tens
         # of GB for the papers100M-shaped graph, whose allocation alone took 1.6 s inside the timed loop when it was made
         # there.  So: the timed layers run undisturbed, and ONE more layer of the same pipeline, right behind them and
@@ -385,84 +421,85 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- the output that was timed, checked on sampled rows against fp64 (every rank its own rows) --------
-    gsel = torch.Generator(device="cpu")
-    gsel.manual_seed(1234 + rank)
-    # BASELINE.md §3 / SURVEY §8(d): the FULL matrix for n <= 3 M (every output row of every rank), a fixed random sample of
-    # rows beyond (4 096 on one GPU)
-    full_check = n <= FULL_CHECK_MAX_N
-    nsample = local_m if full_check else min(4096 if world == 1 else 1024, local_m)
-    sel = torch.arange(local_m) if full_check else torch.randperm(local_m, generator=gsel)[:nsample].sort().values
-    if not sharded:
-        rel, checked = sampled_rows_rel_err(rowptr, col, val, H, out, sel, batch_nnz=1 << 22)
-    else:
-        op_rp, op_col, op_val = shard.as_buffer_operator()      # the layer as a map between exchange buffers
-        own = shard.buffer_rows_of_local_rows(dev)
-        rel, checked = 0.0, 0
-        for p, w in enumerate(pipe.widths):                   # plane by plane: Â·(plane of the last layer's input)
-            got = pipe.src[p].index_select(0, own)
-            r_p, checked = sampled_rows_rel_err(op_rp, op_col, op_val, last_in[p], got, sel)
-            rel = max(rel, r_p)
-        del last_in
-    verdict = torch.tensor([rel], dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(verdict, op=dist.ReduceOp.MAX)        # every rank learns the worst error: all fail together
-    rel_all = float(verdict.item())
-    check_failed = not (rel_all <= TOL)
+    check_failed, weighted_ms = False, None
+    if args.full:
+        # ---- the output that was timed, checked on sampled rows against fp64 (every rank its own rows) --------
+        gsel = torch.Generator(device="cpu")
+        gsel.manual_seed(1234 + rank)
+        # BASELINE.md §3 / SURVEY §8(d): the FULL matrix for n <= 3 M (every output row of every rank), a fixed random sample of
+        # rows beyond (4 096 on one GPU)
+        full_check = n <= FULL_CHECK_MAX_N
+        nsample = local_m if full_check else min(4096 if world == 1 else 1024, local_m)
+        sel = torch.arange(local_m) if full_check else torch.randperm(local_m, generator=gsel)[:nsample].sort().values
+        if not sharded:
+            rel, checked = sampled_rows_rel_err(rowptr, col, val, H, out, sel, batch_nnz=1 << 22)
+        else:
+            op_rp, op_col, op_val = shard.as_buffer_operator()      # the layer as a map between exchange buffers
+            own = shard.buffer_rows_of_local_rows(dev)
+            rel, checked = 0.0, 0
+            for p, w in enumerate(pipe.widths):                   # plane by plane: Â·(plane of the last layer's input)
+                got = pipe.src[p].index_select(0, own)
+                r_p, checked = sampled_rows_rel_err(op_rp, op_col, op_val, last_in[p], got, sel)
+                rel = max(rel, r_p)
+            del last_in
+        verdict = torch.tensor([rel], dtype=torch.float64, device=dev)
+        if world > 1:
+            dist.all_reduce(verdict, op=dist.ReduceOp.MAX)        # every rank learns the worst error: all fail together
+        rel_all = float(verdict.item())
+        check_failed = not (rel_all <= TOL)
 
-    # ---- roofline of the dominant kernel (the plan's main kernel), this rank's launches ---------
-    # (N = 1: one timed interval per SpMM = all column passes of the main kernel; N > 1: one per
-    #  64-column plane SpMM of this rank's row block)
-    kp = k if not sharded else min(k, args.plane_cols)    # columns per timed SpMM
-    passes = local_adj.num_passes(kp)                     # main-kernel launches per timed SpMM
-    spmm_avg = sum(kernel_ms) / max(len(kernel_ms), 1) * 1e-3
-    kavg = spmm_avg / passes                              # per LAUNCH, what rocprofv3 --stats averages
-    cols_per_launch = kp // passes
-    balg = algorithmic_bytes(local_m, local_nnz, kp) / passes
-    achieved = balg / kavg if kavg > 0 else 0.0
-    gathered = local_nnz * cols_per_launch * 4            # feature-row bytes the kernel pulls through L2 -> CU per launch
-    kname = local_adj.main_kernel(kp)
-    full_size = args.scale == 1.0 and (args.graph != "rmat24" or args.rmat_scale == 24)
-    pmc = pmc_traffic(args.graph, k, order, passes, kname.split("<")[0]) if (not sharded and full_size and
-                                                                             args.graph_device == "gpu") else None
-    traffic, pmc_hit, pmc_src = pmc if pmc else (None, None, None)
-    n_cols = n if not sharded else shard.world * shard.max_rows
-    compulsory = local_nnz * 8 + (local_m + 1) * 4 + n_cols * kp * 4 + local_m * kp * 4
-    # Which wall?  A column-sliced plan keeps its gathers in the XCDs' L2s (the Reddit-shaped graph: 93 % hits): the
-    # bounded fraction is L2 -> CU bytes.  An unsliced plan on a table far larger than the caches gathers from HBM /
-    # Infinity Cache: SURVEY §8(d)'s algorithmic bytes over the HBM peak IS the fraction there (<= 1 by construction).
-    # (a table that fits the 256 MiB Infinity Cache as it is never reaches HBM either: same wall, same fraction)
-    l2_bound = local_adj.num_slices > 1 or n_cols * kp * 4 <= (256 << 20)
-    frac_l2 = round(gathered / kavg / L2_PEAK, 4) if kavg > 0 else None
-    frac_alg = round(achieved / HBM_PEAK, 4)
-    concurrent = len(pipe.widths) if (sharded and pipe.streams is not None) else 1
-    if concurrent > 1:
-        # the planes' main kernels run side by side on their own streams: a launch's duration includes the share of the
-        # chip the other plane holds, so the fractions are taken over the LAYER (all planes' bytes / step time)
-        layer_s = elapsed / args.steps
-        frac_l2 = round(local_nnz * k * 4 / layer_s / L2_PEAK, 4)
-        frac_alg = round(algorithmic_bytes(local_m, local_nnz, k) / layer_s / HBM_PEAK, 4)
+        # ---- roofline of the dominant kernel (the plan's main kernel), this rank's launches ---------
+        # (N = 1: one timed interval per SpMM = all column passes of the main kernel; N > 1: one per
+        #  64-column plane SpMM of this rank's row block)
+        kp = k if not sharded else min(k, args.plane_cols)    # columns per timed SpMM
+        passes = local_adj.num_passes(kp)                     # main-kernel launches per timed SpMM
+        spmm_avg = sum(kernel_ms) / max(len(kernel_ms), 1) * 1e-3
+        kavg = spmm_avg / passes                              # per LAUNCH, what rocprofv3 --stats averages
+        cols_per_launch = kp // passes
+        balg = algorithmic_bytes(local_m, local_nnz, kp) / passes
+        achieved = balg / kavg if kavg > 0 else 0.0
+        gathered = local_nnz * cols_per_launch * 4            # feature-row bytes the kernel pulls through L2 -> CU per launch
+        kname = local_adj.main_kernel(kp)
+        full_size = args.scale == 1.0 and (args.graph != "rmat24" or args.rmat_scale == 24)
+        pmc = pmc_traffic(args.graph, k, order, passes, kname.split("<")[0]) if (not sharded and full_size and
+                                                                                 args.graph_device == "gpu") else None
+        traffic, pmc_hit, pmc_src = pmc if pmc else (None, None, None)
+        n_cols = n if not sharded else shard.world * shard.max_rows
+        compulsory = local_nnz * 8 + (local_m + 1) * 4 + n_cols * kp * 4 + local_m * kp * 4
+        # Which wall?  A column-sliced plan keeps its gathers in the XCDs' L2s (the Reddit-shaped graph: 93 % hits): the
+        # bounded fraction is L2 -> CU bytes.  An unsliced plan on a table far larger than the caches gathers from HBM /
+        # Infinity Cache: SURVEY §8(d)'s algorithmic bytes over the HBM peak IS the fraction there (<= 1 by construction).
+        # (a table that fits the 256 MiB Infinity Cache as it is never reaches HBM either: same wall, same fraction)
+        l2_bound = local_adj.num_slices > 1 or n_cols * kp * 4 <= (256 << 20)
+        frac_l2 = round(gathered / kavg / L2_PEAK, 4) if kavg > 0 else None
+        frac_alg = round(achieved / HBM_PEAK, 4)
+        concurrent = len(pipe.widths) if (sharded and pipe.streams is not None) else 1
+        if concurrent > 1:
+            # the planes' main kernels run side by side on their own streams: a launch's duration includes the share of the
+            # chip the other plane holds, so the fractions are taken over the LAYER (all planes' bytes / step time)
+            layer_s = elapsed / args.steps
+            frac_l2 = round(local_nnz * k * 4 / layer_s / L2_PEAK, 4)
+            frac_alg = round(algorithmic_bytes(local_m, local_nnz, k) / layer_s / HBM_PEAK, 4)
 
-    # the same SpMM with the matrix values kept (matrices whose values do not factor as u[r]*u[c] run this pass):
-    # a second plan told to forget the factors (API, not an environment switch), a short timed loop of its own
-    weighted_ms = None
-    if not sharded and l2_bound and local_adj.has_value_factors and not check_failed:
-        adj_w = gcn_amd.CsrAdjacency(rowptr, col, val, (n, n), symmetric=True, chunk_nnz=args.chunk)
-        adj_w.plan                                                         # noqa: B018  (builds the plan)
-        adj_w.set_value_factors(None, None)
-        reps = max(3, min(args.steps, 10))
-        for _ in range(2):
-            adj_w.matmul_raw(H, out=out)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            adj_w.matmul_raw(H, out=out)
-        e1.record()
-        torch.cuda.synchronize()
-        weighted_ms = {"ms_per_spmm": round(e0.elapsed_time(e1) / reps, 4), "kernel": adj_w.main_kernel(k), "spmms_timed": reps,
-                       "what": "whole SpMM with the value stream kept (gcn_spmm_plan_set_value_factors(null, null)): what an "
-                               "adjacency whose values are not u[r]*u[c] costs on this graph"}
-        del adj_w
+        # the same SpMM with the matrix values kept (matrices whose values do not factor as u[r]*u[c] run this pass):
+        # a second plan told to forget the factors (API, not an environment switch), a short timed loop of its own
+        if not sharded and l2_bound and local_adj.has_value_factors and not check_failed:
+            adj_w = gcn_amd.CsrAdjacency(rowptr, col, val, (n, n), symmetric=True, chunk_nnz=args.chunk)
+            adj_w.plan                                                         # noqa: B018  (builds the plan)
+            adj_w.set_value_factors(None, None)
+            reps = max(3, min(args.steps, 10))
+            for _ in range(2):
+                adj_w.matmul_raw(H, out=out)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                adj_w.matmul_raw(H, out=out)
+            e1.record()
+            torch.cuda.synchronize()
+            weighted_ms = {"ms_per_spmm": round(e0.elapsed_time(e1) / reps, 4), "kernel": adj_w.main_kernel(k), "spmms_timed": reps,
+                           "what": "whole SpMM with the value stream kept (gcn_spmm_plan_set_value_factors(null, null)): what an "
+                                   "adjacency whose values are not u[r]*u[c] costs on this graph"}
+            del adj_w
 
     if rank == 0:
         flops = 2.0 * nnz * k if not sim else 2.0 * local_nnz * k
@@ -507,53 +544,56 @@ def main():
                 "prelaid": bool(sharded and shard.prelaid),
                 "chunks": f"{local_adj.num_chunks} x {local_adj.chunk_size} nnz",
             },
-            "check": {"rel_err": rel_all, "tol": TOL, "rows_per_rank": int(checked), "passed": not check_failed,
-                      "what": ("the layer right behind the timed ones (same pipeline, outside the clock)" if sharded else "last timed step's output")
-                              + (" vs fp64 evaluation of EVERY output row (n <= 3 M: the full matrix" if full_check else
-                                 " vs fp64 evaluation of sampled rows (n > 3 M") + "; torch, gcn_amd/check.py), max over ranks",
-                      "rows_total": int(local_m), "full_matrix": bool(full_check)},
-            "roofline": {
-                "bound": "l2" if l2_bound else "hbm",
-                "kernel": kname,
-                "slices": local_adj.num_slices,
-                # SURVEY §8(d) contract figure: one gathered feature row per non-zero charged to HBM
-                "achieved": round(achieved / 1e9, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                "algorithmic_over_hbm_peak": frac_alg,
-                "algorithmic_note": ("not a roofline fraction here: most gathered rows are served by L2, so the contract's byte "
-                                     "count exceeds what crosses any one interface") if l2_bound else
-                                    "the table is far larger than the caches: this IS the fraction of the HBM roofline (frac)",
-                # the physically bounded fraction of the wall this kernel is bound by
-                "frac": frac_l2 if l2_bound else frac_alg,
-                "frac_of": ("L2->CU gather path: gathered feature-row bytes per launch / kernel time / 34.5 TB/s "
-                            "(MI355X_MICROARCH.md §L2) - the wall the sliced kernel is bound by (texture addressers busy 85 %)")
-                           if l2_bound else "HBM: SURVEY §8(d) algorithmic bytes per launch / kernel time / 8.0 TB/s",
-                "frac_l2": frac_l2,
-                "gathered_bytes_per_launch": int(gathered),
-                "frac_fabric": None if traffic is None or kavg <= 0 else round(traffic / kavg / FABRIC_GATHER_CEILING, 4),
-                "fabric_ceiling": "8.6 TB/s: random 256-byte-row gathers from an Infinity-Cache-resident table (MI355X_MICROARCH.md)",
-                "frac_hbm_compulsory": round(compulsory / spmm_avg / HBM_PEAK, 4) if spmm_avg > 0 else None,
-                "algorithmic_bytes_per_launch": int(balg),
-                "compulsory_bytes_per_spmm": int(compulsory),
-                "launches_per_spmm": passes, "columns_per_launch": cols_per_launch, "concurrent_planes": concurrent,
-                "frac_note": None if concurrent == 1 else "planes run concurrently: frac / frac_l2 / algorithmic_over_hbm_peak are "
-                             "taken over the whole layer (all planes' bytes / ms_per_step), kernel_ms_avg stays per plane launch",
-                "kernel_ms_avg": round(kavg * 1e3, 4),
-                "spmm_ms_min": round(min(kernel_ms), 4) if kernel_ms else None,
-                "spmms_timed": len(kernel_ms),
-                "timing": "HIP events recorded by libgcnspmm on the launch stream around the main-kernel "
-                          "passes of every timed SpMM (gcn_spmm_profile_begin/_end)",
-                "traffic": traffic,
-                "traffic_GBps": None if traffic is None or kavg <= 0 else round(traffic / kavg / 1e9, 1),
-                "traffic_over_compulsory": None if traffic is None else round(traffic / compulsory, 3),
-                "l2_hit_rate": pmc_hit,
-                "traffic_source": "not collected in this run" if traffic is None else
-                f"committed profile of this same command and kernel, NOT measured in this run: {pmc_src} "
-                "(separate rocprofv3 --pmc passes; FETCH_SIZE x2 gfx950 correction + WRITE_SIZE; L2-miss bytes incl. "
-                "Infinity-Cache hits)",
-                "weighted": weighted_ms,
-            },
-            "gflops_kernel_only": round(2.0 * local_nnz * kp / spmm_avg / 1e9, 1) if spmm_avg > 0 else None,
         }
+        if args.full:
+            line.update({
+                "check": {"rel_err": rel_all, "tol": TOL, "rows_per_rank": int(checked), "passed": not check_failed,
+                          "what": ("the layer right behind the timed ones (same pipeline, outside the clock)" if sharded else "last timed step's output")
+                                  + (" vs fp64 evaluation of EVERY output row (n <= 3 M: the full matrix" if full_check else
+                                     " vs fp64 evaluation of sampled rows (n > 3 M") + "; torch, gcn_amd/check.py), max over ranks",
+                          "rows_total": int(local_m), "full_matrix": bool(full_check)},
+                "roofline": {
+                    "bound": "l2" if l2_bound else "hbm",
+                    "kernel": kname,
+                    "slices": local_adj.num_slices,
+                    # SURVEY §8(d) contract figure: one gathered feature row per non-zero charged to HBM
+                    "achieved": round(achieved / 1e9, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                    "algorithmic_over_hbm_peak": frac_alg,
+                    "algorithmic_note": ("not a roofline fraction here: most gathered rows are served by L2, so the contract's byte "
+                                         "count exceeds what crosses any one interface") if l2_bound else
+                                        "the table is far larger than the caches: this IS the fraction of the HBM roofline (frac)",
+                    # the physically bounded fraction of the wall this kernel is bound by
+                    "frac": frac_l2 if l2_bound else frac_alg,
+                    "frac_of": ("L2->CU gather path: gathered feature-row bytes per launch / kernel time / 34.5 TB/s "
+                                "(MI355X_MICROARCH.md §L2) - the wall the sliced kernel is bound by (texture addressers busy 85 %)")
+                               if l2_bound else "HBM: SURVEY §8(d) algorithmic bytes per launch / kernel time / 8.0 TB/s",
+                    "frac_l2": frac_l2,
+                    "gathered_bytes_per_launch": int(gathered),
+                    "frac_fabric": None if traffic is None or kavg <= 0 else round(traffic / kavg / FABRIC_GATHER_CEILING, 4),
+                    "fabric_ceiling": "8.6 TB/s: random 256-byte-row gathers from an Infinity-Cache-resident table (MI355X_MICROARCH.md)",
+                    "frac_hbm_compulsory": round(compulsory / spmm_avg / HBM_PEAK, 4) if spmm_avg > 0 else None,
+                    "algorithmic_bytes_per_launch": int(balg),
+                    "compulsory_bytes_per_spmm": int(compulsory),
+                    "launches_per_spmm": passes, "columns_per_launch": cols_per_launch, "concurrent_planes": concurrent,
+                    "frac_note": None if concurrent == 1 else "planes run concurrently: frac / frac_l2 / algorithmic_over_hbm_peak are "
+                                 "taken over the whole layer (all planes' bytes / ms_per_step), kernel_ms_avg stays per plane launch",
+                    "kernel_ms_avg": round(kavg * 1e3, 4),
+                    "spmm_ms_min": round(min(kernel_ms), 4) if kernel_ms else None,
+                    "spmms_timed": len(kernel_ms),
+                    "timing": "HIP events recorded by libgcnspmm on the launch stream around the main-kernel "
+                              "passes of every timed SpMM (gcn_spmm_profile_begin/_end)",
+                    "traffic": traffic,
+                    "traffic_GBps": None if traffic is None or kavg <= 0 else round(traffic / kavg / 1e9, 1),
+                    "traffic_over_compulsory": None if traffic is None else round(traffic / compulsory, 3),
+                    "l2_hit_rate": pmc_hit,
+                    "traffic_source": "not collected in this run" if traffic is None else
+                    f"committed profile of this same command and kernel, NOT measured in this run: {pmc_src} "
+                    "(separate rocprofv3 --pmc passes; FETCH_SIZE x2 gfx950 correction + WRITE_SIZE; L2-miss bytes incl. "
+                    "Infinity-Cache hits)",
+                    "weighted": weighted_ms,
+                },
+                "gflops_kernel_only": round(2.0 * local_nnz * kp / spmm_avg / 1e9, 1) if spmm_avg > 0 else None,
+            })
         if order != "none":
             line["config"]["ordering_seconds"] = round(order_secs, 3)
         if not sharded:
@@ -570,7 +610,7 @@ def main():
                 "note": "a 6x aggregate at N = 8 needs (rank share + unhidden exchange) <= ms_per_step(N = 1) / 6; "
                         "ms_per_step(N = 1) is the driver's own N = 1 run (2.66-2.70 ms in round 4 -> 0.443-0.450 ms)",
             }
-        if not sharded and not args.no_cpu_baseline and not check_failed:
+        if args.full and not sharded and not args.no_cpu_baseline and not check_failed:
             line["cpu_baseline"] = cpu_baseline(rowptr, col, val, n, k, H, args.graph)
         print(json.dumps(line), flush=True)
 

@@ -9,6 +9,9 @@ Regenerates tests/golden/*.npz from the REFERENCE ITSELF, in the build container
   perm_apply through the reference's C ABI, renumber.cu:23,157,233,319) and
   oracle/_ref/libref_orders.so (order_deg / order_rcm / complete_gorder) — both
   compiled from the reference's sources by oracle/Makefile.
+* refbuild_<graph>.npz — the same reorderers' outputs on the larger random graphs of
+  tests/util.py (ref_build_graphs): permutations and orders in full, the inputs and the
+  renumbered CSRs as digests (`--ref-build-only` writes just these).
 * gcn1_<case>.npz — Â, X, seeded weights and the layer outputs of the Python
   reference's own 2-layer GCN on CPU (pygcn/gcn1.py:40-58,102-126 with
   utils.normalize_adj_tensor, utils.py:78-90,126-135), i.e. outputs of the
@@ -141,6 +144,40 @@ def gen_reorder():
         print("wrote reorder_%s.npz (n=%d nnz=%d)" % (name, n, nnz), flush=True)
 
 
+def gen_reorder_ref_build():
+    """refbuild_<graph>.npz: the reference build's outputs on the larger random graphs of tests/util.py
+    (ref_build_graphs).  The graphs are regenerated from their seeds, so only a digest of each input is kept; the
+    renumbered CSRs are kept as digests too (util.arrays_sha256), the permutations and orders in full."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from util import arrays_sha256, ref_build_graphs
+    ref = ctypes.CDLL(os.path.join(HERE, "_ref", "renumber_ref.so"))
+    refo = ctypes.CDLL(os.path.join(HERE, "_ref", "libref_orders.so"))
+    for name, (rp, ci, va) in ref_build_graphs():
+        n, nnz = len(rp) - 1, len(ci)
+        rec = dict(input_sha256=arrays_sha256(rp, ci, va))
+        for fn in ("dfs", "gorder", "rabbit"):
+            a = [rp.copy(), ci.copy(), va.copy(), np.arange(n, dtype=np.int32)]
+            getattr(ref, fn)(_p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), n, n, nnz)
+            rec[f"{fn}_vomp"] = a[3]
+            rec[f"{fn}_csr_sha256"] = arrays_sha256(*a[:3])
+        for which, wname in enumerate(("total", "out", "in")):
+            for desc in (0, 1):
+                o = np.zeros(n, np.int64)
+                refo.ref_order_deg(_p(rp), _p(ci), n, nnz, which, desc, _p(o))
+                rec[f"deg_{wname}_{'desc' if desc else 'asc'}"] = o.astype(np.int32)
+        for directed in (0, 1):
+            o = np.zeros(n, np.int64)
+            refo.ref_order_rcm(_p(rp), _p(ci), n, nnz, directed, _p(o))
+            rec[f"rcm_{'directed' if directed else 'undirected'}"] = o.astype(np.int32)
+        for w in (2, 3, 7):
+            o = np.zeros(n, np.int64)
+            refo.ref_complete_gorder(_p(rp), _p(ci), n, nnz, w, _p(o))
+            rec[f"gorder_w{w}"] = o.astype(np.int32)
+        np.savez_compressed(os.path.join(OUT, f"refbuild_{name}.npz"), **rec)
+        print("wrote refbuild_%s.npz (n=%d nnz=%d)" % (name, n, nnz), flush=True)
+
+
 def gen_gcn1():
     import torch
     sys.path.insert(0, REF)
@@ -241,9 +278,13 @@ if __name__ == "__main__":
     if "--train-only" in sys.argv:
         gen_gcn1_train()
         sys.exit(0)
+    if "--ref-build-only" in sys.argv:
+        gen_reorder_ref_build()
+        sys.exit(0)
     if not os.path.isdir(REF):
         sys.exit("needs /root/reference (build container only)")
     os.makedirs(OUT, exist_ok=True)
     gen_reorder()
+    gen_reorder_ref_build()
     gen_gcn1()
     gen_gcn1_train()

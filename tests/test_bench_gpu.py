@@ -1,6 +1,6 @@
-"""bench.py end to end on a shrunken graph: the default invocation (with the CPU baseline leg), the
-row-sharded path on one rank and the simulated rank share must all print the one JSON line the driver
-parses.  (--scale invalidates the metric; this only guards the plumbing.)"""
+"""bench.py end to end on a shrunken graph: the plain invocation and its output dump, the --full invocation (with the
+CPU baseline leg), the row-sharded path on one rank and the simulated rank share must all print the one JSON line the
+driver parses.  (--scale invalidates the metric; this only guards the plumbing.)"""
 import json
 import os
 import subprocess
@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _bench(*flags):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "0.02", "--steps", "2",
-                          "--warmup", "1", *flags], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          "--warmup", "1", "--full", *flags], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -41,6 +41,42 @@ def test_default_invocation_prints_the_contract_line_with_roofline_and_cpu_basel
     assert 0 < d["config"]["plan_build_seconds"] < 60           # device CSR -> plan + first SpMM, outside the timed steps
 
 
+def test_plain_invocation_prints_the_headline_only_and_dumps_the_timed_output(tmp_path):
+    """a plain run does only what the headline figure needs: no check, roofline or CPU baseline in its line.  Its
+    --dump-outputs file is the last timed step's output, here every row of it, and equals Â·H for the seeded inputs
+    regenerated in this process"""
+    import numpy as np
+    import torch
+    from gcn_amd import graphgen
+    from gcn_amd.check import sampled_rows_rel_err
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "0.02", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "GFLOP/s" and d["dtype"] == "f32" and d["higher_is_better"] is True and d["value"] > 0
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    for key in ("check", "roofline", "cpu_baseline", "gflops_kernel_only"):
+        assert key not in d, key
+    n, k = d["config"]["n"], d["config"]["k"]
+    C = np.load(tmp_path / "C.npy")
+    assert C.dtype == np.float32 and C.shape == (n, k)
+    dev = torch.device("cuda:0")
+    rowptr, col, val, _ = graphgen.make_graph("reddit", device=dev, seed=1, scale=0.02)
+    H = graphgen.random_features(n, k, seed=2, device=dev)
+    rel, rows = sampled_rows_rel_err(rowptr, col, val, H, torch.from_numpy(C).to(dev), torch.arange(n))
+    assert rows == n and rel <= 1e-5, rel
+
+
+def test_sharded_run_dumps_its_own_rows(tmp_path):
+    import numpy as np
+    d = _bench("--no-cpu-baseline", "--sim-world", "4", "--dump-outputs", str(tmp_path))
+    C = np.load(tmp_path / "C.npy")
+    assert C.dtype == np.float32 and C.shape == (d["check"]["rows_total"], d["config"]["k"])
+    assert np.isfinite(C).all() and np.abs(C).max() > 0
+
+
 @pytest.mark.parametrize("flags", [("--no-cpu-baseline", "--force-shard"), ("--no-cpu-baseline", "--sim-world", "4"),
                                    ("--no-cpu-baseline", "--sim-world", "4", "--no-plane-streams"),
                                    ("--no-cpu-baseline", "--gather-width", "1", "--blocks-per-cu", "8")])
@@ -59,7 +95,7 @@ def test_config3_and_config5_modes_renumber_then_multiply_and_check(flags, order
     """BASELINE configs 3 and 5 through bench.py at a reduced size: the graph is renumbered by the library's own
     reorderers (device RCM / degree, host Gorder), the SpMM runs on the renumbered matrix and the timed output is
     checked against fp64 on sampled rows; the line says which config it is and that it is not the headline one"""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags, "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags, "--steps", "2", "--warmup", "1", "--full"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -78,7 +114,7 @@ def test_structured_stand_ins_renumbered_by_rabbit_on_the_device_and_autotuned(g
     Rabbit on the device, plan shape chosen by CsrAdjacency.autotune() (slices x column tile), EVERY output row checked against
     fp64 (n <= 3 M), the generator's recipe in the line"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--graph", graph, "--scale", scale, "--order", "rabbit",
-                          "--autotune", "--mixing", "0.3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+                          "--autotune", "--mixing", "0.3", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -94,7 +130,7 @@ def test_papers100m_mode_runs_a_rank_share_built_from_its_own_block():
     """BASELINE config 4 through the product path at a reduced scale: the rank is built by from_row_block from the
     block generator (the whole graph never exists), one GPU computes rank 0's share of the 8-way partition"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--graph", "papers100m", "--scale", "0.002",
-                          "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert d["check"]["passed"] and "8-way partition" in d["config"]["workload"] and d["config"]["n"] == int(111059956 * 0.002)
@@ -109,7 +145,7 @@ def test_two_rank_rehearsal_on_one_gpu_exchanges_and_checks_on_every_rank():
         env = dict(os.environ, GCN_AMD_BENCH_REHEARSAL="1")
         out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                               "--master-addr", "127.0.0.1", "--master-port", "29731", os.path.join(ROOT, "bench.py"),
-                              "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1", "--exchange", exchange],
+                              "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1", "--full", "--exchange", exchange],
                              cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
         assert out.returncode == 0, out.stderr[-3000:]
         d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -125,7 +161,7 @@ def test_four_rank_rehearsal_on_one_gpu(exchange):
     env = dict(os.environ, GCN_AMD_BENCH_REHEARSAL="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
                           "--master-addr", "127.0.0.1", "--master-port", "29751", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "4", "--scale", "0.12", "--steps", "2", "--warmup", "1", "--exchange", exchange],
+                          "--gpus", "4", "--scale", "0.12", "--steps", "2", "--warmup", "1", "--full", "--exchange", exchange],
                          cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -146,7 +182,7 @@ def test_config5_gorder_leg_loads_an_offline_rank_for_the_cpu_generated_graph(tm
                              capture_output=True, text=True, timeout=600)
         assert out.returncode == 0 and os.path.exists(rank_f) and os.path.exists(meta_f), out.stderr[-1500:]
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--graph", "rmat24", "--rmat-scale", "12", "--graph-device", "cpu",
-               "--order", "gorder", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+               "--order", "gorder", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
         out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-1500:]
         d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -171,7 +207,7 @@ def test_two_rank_rehearsal_with_both_planes_on_one_stream(exchange):
     env = dict(os.environ, GCN_AMD_BENCH_REHEARSAL="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29761", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--scale", "0.12", "--steps", "3", "--warmup", "1", "--exchange", exchange,
+                          "--gpus", "2", "--scale", "0.12", "--steps", "3", "--warmup", "1", "--full", "--exchange", exchange,
                           "--no-plane-streams"], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -187,7 +223,7 @@ def test_two_rank_rehearsal_with_the_prelaid_exchange_buffers(exchange):
     env = dict(os.environ, GCN_AMD_BENCH_REHEARSAL="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29741", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--scale", "0.12", "--steps", "3", "--warmup", "1", "--exchange", exchange],
+                          "--gpus", "2", "--scale", "0.12", "--steps", "3", "--warmup", "1", "--full", "--exchange", exchange],
                          cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])

@@ -1,6 +1,6 @@
 """Product reorderers (C++ in libgcnspmm.so, bound through the C ABI): bit-exact against
-(i) the golden vectors recorded from the reference's compiled code, (ii) the reference build
-itself (oracle/_ref, present in the build container) on random graphs, (iii) the independent
+(i) the golden vectors recorded from the reference's compiled code, (ii) the reference build on
+random graphs (its recorded outputs, and the build itself where oracle/_ref exists), (iii) the independent
 Python oracle; plus the invariants the reference asserts (renumber.cu:120-149,283-313)."""
 import ctypes
 import glob
@@ -13,7 +13,7 @@ import scipy.sparse as sp
 
 import gcn_amd
 from gcn_amd import reorder
-from util import GOLDEN, ROOT, sym_norm_graph
+from util import GOLDEN, ROOT, arrays_sha256, ref_build_graphs, sym_norm_graph
 
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import reorder_oracle as ro  # noqa: E402
@@ -50,28 +50,27 @@ def test_bit_exact_vs_reference_golden(path):
     assert np.array_equal(va2, g["gorder_val"]) and np.array_equal(vomp, g["gorder_vomp"])
 
 
-def _graphs():
-    yield "sym_2k", sym_norm_graph(2000, 20000, seed=10)
-    yield "sym_sparse", sym_norm_graph(3000, 4000, seed=11)
-    rng = np.random.default_rng(12)                      # skewed, asymmetric, with self-loops
-    n, e = 1500, 12000
-    u = np.minimum(n - 1, (n * rng.random(e) ** 2.5).astype(int)); v = rng.integers(0, n, e)
-    A = sp.coo_matrix((np.ones(e), (u, v)), shape=(n, n)).tocsr(); A = (A + sp.eye(n)).tocsr()
-    A.data[:] = rng.random(A.nnz) + 0.1; A.sort_indices()
-    yield "directed_skewed", (A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float32))
-    # R-MAT, products-shaped degree skew (hub rows, many equal dQ candidates): the case where Rabbit's
-    # "first maximum in key order" tie rule and the equal-degree introsort permutation really matter
-    from gcn_amd import graphgen
-    rowptr, col, val, _ = graphgen.make_graph("products", device="cpu", seed=3, scale=0.006)
-    yield "rmat_products_shaped", (rowptr.numpy(), col.numpy(), val.numpy())
-
-
-@pytest.mark.skipif(not (os.path.exists(REF_SO) and os.path.exists(REF_ORD)),
-                    reason="oracle/_ref not built (needs /root/reference; build container only)")
-@pytest.mark.parametrize("name,graph", list(_graphs()), ids=[n for n, _ in _graphs()])
+@pytest.mark.parametrize("name,graph", list(ref_build_graphs()), ids=[n for n, _ in ref_build_graphs()])
 def test_bit_exact_vs_reference_build_on_random_graphs(name, graph, capfd):
+    """against the reference build's outputs recorded on these graphs (tests/golden/refbuild_<name>.npz,
+    oracle/make_golden.py) and, where oracle/_ref is built, against that build run here as well"""
     rp, ci, va = graph
     n, nnz = len(rp) - 1, len(ci)
+    g = np.load(os.path.join(GOLDEN, f"refbuild_{name}.npz"))
+    assert arrays_sha256(rp, ci, va) == str(g["input_sha256"]), "the generator no longer makes the recorded graph"
+    for fn in ("dfs", "gorder", "rabbit"):
+        b = getattr(reorder, fn)(rp, ci, va)
+        assert np.array_equal(b[3], g[f"{fn}_vomp"]), fn
+        assert arrays_sha256(*b[:3]) == str(g[f"{fn}_csr_sha256"]), fn
+    for wname in ("total", "out", "in"):
+        for desc in (False, True):
+            assert np.array_equal(reorder.order_deg(rp, ci, wname, desc), g[f"deg_{wname}_{'desc' if desc else 'asc'}"])
+    for d in (False, True):
+        assert np.array_equal(reorder.order_rcm(rp, ci, d), g[f"rcm_{'directed' if d else 'undirected'}"])
+    for w in (2, 3, 7):
+        assert np.array_equal(reorder.order_gorder(rp, ci, w), g[f"gorder_w{w}"])
+    if not (os.path.exists(REF_SO) and os.path.exists(REF_ORD)):
+        return
     ref, refo = ctypes.CDLL(REF_SO), ctypes.CDLL(REF_ORD)
     p = lambda a: ctypes.c_void_p(a.ctypes.data)
     for fn in ("dfs", "gorder", "rabbit"):

@@ -69,6 +69,35 @@ def sym_norm_graph(n, e, seed):
     return A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float32)
 
 
+def ref_build_graphs():
+    """the random graphs the reorderers are compared with the reference build on (tests/test_reorder.py); their
+    recorded outputs are tests/golden/refbuild_<name>.npz (oracle/make_golden.py)"""
+    yield "sym_2k", sym_norm_graph(2000, 20000, seed=10)
+    yield "sym_sparse", sym_norm_graph(3000, 4000, seed=11)
+    rng = np.random.default_rng(12)                      # skewed, asymmetric, with self-loops
+    n, e = 1500, 12000
+    u = np.minimum(n - 1, (n * rng.random(e) ** 2.5).astype(int)); v = rng.integers(0, n, e)
+    A = sp.coo_matrix((np.ones(e), (u, v)), shape=(n, n)).tocsr(); A = (A + sp.eye(n)).tocsr()
+    A.data[:] = rng.random(A.nnz) + 0.1; A.sort_indices()
+    yield "directed_skewed", (A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float32))
+    # R-MAT, products-shaped degree skew (hub rows, many equal dQ candidates): the case where Rabbit's
+    # "first maximum in key order" tie rule and the equal-degree introsort permutation really matter
+    from gcn_amd import graphgen
+    rowptr, col, val, _ = graphgen.make_graph("products", device="cpu", seed=3, scale=0.006)
+    yield "rmat_products_shaped", (rowptr.numpy(), col.numpy(), val.numpy())
+
+
+def arrays_sha256(*arrays):
+    """one digest of dtypes, shapes and bytes: how the golden files record outputs too large to store"""
+    import hashlib
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(f"{a.dtype.str}{a.shape}".encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
 def sampled_rows_oracle_err(rowptr_dev, col_dev, val_dev, B_dev, C_dev, rows):
     """rel. error of C_dev[rows] against the fp64 C oracle on a compacted copy of the sampled rows: only the rows
     of B the sample references travel to the host (full-size configs: B has tens of GB).  All *_dev are torch

@@ -11,7 +11,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 for v in "${vals[@]}"; do
   export $name=$v
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$v -- python3 bench.py --no-cpu-baseline "$@" > $out/bench_$v.json 2> $out/rocprof_$v.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$v -- python3 bench.py --full --no-cpu-baseline "$@" > $out/bench_$v.json 2> $out/rocprof_$v.err
   find $out/stats_$v -name "*kernel_trace.csv" -delete
   f=$(find $out/stats_$v -name "*kernel_stats.csv" | head -1)
   echo "== $name=$v" | tee -a $out/log.txt

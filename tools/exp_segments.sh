@@ -5,7 +5,7 @@
 out=$1; segs=$2; shift 2
 mkdir -p $out
 for seg in $segs; do
-  GCN_AMD_GROUP_SEGMENTS=$seg python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline "$@" > $out/b_${seg}.json 2> $out/b_${seg}.err || { echo "seg $seg FAILED"; tail -2 $out/b_${seg}.err; continue; }
+  GCN_AMD_GROUP_SEGMENTS=$seg python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline "$@" > $out/b_${seg}.json 2> $out/b_${seg}.err || { echo "seg $seg FAILED"; tail -2 $out/b_${seg}.err; continue; }
   python3 - $out/b_${seg}.json $seg <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][0])

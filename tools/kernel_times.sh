@@ -6,7 +6,7 @@ out=gpurun_out/${1:-r02zx}
 mkdir -p $out
 timeout -k 10 300 python3 -m pytest tests/test_spmm_gpu.py tests/test_layers_gpu.py -x -q -k "slic or dropout or value_free or fused or epilogue" > $out/pytest.log 2>&1 || { tail -30 $out/pytest.log; exit 1; }
 tail -2 $out/pytest.log
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/rocprof.err
 f=$(find $out/stats -name "*kernel_stats.csv" | head -1)
 python3 - "$f" <<'PY' | tee -a $out/log.txt
 import csv, sys

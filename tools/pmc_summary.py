@@ -6,7 +6,7 @@ WRITE_SIZE 2; never combined with the hip/hsa trace domains):
 
     for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
       rocprofv3 --pmc $c --kernel-trace --output-format csv -d gpurun_out/pmc_<tag>_$c -- \
-          python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
+          python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline
     done
     python tools/pmc_summary.py --glob 'gpurun_out/pmc_<tag>_*' --graph reddit --k 128 \
         --launches-per-spmm 2 --out profiles/pmc_latest.json

@@ -10,14 +10,14 @@ export TMPDIR=/tmp
 out=gpurun_out/$tag
 mkdir -p $out
 cpu="--no-cpu-baseline"; [ "${GCN_PROFILE_CPU:-0}" == "1" ] && cpu=""
-python3 bench.py "$@" $cpu > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+python3 bench.py --full "$@" $cpu > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 tail -c 600 $out/bench.json; echo
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py "$@" --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/rocprof.err || { tail -20 $out/rocprof.err; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full "$@" --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/rocprof.err || { tail -20 $out/rocprof.err; exit 1; }
 find $out/stats -name "*kernel_stats.csv" -exec head -6 {} \; | cut -c1-220
 find $out/stats -name "*kernel_trace.csv" -delete      # (the stats table is what is kept: gpurun_out merges back <= 64 MiB)
 for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
   d=$out/pmc_$(echo $c | tr ' ' '_')
-  rocprofv3 --pmc $c --kernel-trace --kernel-include-regex "gcn::" --output-format csv -d $d -- python3 bench.py "$@" --steps 3 --warmup 1 --no-cpu-baseline > $d.json 2> $d.err || { tail -20 $d.err; exit 1; }
+  rocprofv3 --pmc $c --kernel-trace --kernel-include-regex "gcn::" --output-format csv -d $d -- python3 bench.py --full "$@" --steps 3 --warmup 1 --no-cpu-baseline > $d.json 2> $d.err || { tail -20 $d.err; exit 1; }
   find $d -name "*kernel_trace.csv" -delete; find $d -name "*agent_info.csv" -delete
   echo "pmc $c done"
 done
