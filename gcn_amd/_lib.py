@@ -18,6 +18,7 @@ class GcnAmdError(RuntimeError):
 
 ERR_NOT_FACTORED = 6         # GCN_ERR_NOT_FACTORED
 ERR_INTERNAL = 7             # GCN_ERR_INTERNAL (a consistency guard tripped: gcn_order_rabbit_device)
+DTYPE_F32, DTYPE_BF16 = 0, 1 # GCN_DTYPE_F32 / GCN_DTYPE_BF16 (gcn_spmm_csr_bf16_epilogue)
 
 
 _c_i32 = ctypes.c_int32
@@ -38,6 +39,10 @@ SIGNATURES = {
     "gcn_spmm_csr_f32_epilogue": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i32, ctypes.c_float,
                                                  ctypes.c_uint64, ctypes.c_uint64, _c_i32, _c_p]),
     "gcn_dropout_f32": (ctypes.c_int, [_c_p, _c_p, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _c_p]),
+    "gcn_spmm_csr_bf16_epilogue": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_p, _c_i32, ctypes.c_float,
+                                                  ctypes.c_uint64, ctypes.c_uint64, _c_i32, _c_p]),
+    "gcn_spmm_csr_bf16": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_p]),
+    "gcn_dropout_bf16": (ctypes.c_int, [_c_p, _c_p, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _c_p]),
     "gcn_spmm_plan_set_tile_cols": (ctypes.c_int, [_c_p, _c_i32]),
     "gcn_spmm_plan_set_blocks_per_cu": (ctypes.c_int, [_c_p, _c_i32]),
     "gcn_spmm_plan_set_gather_width": (ctypes.c_int, [_c_p, _c_i32]),
@@ -50,6 +55,7 @@ SIGNATURES = {
     "gcn_exchange_wait": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_i32, _c_p, ctypes.c_double, _c_p]),
     "gcn_spmm_plan_num_passes": (_c_i32, [_c_p, _c_i32]),
     "gcn_spmm_plan_main_kernel": (ctypes.c_int, [_c_p, _c_i32, _c_i32, ctypes.c_char_p, _c_i32]),
+    "gcn_spmm_plan_main_kernel_bf16": (ctypes.c_int, [_c_p, _c_i32, _c_i32, ctypes.c_char_p, _c_i32]),
     "gcn_spmm_plan_enable_slicing": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_p]),
     "gcn_spmm_plan_num_slices": (_c_i32, [_c_p]),
     "gcn_spmm_plan_narrow_slices": (_c_i32, [_c_p, _c_i32]),

@@ -275,6 +275,91 @@ int gcn_dropout_f32(float* dst, const float* src, int64_t count, float dropout_p
   return launch_dropout(dst, src, (long long)count, d, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
 }
 
+// bf16 operands: B is bf16, C fp32 or bf16 (c_dtype), every sum fp32.  The hot path (bf16_route, plan_policy.cpp) re-lays B
+// as a bf16 table in the group kernels' slice layout, walks it with the bf16 group kernel into the fp32 partial rows and
+// reduces them with the whole epilogue, rounding once when C is bf16.  Every other plan and width takes the fallback: B
+// widened to fp32, the fp32 entry above with its whole epilogue (into C itself when C is fp32), the result narrowed.
+// Correct everywhere, fast only on the hot path.
+int gcn_spmm_csr_bf16_epilogue(gcn_spmm_plan_t* p, const int32_t* rowptr, const int32_t* col, const float* val,
+                               const void* B, void* C, int32_t c_dtype, const float* bias, int32_t relu,
+                               float dropout_p, uint64_t seed, uint64_t offset, int32_t k, void* stream) {
+  if (!p || k < 0 || !(dropout_p >= 0.f && dropout_p < 1.f)) return GCN_ERR_INVALID_ARG;
+  if (c_dtype != GCN_DTYPE_F32 && c_dtype != GCN_DTYPE_BF16) return GCN_ERR_INVALID_ARG;
+  if (p->m == 0 || k == 0) return GCN_OK;
+  if (!C || !rowptr || (p->nnz > 0 && (!col || !val || !B))) return GCN_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned short* Bh = static_cast<const unsigned short*>(B);
+  const Bf16Route rt = bf16_route(p, k, /*build=*/true, rowptr, col, val, st);
+  if (!rt.group) {
+    float* Cf = static_cast<float*>(C);
+    if (c_dtype == GCN_DTYPE_BF16) {
+      if (grow(p->cwide, (size_t)p->m * (size_t)k) != GCN_OK) return GCN_ERR_ALLOC;
+      Cf = p->cwide;
+    }
+    const float* Bf = nullptr;
+    if (p->nnz > 0) {
+      if (grow(p->bwide, (size_t)p->n * (size_t)k) != GCN_OK) return GCN_ERR_ALLOC;
+      if (launch_bf16_to_f32(p->bwide, Bh, (long long)p->n * k, st) != hipSuccess) return GCN_ERR_HIP;
+      Bf = p->bwide;
+    }
+    const int rc = gcn_spmm_csr_f32_epilogue(p, rowptr, col, val, Bf, Cf, bias, relu, dropout_p, seed, offset, k, stream);
+    if (rc != GCN_OK || c_dtype == GCN_DTYPE_F32) return rc;
+    return launch_f32_to_bf16(static_cast<unsigned short*>(C), Cf, (long long)p->m * k, st) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+  }
+  // hot path: the bf16 table reuses the bytes of the plan's fp32 copy of B
+  const SliceSet& ss = rt.ss;
+  const GroupStream& G = *ss.g;
+  const size_t table_elems = (size_t)ss.table_rows() * (size_t)rt.ldh;      // bf16 entries
+  if (grow(p->bpad, (table_elems + 1) / 2) != GCN_OK) return GCN_ERR_ALLOC;
+  unsigned short* table = reinterpret_cast<unsigned short*>(p->bpad.get());
+  if (launch_relay_bf16_sliced(table, Bh, rt.weighted ? nullptr : p->factors.u_col, p->n, k, rt.ldh, ss.S, G.w, st) != hipSuccess)
+    return GCN_ERR_HIP;
+  if (grow(p->ws, ws_elems(p, k)) != GCN_OK) return GCN_ERR_ALLOC;
+  if (grow(p->cv, (size_t)ss.S * (size_t)p->m * (size_t)k) != GCN_OK) return GCN_ERR_ALLOC;
+  GroupArgs ga;
+  ga.stream = G.stream; ga.chunk_meta = G.chunk_meta;
+  ga.vals = rt.weighted ? G.vals.get() : nullptr;
+  ga.Bp = nullptr; ga.Cv = p->cv; ga.P = p->ws;
+  ga.nchunks = G.nchunks; ga.T = G.T; ga.k = k; ga.ldb = rt.ldh;
+  ga.table_rows = ss.table_rows();
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;             // live timing of the main kernel (gcn_spmm_profile_begin)
+  if (p->prof.armed()) { const auto pr = p->prof.next(); ev0 = pr.first; ev1 = pr.second; }
+  if (ev0 && hipEventRecord(ev0, st) != hipSuccess) return GCN_ERR_HIP;
+  if (launch_spmm_group_bf16(ga, table, st) != hipSuccess) return GCN_ERR_HIP;
+  if (ev1 && hipEventRecord(ev1, st) != hipSuccess) return GCN_ERR_HIP;
+  CutLists cuts;                                       // (as spmm_impl)
+  if (group_fused_fixup() && G.cutptr) { cuts.ptr = G.cutptr; cuts.chunk = G.cutchunk; cuts.P = p->ws; }
+  else if (launch_group_fixup(G.fix, G.nfix, p->ws, p->cv, k, st) != hipSuccess) return GCN_ERR_HIP;
+  DropoutSpec drop;
+  drop.p = dropout_p; drop.seed = seed; drop.offset = offset;
+  const float* rowscale = rt.weighted ? nullptr : p->factors.u_row.get();
+  const hipError_t e = c_dtype == GCN_DTYPE_F32
+      ? launch_slice_reduce(p->cv, static_cast<float*>(C), bias, relu ? 1 : 0, p->m, ss.S, k, st, 0, rowscale, drop, nullptr,
+                            nullptr, 0, cuts)
+      : launch_slice_reduce_bf16(p->cv, static_cast<unsigned short*>(C), bias, relu ? 1 : 0, p->m, ss.S, k, rowscale, drop, cuts, st);
+  return e == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_spmm_csr_bf16(gcn_spmm_plan_t* p, const int32_t* rowptr, const int32_t* col, const float* val, const void* B, void* C,
+                      int32_t c_dtype, int32_t k, void* stream) {
+  return gcn_spmm_csr_bf16_epilogue(p, rowptr, col, val, B, C, c_dtype, nullptr, 0, 0.f, 0, 0, k, stream);
+}
+
+int gcn_dropout_bf16(void* dst, const void* src, int64_t count, float dropout_p, uint64_t seed, uint64_t offset, void* stream) {
+  if (count < 0 || !(dropout_p >= 0.f && dropout_p < 1.f)) return GCN_ERR_INVALID_ARG;
+  if (count == 0) return GCN_OK;
+  if (!dst || !src) return GCN_ERR_INVALID_ARG;
+  DropoutSpec d;
+  d.p = dropout_p; d.seed = seed; d.offset = offset;
+  if (!d.on()) {
+    if (dst == src) return GCN_OK;
+    return hipMemcpyAsync(dst, src, 2 * (size_t)count, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess
+               ? GCN_OK : GCN_ERR_HIP;
+  }
+  return launch_dropout_bf16(static_cast<unsigned short*>(dst), static_cast<const unsigned short*>(src), (long long)count, d,
+                             (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
 int gcn_spmm_profile_begin(gcn_spmm_plan_t* p, int32_t capacity) {
   if (!p || capacity <= 0 || p->prof.capacity() > 0) return GCN_ERR_INVALID_ARG;
   return p->prof.begin(capacity) == hipSuccess ? GCN_OK : GCN_ERR_HIP;   // (a failed create leaves no events behind)

@@ -148,6 +148,7 @@ struct gcn_spmm_plan {
   gcn::DevBuf<float> cv;                            // partial outputs [S*m x k], grow-only
   gcn::DevBuf<float> bpad;                          // B re-laid (rows padded to whole lines and/or scaled by u_col), grow-only
   gcn::DevBuf<float> cpad;                          // result with k rounded up to a multiple of 4 (k % 4 != 0), grow-only
+  gcn::DevBuf<float> bwide, cwide;                  // bf16 calls on the fallback: B widened to fp32, the fp32 result before narrowing
   gcn::DevBuf<int> dyn;                             // drop-in flexspmm: {recognised, chunks, cut rows, 0} of the current call (device)
   gcn::EventPairs prof;
   int tile_cols = 0;                                // 0 = auto

@@ -290,6 +290,32 @@ SliceSet pick_slice_set(gcn_spmm_plan* p, int k, int* ldb, bool* relay, bool bui
   return s;
 }
 
+// bf16 operands (spmm_group_bf16.hip): widths k >= 64 with k % 8 == 0 on a plan that runs a group kernel.  The slice set
+// follows the table's row BYTES, not k: a bf16 call at k takes the set of an fp32 call at k / 2 (k = 64: the narrow set
+// of 128-byte rows, built here at first use like the fp32 k <= 32 one).  Rows of the bf16 table are padded to whole
+// 128-byte lines.  Anything else — unsliced plans, panels, narrow / odd widths — takes the fallback.
+Bf16Route bf16_route(gcn_spmm_plan* p, int k, bool build, const int32_t* rowptr, const int32_t* col, const float* val,
+                     hipStream_t st) {
+  Bf16Route r;
+  if (k < 64 || k % 8 != 0 || p->nnz <= 0 || p->panels.R != 0 || !p->group.ready()) return r;
+  const int ldh = (k + 63) / 64 * 64;
+  const int kw = k / 2, ldw = ldh / 2;                 // the fp32 width and stride with the same row bytes
+  const bool valless = valless_pays(p, kw, ldw);
+  const bool weighted = !valless && weighted_pass(p, kw, ldw);
+  if (!group_launch(p, valless, weighted)) return r;
+  SliceSet ss = own_slice_set(p);
+  if (valless) {
+    int ld = ldw;
+    bool relay = false;                                // (the five-engine kernel's 48-float rows: an fp32 matter only)
+    ss = pick_slice_set(p, kw, &ld, &relay, build, rowptr, col, val, st);
+  }
+  const GroupStream* g = ss.g;
+  if (!g || !g->ready() || g->nchunks % 32 != 0 || g->T < 64 || g->T % 64 != 0) return r;
+  if (spmm_group_bf16_needs_big(ss.table_rows(), ldh) && ldh * 2 >= (1 << 17)) return r;
+  r.group = true; r.weighted = weighted; r.ss = ss; r.ldh = ldh;
+  return r;
+}
+
 }  // namespace gcn
 
 using namespace gcn;
@@ -357,6 +383,16 @@ int gcn_spmm_plan_main_kernel(const gcn_spmm_plan_t* p, int32_t k, int32_t epilo
     return GCN_OK;
   }
   describe_main_kernel(a, buf, (size_t)buflen);
+  return GCN_OK;
+}
+
+int gcn_spmm_plan_main_kernel_bf16(const gcn_spmm_plan_t* p, int32_t k, int32_t epilogue, char* buf, int32_t buflen) {
+  if (!p || k <= 0 || !buf || buflen <= 0) return GCN_ERR_INVALID_ARG;
+  // (the slice set only as it exists: nothing is built here)
+  const Bf16Route r = bf16_route(const_cast<gcn_spmm_plan*>(p), k, /*build=*/false, nullptr, nullptr, nullptr, nullptr);
+  if (!r.group) return gcn_spmm_plan_main_kernel(p, k, epilogue, buf, buflen);    // the fallback runs the fp32 entry
+  const char* bigs = spmm_group_bf16_needs_big(r.ss.table_rows(), r.ldh) ? "true" : "false";
+  snprintf(buf, (size_t)buflen, r.weighted ? "gcn::spmm_group_bf16_weighted_kernel<%s>" : "gcn::spmm_group_bf16_kernel<%s>", bigs);
   return GCN_OK;
 }
 

@@ -48,6 +48,17 @@ bool odd_width_detour(const gcn_spmm_plan* p, int k);
 SliceSet pick_slice_set(gcn_spmm_plan* p, int k, int* ldb, bool* relay, bool build, const int32_t* rowptr, const int32_t* col,
                         const float* val, hipStream_t st);
 
+// How a bf16 call at width k runs (api_spmm.cpp, gcn_spmm_csr_bf16_epilogue): on the bf16 group walk (group = true) —
+// value-free or weighted, on the slice set an fp32 call with the same table row BYTES would take (k / 2 columns), from a
+// bf16 table with rows of ldh columns — or, group = false, on the fallback (B widened to fp32, the fp32 entry, C narrowed).
+struct Bf16Route {
+  bool group = false, weighted = false;
+  SliceSet ss;
+  int ldh = 0;
+};
+Bf16Route bf16_route(gcn_spmm_plan* p, int k, bool build, const int32_t* rowptr, const int32_t* col, const float* val,
+                     hipStream_t st);
+
 // plan_build.cpp
 int count_empty(const int* rowptr, int m, int* out, hipStream_t st);
 void build_sliced_streams(gcn_spmm_plan* p, hipStream_t st);

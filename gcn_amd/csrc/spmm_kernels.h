@@ -142,6 +142,18 @@ hipError_t launch_group_fixup(const int* fix, int nfix, const float* P, float* C
 hipError_t launch_scale_rows_sliced(float* dst, const float* src, const float* rowscale, int n, int k, int ld,
                                     int S, int w, hipStream_t s);
 
+// spmm_group_bf16.hip — bf16 feature operands, fp32 accumulation.  The group walk on a bf16 table Bh (the layout of
+// GroupArgs::Bp, rows a.ldb bf16 apart, a.ldb % 8 == 0; a.Bp is not read), k % 8 == 0, partial rows into the fp32 Cv / P.
+hipError_t launch_spmm_group_bf16(const GroupArgs& a, const unsigned short* Bh, hipStream_t s);
+bool spmm_group_bf16_needs_big(long long table_rows, int ldh);   // BIG addressing for a bf16 table (counted in bytes)
+// the bf16 table: rowscale nullptr copies the bits (weighted pass), else bf16(rowscale[c] * src[c, :]) with one RNE rounding
+hipError_t launch_relay_bf16_sliced(unsigned short* dst, const unsigned short* src, const float* rowscale, int n, int k, int ld,
+                                    int S, int w, hipStream_t s);
+hipError_t launch_bf16_to_f32(float* dst, const unsigned short* src, long long count, hipStream_t st);
+hipError_t launch_f32_to_bf16(unsigned short* dst, const float* src, long long count, hipStream_t st);
+hipError_t launch_dropout_bf16(unsigned short* dst, const unsigned short* src, long long count, const DropoutSpec& drop,
+                               hipStream_t st);
+
 // spmm_panel.hip — LDS-staged feature tiles per row panel (near-diagonal matrices)
 // cnt_dev (optional, [panels]): in-window non-zeros of every panel
 hipError_t panel_plan(const int* rowptr, const int* col, int m, int n, int R, int* w0_dev,
@@ -194,6 +206,10 @@ hipError_t launch_slice_reduce(const float* Cv, float* C, const float* bias, int
                                const DropoutSpec& drop = DropoutSpec{}, const int* guard = nullptr,   // guard: skip when *guard == 0
                                const float* outscale = nullptr, int gap_w = 0,    // pre-laid output: row r -> r + r / gap_w, times outscale[r]
                                const CutLists& cuts = CutLists{});
+// launch_slice_reduce with a bf16 result (k % 4 == 0; no accumulate / pre-laid output): the same sums in the same order,
+// the same epilogue, one RNE rounding at the end
+hipError_t launch_slice_reduce_bf16(const float* Cv, unsigned short* C, const float* bias, int relu, int m, int S, int k,
+                                    const float* rowscale, const DropoutSpec& drop, const CutLists& cuts, hipStream_t st);
 // dst[i] = dropout(src[i]) for i < total, mask from the flat index i (dst may be src)
 hipError_t launch_dropout(float* dst, const float* src, long long total, const DropoutSpec& drop, hipStream_t st);
 // values factor as u[r]*u[c]?  u_out[n] (device), *ok_host = 1 when every stored entry matches within 4 ulp

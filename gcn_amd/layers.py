@@ -25,6 +25,14 @@ from . import preprocess, reorder, timers
 from .spmm import CsrAdjacency, _SpmmFunction, dropout_rows, gather_rows
 
 
+def _spmm_operand(x):
+    """the dense operand of an SpMM inside the model: under a bf16 autocast region the aggregation runs in bf16 like the
+    dense products around it (autocast does not cast the operands of a custom autograd Function by itself)"""
+    if torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16 and x.dtype == torch.float32:
+        return x.to(torch.bfloat16)
+    return x
+
+
 class _FusedSpmmBiasRelu(torch.autograd.Function):
     """out = dropout(relu(Â·X + b)) in one pass over the SpMM output (gcn6.py:141-142, 245-246 as one epilogue);
     backward through the regenerated dropout mask, the ReLU mask, Âᵀ and the bias sum.  dropout = None or
@@ -46,7 +54,8 @@ class _FusedSpmmBiasRelu(torch.autograd.Function):
             g = g * (out > 0)                          # (dropped elements are 0 in `out`, and their gradient is 0 already)
         g = g.contiguous()
         gx = ctx.adj.transpose().matmul_raw(g) if ctx.needs_input_grad[1] else None
-        return None, gx, (g.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None), None, None
+        gb = g.float().sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None     # (fp32 bias, bf16 activations too)
+        return None, gx, gb, None, None
 
 
 class _Layer(nn.Module):
@@ -82,9 +91,9 @@ class GraphConvolution(_Layer):
             support = torch.spmm(input, self.weight) if input.is_sparse else torch.mm(input, self.weight)
         if fuse_epilogue:
             with self.timers.hc.af:
-                return _FusedSpmmBiasRelu.apply(adj, support, self.bias, relu, dropout)
+                return _FusedSpmmBiasRelu.apply(adj, _spmm_operand(support), self.bias, relu, dropout)
         with self.timers.hc.af:
-            output = _SpmmFunction.apply(adj, support)
+            output = _SpmmFunction.apply(adj, _spmm_operand(support))
         if self.bias is not None:
             with self.timers.hc.bi:
                 output = output + self.bias
@@ -96,7 +105,7 @@ class GraphConvolution2(_Layer):
 
     def forward(self, input, adj, relu=False, fuse_epilogue=False):
         with self.timers.hc.af:
-            support = _SpmmFunction.apply(adj, input)
+            support = _SpmmFunction.apply(adj, _spmm_operand(input))
         with self.timers.hc.xw:
             output = torch.mm(support, self.weight)
         if self.bias is not None:
@@ -110,7 +119,7 @@ class GCN(nn.Module):
 
     def __init__(self, nfeat, nhid, nclass, dataset="dataset", dropout=0.5, lr=0.01, weight_decay=5e-4,
                  with_relu=True, with_bias=True, device=None, order="rabbit", fuse_epilogue=False,
-                 layer_order="reference", precompute_ax=False):
+                 layer_order="reference", precompute_ax=False, compute_dtype=torch.float32):
         super().__init__()
         assert device is not None, "Please specify 'device'!"
         self.device, self.nfeat, self.hidden_sizes, self.nclass = device, nfeat, [nhid], nclass
@@ -136,6 +145,12 @@ class GCN(nn.Module):
         # epoch's layer 1 is a dense product — no SpMM in its forward pass and none in its backward pass (W1's gradient is
         # (ÂX)ᵀ·g).  Same function, fp32 rounding apart; n x nfeat floats of memory.  Off by default (the reference recomputes).
         self.precompute_ax = precompute_ax
+        # compute_dtype=torch.bfloat16: the forward passes of fit / forward / test / predict run under
+        # torch.autocast("cuda", bfloat16) — the dense products and the SpMMs (bf16 operands, fp32 sums) in bf16; the
+        # parameters, Adam's state and the loss stay fp32
+        if compute_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("compute_dtype must be torch.float32 or torch.bfloat16")
+        self.compute_dtype = compute_dtype
         self._ax = None
         self.output = None
         self.adj = self.features = self.labels = self.vo_mp = None
@@ -171,13 +186,16 @@ class GCN(nn.Module):
                 h = h + self.gc1.bias
         return F.relu(h) if self.with_relu else h
 
+    def _autocast(self):
+        return torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.compute_dtype == torch.bfloat16)
+
     def forward(self, x, adj):
-        with self.dur_fwd:
+        with self.dur_fwd, self._autocast():
             if self.precompute_ax and x is self.features and adj is self.adj and not x.requires_grad:
                 x = self._layer1_from_cached_ax(x, adj)
                 x = F.dropout(x, self.dropout, training=self.training)
                 x = self.gc2(x, adj)
-                return F.log_softmax(x, dim=1)
+                return F.log_softmax(x.float(), dim=1)
             # (under HIP-graph capture the Philox offset, a host integer, would be frozen into the graph — every replay the
             #  same mask; torch's own dropout draws from the generator state the graph registers, so it takes over there)
             if self.fuse_epilogue and self.training and self.dropout > 0 and not torch.cuda.is_current_stream_capturing():
@@ -191,7 +209,7 @@ class GCN(nn.Module):
                 x = self.gc1(x, adj, relu=self.with_relu, fuse_epilogue=self.fuse_epilogue)
                 x = F.dropout(x, self.dropout, training=self.training)
             x = self.gc2(x, adj)
-            return F.log_softmax(x, dim=1)
+            return F.log_softmax(x.float(), dim=1)
 
     def get_extra_state(self):
         return {"dropout_seed": self.dropout_seed, "dropout_calls": self._dropout_calls}
@@ -248,6 +266,8 @@ class GCN(nn.Module):
         """gcn6.fit (gcn6.py:262-410).  hip_graph=True: the training step — forward, loss, backward, Adam — is captured
         once in a HIP graph after three eager iterations and replayed for the rest: for graphs small enough that an epoch
         is a few dozen launch-bound kernels (Cora-, Pubmed-shaped), where the launches, not the kernels, set the pace."""
+        if hip_graph and self.compute_dtype != torch.float32:
+            raise ValueError("hip_graph=True with compute_dtype=torch.bfloat16: not supported yet")
         if initialize:
             self.initialize()
         if not (reuse_prepared and self.adj is not None):   # (a second fit on the same graph keeps steps 1-4)

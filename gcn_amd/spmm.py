@@ -278,11 +278,14 @@ class CsrAdjacency:
         self.slices, self.tile_cols = best
         return dict(sorted(tried.items(), key=lambda kv: kv[1]))
 
-    def main_kernel(self, k, epilogue=False):
-        """name of the main kernel a k-wide SpMM on this plan launches (as rocprofv3 prints it)"""
+    def main_kernel(self, k, epilogue=False, dtype=torch.float32):
+        """name of the main kernel a k-wide SpMM on this plan launches (as rocprofv3 prints it); dtype=torch.bfloat16:
+        that of a bf16 call (the fp32 kernel of the fallback where the bf16 group kernel does not apply)"""
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise _lib.GcnAmdError(f"no SpMM for {dtype} operands (fp32 and bf16 only)")
+        fn = "gcn_spmm_plan_main_kernel_bf16" if dtype == torch.bfloat16 else "gcn_spmm_plan_main_kernel"
         buf = ctypes.create_string_buffer(128)
-        _lib.check(_lib.load().gcn_spmm_plan_main_kernel(self.plan, int(k), int(bool(epilogue)), buf, 128),
-                   "gcn_spmm_plan_main_kernel")
+        _lib.check(getattr(_lib.load(), fn)(self.plan, int(k), int(bool(epilogue)), buf, 128), fn)
         return buf.value.decode()
 
     def profile_begin(self, capacity):
@@ -316,13 +319,16 @@ class CsrAdjacency:
 
     # -- the op ------------------------------------------------------------------
     def matmul_raw(self, dense, out=None, bias=None, relu=False, dropout=None):
-        """C = dropout(act(Â·dense + bias)) with no autograd; dense is [n x k] fp32 on the same device.
+        """C = dropout(act(Â·dense + bias)) with no autograd; dense is [n x k] fp32 or bf16 on the same device.
         dropout = (p, seed, offset): the mask of gcn_spmm_csr_f32_epilogue (element i kept iff its Philox word
-        passes; kept values scaled by 1/(1-p)); `dropout_rows` applies the same mask to a gradient."""
-        if not dense.is_cuda or dense.dtype != torch.float32 or dense.dim() != 2:
-            raise _lib.GcnAmdError("dense operand must be a 2-D fp32 CUDA/HIP tensor")
+        passes; kept values scaled by 1/(1-p)); `dropout_rows` applies the same mask to a gradient.
+        bf16 `dense` (gcn_spmm_csr_bf16_epilogue): every sum in fp32; the result is bf16 unless `out` is an fp32 tensor."""
+        if not dense.is_cuda or dense.dtype not in (torch.float32, torch.bfloat16) or dense.dim() != 2:
+            raise _lib.GcnAmdError("dense operand must be a 2-D fp32 or bf16 CUDA/HIP tensor")
         if dense.shape[0] != self.n:
             raise ValueError(f"shape mismatch: A is {self.m}x{self.n}, B is {tuple(dense.shape)}")
+        if dense.dtype == torch.bfloat16:
+            return self._matmul_raw_bf16(dense.contiguous(), out, bias, relu, dropout)
         dense = dense.contiguous()
         k = int(dense.shape[1])
         if out is None:
@@ -345,6 +351,24 @@ class CsrAdjacency:
                                                     _ptr(self.val), _ptr(dense), _ptr(out), bp,
                                                     1 if relu else 0, k, _stream_ptr(self.device))
         _lib.check(st, "gcn_spmm_csr_f32")
+        return out
+
+    def _matmul_raw_bf16(self, dense, out, bias, relu, dropout):
+        k = int(dense.shape[1])
+        if out is None:
+            out = torch.empty((self.m, k), dtype=torch.bfloat16, device=dense.device)
+        elif not (out.is_contiguous() and out.shape == (self.m, k) and out.dtype in (torch.float32, torch.bfloat16)):
+            raise ValueError("out must be a contiguous fp32 or bf16 [m x k] tensor")
+        if bias is not None:
+            bias = bias.to(dtype=torch.float32).contiguous()       # (the epilogue runs in fp32)
+        c_dtype = _lib.DTYPE_BF16 if out.dtype == torch.bfloat16 else _lib.DTYPE_F32
+        p, seed, offset = (float(dropout[0]), int(dropout[1]), int(dropout[2])) if dropout is not None else (0.0, 0, 0)
+        bp = _ptr(bias) if bias is not None else ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            st = _lib.load().gcn_spmm_csr_bf16_epilogue(self.plan, _ptr(self.rowptr), _ptr(self.col), _ptr(self.val),
+                                                        _ptr(dense), _ptr(out), c_dtype, bp, 1 if relu else 0,
+                                                        p if p > 0.0 else 0.0, seed, offset, k, _stream_ptr(self.device))
+        _lib.check(st, "gcn_spmm_csr_bf16_epilogue")
         return out
 
 
@@ -451,14 +475,16 @@ def gather_rows(src, idx, out=None):
 def dropout_rows(x, p, seed, offset, out=None):
     """out = x with the dropout mask of the fused epilogue (gcn_dropout_f32): element i of the contiguous fp32 tensor
     is kept (and scaled by 1/(1-p)) iff its Philox4x32-10 word passes — the same function of (seed, offset, i) the
-    SpMM epilogue uses, so applying it to a gradient is the backward of that epilogue."""
-    if not x.is_cuda or x.dtype != torch.float32:
-        raise _lib.GcnAmdError("dropout_rows needs an fp32 CUDA/HIP tensor")
+    SpMM epilogue uses, so applying it to a gradient is the backward of that epilogue.  bf16 tensors: the same mask
+    (gcn_dropout_bf16)."""
+    if not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.GcnAmdError("dropout_rows needs an fp32 or bf16 CUDA/HIP tensor")
     x = x.contiguous()
     if out is None:
         out = torch.empty_like(x)
+    fn = "gcn_dropout_bf16" if x.dtype == torch.bfloat16 else "gcn_dropout_f32"
     with torch.cuda.device(x.device):
-        st = _lib.load().gcn_dropout_f32(_ptr(out), _ptr(x), int(x.numel()), float(p), int(seed), int(offset),
-                                         _stream_ptr(x.device))
-    _lib.check(st, "gcn_dropout_f32")
+        st = getattr(_lib.load(), fn)(_ptr(out), _ptr(x), int(x.numel()), float(p), int(seed), int(offset),
+                                      _stream_ptr(x.device))
+    _lib.check(st, fn)
     return out

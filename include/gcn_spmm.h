@@ -111,6 +111,30 @@ int gcn_spmm_csr_f32_epilogue(gcn_spmm_plan_t* plan,
 int gcn_dropout_f32(float* dst_dev, const float* src_dev, int64_t count, float dropout_p, uint64_t seed,
                     uint64_t offset, void* stream);
 
+
+/* bf16 feature operands (torch.bfloat16; raw 16-bit words on the device), fp32 accumulation everywhere.  B is bf16
+ * [n x k] row-major; C is [m x k] row-major of c_dtype (GCN_DTYPE_F32 or GCN_DTYPE_BF16; anything else:
+ * GCN_ERR_INVALID_ARG); the epilogue and its dropout mask are those of gcn_spmm_csr_f32_epilogue, applied in fp32, and a
+ * bf16 C is rounded once (round to nearest even).  Values and bias stay fp32.
+ *   Hot path: k % 8 == 0, k >= 64, on a plan whose k-wide call would run a group kernel (column slicing, no panels): B is
+ *   re-laid as a bf16 table in the group kernels' slice layout — value-free pass: bf16(u_col[c] * B[c, :]), rounded once
+ *   (relative error <= 2^-9 per entry); weighted pass: the bits of B — and walked by spmm_group_bf16[_weighted]_kernel, one
+ *   128-column tile per pass, into the same fp32 partial rows the fp32 path reduces.  The slice set is the one an fp32
+ *   call with the same row bytes (k / 2 columns) takes.
+ *   Fallback, every other plan and width: B widened to fp32 in a plan buffer, the fp32 entry, C narrowed.  Correct, not
+ *   fast: three passes and fp32 traffic.
+ * A plan is shared with the fp32 calls (its re-laid copy of B serves both); like the fp32 calls, the calls of one plan
+ * are issued on one stream at a time. */
+#define GCN_DTYPE_F32  0
+#define GCN_DTYPE_BF16 1
+int gcn_spmm_csr_bf16_epilogue(gcn_spmm_plan_t* plan, const int32_t* rowptr_dev, const int32_t* col_dev, const float* val_dev,
+                               const void* B_dev, void* C_dev, int32_t c_dtype, const float* bias_dev, int32_t relu,
+                               float dropout_p, uint64_t seed, uint64_t offset, int32_t k, void* stream);
+int gcn_spmm_csr_bf16(gcn_spmm_plan_t* plan, const int32_t* rowptr_dev, const int32_t* col_dev, const float* val_dev,
+                      const void* B_dev, void* C_dev, int32_t c_dtype, int32_t k, void* stream);
+/* gcn_dropout_f32 on bf16 data: the mask of element i as there, the kept value scaled in fp32 and rounded once */
+int gcn_dropout_bf16(void* dst_dev, const void* src_dev, int64_t count, float dropout_p, uint64_t seed, uint64_t offset,
+                     void* stream);
 /* Feature-column tile per kernel pass: 0 = automatic, else 64, 128 or 256 columns.  A k-wide
  * SpMM runs as ceil(k/tile) back-to-back passes, each gathering only its column slice of B
  * (smaller per-pass working set -> more of it stays in L2 / Infinity Cache). */
@@ -136,6 +160,9 @@ int32_t gcn_spmm_plan_num_passes(const gcn_spmm_plan_t* plan, int32_t k);
  * k-wide SpMM on this plan launches with the current settings and 16-byte aligned operands;
  * epilogue != 0: the bias/ReLU variant.  For benchmarks that report which kernel they timed. */
 int gcn_spmm_plan_main_kernel(const gcn_spmm_plan_t* plan, int32_t k, int32_t epilogue, char* buf, int32_t buflen);
+/* ... of a bf16 call (gcn_spmm_csr_bf16_epilogue): the bf16 group kernel on the hot path, else the fp32 kernel the
+ * fallback runs */
+int gcn_spmm_plan_main_kernel_bf16(const gcn_spmm_plan_t* plan, int32_t k, int32_t epilogue, char* buf, int32_t buflen);
 
 /* XCD-aware column slicing (optional, off by default).  Builds, on the device, a slice-major copy
  * of the matrix (`slices` equal column ranges; virtual row s*m+r = the part of row r in slice s)
