@@ -62,6 +62,11 @@ SIGNATURES = {
     "gcn_spmm_plan_prepare_width": (_c_i32, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_p]),
     "gcn_spmm_plan_set_value_factors": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "gcn_spmm_plan_has_value_factors": (_c_i32, [_c_p]),
+    "gcn_spmm_plan_set_values_mutable": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_p]),
+    "gcn_spmm_plan_values_mutable": (_c_i32, [_c_p]),
+    "gcn_spmm_plan_update_values": (ctypes.c_int, [_c_p, _c_p, _c_p]),
+    "gcn_sddmm_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_p]),
+    "gcn_spmm_plan_sddmm_kernel": (ctypes.c_int, [_c_p, _c_i32, ctypes.c_char_p, _c_i32]),
     "gcn_spmm_plan_enable_panels": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_p]),
     "gcn_spmm_plan_panel_rows": (_c_i32, [_c_p]),
     "gcn_spmm_plan_panel_coverage": (ctypes.c_double, [_c_p]),

@@ -170,11 +170,56 @@ int spmm_impl(gcn_spmm_plan* p, const SliceSet& ss, const int32_t* rowptr, const
              ? GCN_OK : GCN_ERR_HIP;
 }
 
+// Does a k-wide SDDMM walk the plan's slice-major copy?  Its traffic is the SpMM's (one gathered row of B per entry), so
+// it follows the four-per-gather kernel's rule: from k = 33; narrower rows walk the caller's CSR.
+bool sddmm_sliced(const gcn_spmm_plan* p, int k) { return p->slicing.S > 1 && p->nnz > 0 && k >= kSliceMinK; }
+
+// The sliced SDDMM's output map (Slicing::vsrc): built with a mutable plan; a plan with fixed values builds it here, at its
+// first sliced SDDMM or in gcn_spmm_plan_prepare_width (it allocates: not inside a stream capture)
+int ensure_value_map(gcn_spmm_plan* p, const int32_t* rowptr, hipStream_t st) {
+  Slicing& sl = p->slicing;
+  std::lock_guard<std::mutex> lk(g_plan_mu);
+  if (sl.vsrc) return GCN_OK;
+  DevBuf<int> v;
+  if (v.alloc((size_t)sl.S * (size_t)p->m) != hipSuccess) return GCN_ERR_ALLOC;
+  if (build_value_map(rowptr, sl.vrowptr, p->m, sl.S, v, st) != hipSuccess) return GCN_ERR_HIP;
+  sl.vsrc = std::move(v);
+  return GCN_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 const char* gcn_version(void) { return GCN_VERSION_STR; }
+
+int gcn_sddmm_csr_f32(gcn_spmm_plan_t* p, const int32_t* rowptr, const int32_t* col, const float* A, const float* B,
+                      float* out_val, int32_t k, void* stream) {
+  if (!p || k < 0) return GCN_ERR_INVALID_ARG;
+  if (p->nnz == 0 || p->m == 0) return GCN_OK;
+  if (!out_val) return GCN_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (k == 0)                                          // (empty sums)
+    return hipMemsetAsync(out_val, 0, sizeof(float) * (size_t)p->nnz, st) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+  if (!rowptr || !col || !A || !B) return GCN_ERR_INVALID_ARG;
+  SddmmArgs s;
+  s.A = A; s.B = B; s.out = out_val; s.m = p->m; s.nnz = p->nnz; s.T = p->T; s.nchunks = p->nchunks; s.k = k;
+  if (sddmm_sliced(p, k)) {
+    const Slicing& sl = p->slicing;
+    if (const int rc = ensure_value_map(p, rowptr, st); rc != GCN_OK) return rc;
+    s.rowptr = sl.vrowptr; s.col = sl.vcol; s.chunk_row = sl.vchunk_row; s.vsrc = sl.vsrc; s.rows = sl.S * p->m;
+  } else {
+    s.rowptr = rowptr; s.col = col; s.chunk_row = p->chunk_row; s.rows = p->m;
+  }
+  return launch_sddmm(s, st) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_spmm_plan_sddmm_kernel(const gcn_spmm_plan_t* p, int32_t k, char* buf, int32_t buflen) {
+  if (!p || k <= 0 || !buf || buflen <= 0) return GCN_ERR_INVALID_ARG;
+  snprintf(buf, (size_t)buflen, "gcn::sddmm_kernel<%s, %s>", sddmm_sliced(p, k) ? "true" : "false",
+           k % 4 == 0 ? "true" : "false");
+  return GCN_OK;
+}
 
 int gcn_spmm_csr_f32_epilogue(gcn_spmm_plan_t* p, const int32_t* rowptr, const int32_t* col, const float* val,
                               const float* B, float* C, const float* bias, int32_t relu, float dropout_p,
@@ -228,6 +273,7 @@ int gcn_spmm_plan_prepare_width(gcn_spmm_plan_t* p, const int32_t* rowptr, const
   int ld_call = odd ? ((k + 3) / 4 * 4 + 31) / 32 * 32 : padded_ldb(p->n, k);
   bool relay48 = false;
   (void)pick_slice_set(p, odd ? (k + 3) / 4 * 4 : k, &ld_call, &relay48, /*build=*/true, rowptr, col, val, (hipStream_t)stream);
+  if (sddmm_sliced(p, k)) return ensure_value_map(p, rowptr, (hipStream_t)stream);   // (the output map of a k-wide SDDMM)
   return GCN_OK;
 }
 

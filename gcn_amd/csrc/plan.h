@@ -93,6 +93,8 @@ struct Slicing {
   DevBuf<int> vcol;                                 // [nnz]
   DevBuf<float> vval;                               // [nnz]
   DevBuf<int> vchunk_row;                           // [nchunks] rows of the virtual CSR
+  DevBuf<int> vsrc;                                 // [S*m] CSR position of every virtual row's first entry (mutable values,
+                                                    //  SDDMM); built with a mutable plan, else at the first sliced SDDMM
 };
 
 // value-free pass, slices <= 65 535 columns and <= 8 of them: 16-bit column stream of the four-per-gather kernel
@@ -107,7 +109,7 @@ struct Col16Stream {
 struct GroupStream {
   DevBuf<unsigned short> stream;                    // [nchunks*T]
   DevBuf<float> vals;                               // [nchunks*T] values in stream order (weighted pass), empty: value-free
-  DevBuf<int> chunk_row, vrowptr, chunk_meta;       // [nchunks], [S*m+1], int2 [nchunks]
+  DevBuf<int> chunk_row, vrowptr, chunk_meta;       // [nchunks], [S*m+1] (kept by mutable plans: the refresh), int2 [nchunks]
   DevBuf<int> fix;                                  // int4 [nfix]: rows cut by chunk ends {virtual row, c, c1, 0}
   DevBuf<int> cutptr, cutchunk;                     // the same pieces per OUTPUT row (CutLists): [m+1], [ncut] chunk numbers
   int nchunks = 0, T = 0, w = 0, nfix = 0, ncut = 0;
@@ -168,6 +170,9 @@ struct gcn_spmm_plan {
   bool alt_tried[1] = {false};
   gcn::Factors factors;
   gcn::Panels panels;
+  // values declared mutable (gcn_spmm_plan_set_values_mutable): no factors, value-free streams or panels; the sliced
+  // copy keeps Slicing::vsrc and GroupStream::vrowptr so that gcn_spmm_plan_update_values can re-lay new values in place
+  bool values_mutable = false;
 };
 
 namespace gcn {

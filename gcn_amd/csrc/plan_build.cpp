@@ -59,7 +59,7 @@ void build_sliced_streams(gcn_spmm_plan* p, hipStream_t st) {
       p->group.chunk_meta.adopt(chunk_meta, 2 * (size_t)nch);
       p->group.nchunks = nch; p->group.T = gT; p->group.w = w;
       p->group.chunk_row.reset();                      // (only the builder needed these two: the kernels read
-      p->group.vrowptr.reset();                        //  chunk_meta and the fix list)
+      if (!p->values_mutable) p->group.vrowptr.reset();   //  chunk_meta and the fix list; a refresh needs the row pointer)
       return;
     }
     drop_streams(p);
@@ -203,7 +203,7 @@ int gcn_spmm_plan_enable_slicing(gcn_spmm_plan_t* p, const int32_t* rowptr, cons
   // that to 4 ulp the sliced main pass can run without its value stream, on a B whose rows were scaled by u,
   // with the row factor applied in the slice reduction.  (Factors handed over by the caller stay.)  Looked
   // for first: the automatic slice count depends on it.
-  if (p->m == p->n && !p->factors.ready() &&
+  if (p->m == p->n && !p->factors.ready() && !p->values_mutable &&
       (!autom || auto_slices(p->m, p->n, p->nnz, false) > 1)) {
     DevBuf<float> u;
     int ok = 0;
@@ -216,7 +216,7 @@ int gcn_spmm_plan_enable_slicing(gcn_spmm_plan_t* p, const int32_t* rowptr, cons
   // ... or depend on the row only / on the column only (r03): an unweighted adjacency (all ones), the row-normalised
   // D^-1 (A+I) of Kipf's pygcn, and its transpose (what the backward pass multiplies with) factor as u_row[r] * 1 and
   // 1 * u_col[c]; any shape.  Same 4-ulp check of every entry.
-  if (!p->factors.ready() && (!autom || auto_slices(p->m, p->n, p->nnz, false) > 1)) {
+  if (!p->factors.ready() && !p->values_mutable && (!autom || auto_slices(p->m, p->n, p->nnz, false) > 1)) {
     for (int mode = 1; mode <= 2 && !p->factors.ready(); ++mode) {
       Factors f;
       int ok = 0;
@@ -243,8 +243,13 @@ int gcn_spmm_plan_enable_slicing(gcn_spmm_plan_t* p, const int32_t* rowptr, cons
       count_empty(sl.vrowptr, (int)vm, &sl.empty_vrows, st) != GCN_OK)
     return GCN_ERR_HIP;
   sl.S = slices;
+  if (p->values_mutable) {                             // (what a refresh needs: the CSR start of every virtual row)
+    if (sl.vsrc.alloc((size_t)vm) != hipSuccess) return GCN_ERR_ALLOC;
+    if (build_value_map(rowptr, sl.vrowptr, p->m, slices, sl.vsrc, st) != hipSuccess) return GCN_ERR_HIP;
+  }
   p->slicing = std::move(sl);
   build_sliced_streams(p, st);
+  if (p->values_mutable && p->group.ready() && (!p->group.vals || !p->group.vrowptr)) return GCN_ERR_INTERNAL;
   return GCN_OK;
 }
 
@@ -265,6 +270,10 @@ int gcn_spmm_plan_set_value_factors(gcn_spmm_plan_t* p, const int32_t* rowptr, c
     return GCN_OK;
   }
   if (!u_row || !u_col || !rowptr || (p->nnz > 0 && (!col || !val))) return GCN_ERR_INVALID_ARG;
+  if (p->values_mutable) {                             // (values that change cannot be promised to factor)
+    build_sliced_streams(p, (hipStream_t)stream);
+    return GCN_ERR_INVALID_ARG;
+  }
   if (p->m == 0 || p->nnz == 0) return GCN_OK;
   hipStream_t st = (hipStream_t)stream;
   int ok = 0;
@@ -292,7 +301,7 @@ int32_t gcn_spmm_plan_has_value_factors(const gcn_spmm_plan_t* p) { return p ? (
 
 int gcn_spmm_plan_enable_panels(gcn_spmm_plan_t* p, const int32_t* rowptr, const int32_t* col,
                                 const float* val, int32_t mode, void* stream) {
-  if (!p || mode < -1 || mode > 1) return GCN_ERR_INVALID_ARG;
+  if (!p || mode < -1 || mode > 1 || (p->values_mutable && mode != 0)) return GCN_ERR_INVALID_ARG;
   p->panels = Panels{};
   if (mode == 0 || p->nnz == 0 || p->m == 0) return GCN_OK;
   if (!rowptr || !col || !val) return GCN_ERR_INVALID_ARG;
@@ -368,6 +377,39 @@ int gcn_spmm_plan_enable_panels(gcn_spmm_plan_t* p, const int32_t* rowptr, const
 int32_t gcn_spmm_plan_panel_rows(const gcn_spmm_plan_t* p) { return p ? p->panels.R : -1; }
 int32_t gcn_spmm_plan_dense_panels(const gcn_spmm_plan_t* p) { return p ? p->panels.ndense : -1; }
 double gcn_spmm_plan_panel_coverage(const gcn_spmm_plan_t* p) { return p ? p->panels.coverage : -1.0; }
+
+// Mutable values: the pattern stays, the values change (learned edge weights).  Everything that exists only for fixed
+// values goes — the factors with the value-free streams built on them (col16, the narrow slice set), and the panels, whose
+// split copies of the values would need a refresh of their own — and the sliced copy is built again, once, as a weighted
+// plan (its automatic slice count re-chosen for one, as gcn_spmm_plan_set_value_factors does), keeping what a refresh
+// needs: Slicing::vsrc (4*S*m bytes) and the group stream's row pointer (4*(S*m+1) bytes).
+int gcn_spmm_plan_set_values_mutable(gcn_spmm_plan_t* p, const int32_t* rowptr, const int32_t* col, const float* val,
+                                     void* stream) {
+  if (!p) return GCN_ERR_INVALID_ARG;
+  const bool resliced = p->slices_auto || p->slicing.S > 1;
+  if (resliced && p->nnz > 0 && (!rowptr || !col || !val)) return GCN_ERR_INVALID_ARG;
+  p->values_mutable = true;
+  p->factors = Factors{};
+  p->panels = Panels{};
+  drop_streams(p);
+  if (!resliced) return GCN_OK;                        // (unsliced: every launch reads the caller's values)
+  return gcn_spmm_plan_enable_slicing(p, rowptr, col, val, p->slices_auto ? -1 : p->slicing.S, stream);
+}
+
+int32_t gcn_spmm_plan_values_mutable(const gcn_spmm_plan_t* p) { return p ? (p->values_mutable ? 1 : 0) : -1; }
+
+// New values (CSR order) into every value-bearing layout of a mutable plan: the sliced copy and the weighted group
+// stream, both from one O(nnz) pass.  No allocation, no synchronisation: legal inside a stream capture.
+int gcn_spmm_plan_update_values(gcn_spmm_plan_t* p, const float* val, void* stream) {
+  if (!p || !p->values_mutable) return GCN_ERR_INVALID_ARG;
+  const Slicing& sl = p->slicing;
+  if (p->nnz == 0 || p->m == 0 || sl.S <= 1) return GCN_OK;
+  if (!val) return GCN_ERR_INVALID_ARG;
+  if (!sl.vsrc || (p->group.vals && !p->group.vrowptr)) return GCN_ERR_INTERNAL;
+  float* gvals = p->group.ready() ? p->group.vals.get() : nullptr;
+  return launch_refresh_values(sl.vrowptr, sl.vsrc, p->group.vrowptr, p->m, sl.S, val, sl.vval, gvals, (hipStream_t)stream) ==
+                 hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
 
 int gcn_spmm_plan_set_tile_cols(gcn_spmm_plan_t* p, int32_t cols) {
   if (!p || !(cols == 0 || cols == 64 || cols == 128 || cols == 256)) return GCN_ERR_INVALID_ARG;

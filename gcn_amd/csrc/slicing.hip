@@ -693,6 +693,52 @@ hipError_t launch_scale_rows_sliced(float* dst, const float* src, const float* r
   return hipGetLastError();
 }
 
+// ---- mutable values: the CSR start of every virtual row, and the refresh of the value layouts ----
+// one thread per row: its parts in slices 0, 1, ... follow each other in the CSR row
+__global__ void value_map_kernel(const int* __restrict__ rowptr, const int* __restrict__ vrowptr, int m, int S,
+                                 int* __restrict__ vsrc) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= m) return;
+  int at = rowptr[r];
+  for (int s = 0; s < S; ++s) {
+    const long long vr = (long long)s * m + r;
+    vsrc[vr] = at;
+    at += vrowptr[vr + 1] - vrowptr[vr];
+  }
+}
+
+hipError_t build_value_map(const int* rowptr, const int* vrowptr, int m, int S, int* vsrc, hipStream_t st) {
+  if (m <= 0 || S <= 0) return hipSuccess;
+  value_map_kernel<<<(m + 255) / 256, 256, 0, st>>>(rowptr, vrowptr, m, S, vsrc);
+  return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256)
+refresh_values_kernel(const int* __restrict__ vrowptr, const int* __restrict__ vsrc, const int* __restrict__ vrowptr_g,
+                      long long vm, const float* __restrict__ val, float* __restrict__ vval, float* __restrict__ gvals) {
+  const int lane = threadIdx.x & 63;
+  const long long nw = (long long)gridDim.x * 4;
+  for (long long vr = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); vr < vm; vr += nw) {
+    const int dst = vrowptr[vr], len = vrowptr[vr + 1] - dst, src = vsrc[vr];
+    const int g = gvals ? vrowptr_g[vr] : 0;
+    for (int i = lane; i < len; i += 64) {
+      const float v = val[src + i];
+      vval[dst + i] = v;
+      if (gvals) gvals[group_phys((long long)g + i)] = v;
+    }
+  }
+}
+
+hipError_t launch_refresh_values(const int* vrowptr, const int* vsrc, const int* vrowptr_g, int m, int S, const float* val,
+                                 float* vval, float* gvals, hipStream_t st) {
+  const long long vm = (long long)S * m;
+  if (vm <= 0) return hipSuccess;
+  long long nb = (vm + 3) / 4;
+  if (nb > 16384) nb = 16384;
+  refresh_values_kernel<<<(int)nb, 256, 0, st>>>(vrowptr, vsrc, vrowptr_g, vm, val, vval, gvals);
+  return hipGetLastError();
+}
+
 // ---- do the values factor as u[r] * u[c]?  (the GCN normalisation D^-1/2 (A+I) D^-1/2: u = D^-1/2) ----
 // u[r] = sqrt(A[r, r]) from the stored diagonal (binary search in the column-sorted row)
 __global__ void rank1_diag_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,

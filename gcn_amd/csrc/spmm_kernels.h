@@ -142,6 +142,26 @@ hipError_t launch_group_fixup(const int* fix, int nfix, const float* P, float* C
 hipError_t launch_scale_rows_sliced(float* dst, const float* src, const float* rowscale, int n, int k, int ld,
                                     int S, int w, hipStream_t s);
 
+// sddmm.hip — out[e] = sum_j A[row(e), j] * B[col(e), j] for every stored entry, in CSR order.  Chunks of T entries of a
+// CSR (the caller's, vsrc = nullptr) or of a plan's slice-major virtual CSR (rows = S*m; vsrc[vr] = CSR position of the
+// first entry of virtual row vr; A row vr % m).  A [m x k] and B [n x k] row-major fp32.
+struct SddmmArgs {
+  const int *rowptr = nullptr, *col = nullptr, *chunk_row = nullptr, *vsrc = nullptr;
+  const float *A = nullptr, *B = nullptr;
+  float* out = nullptr;
+  int rows = 0, m = 0, nnz = 0, T = 0, nchunks = 0, k = 0;
+};
+hipError_t launch_sddmm(const SddmmArgs& s, hipStream_t st);
+bool sddmm_vec(const float* A, const float* B, int k);   // 16-byte loads (k % 4 == 0, aligned operands)
+
+// slicing.hip — mutable values.  vsrc[s*m + r] = CSR position of the first entry of row r in slice s (from the sliced
+// row pointer; column-sorted rows make every (row, slice) part one contiguous run of the CSR row).
+hipError_t build_value_map(const int* rowptr, const int* vrowptr, int m, int S, int* vsrc, hipStream_t st);
+// new CSR-order values into the sliced copy (vval, slice-major) and, when gvals is set, into the group stream's values
+// (position group_phys(vrowptr_g[vr] + i)); padding entries keep their zero.  One wave per virtual row, no allocation.
+hipError_t launch_refresh_values(const int* vrowptr, const int* vsrc, const int* vrowptr_g, int m, int S, const float* val,
+                                 float* vval, float* gvals, hipStream_t st);
+
 // spmm_group_bf16.hip — bf16 feature operands, fp32 accumulation.  The group walk on a bf16 table Bh (the layout of
 // GroupArgs::Bp, rows a.ldb bf16 apart, a.ldb % 8 == 0; a.Bp is not read), k % 8 == 0, partial rows into the fp32 Cv / P.
 hipError_t launch_spmm_group_bf16(const GroupArgs& a, const unsigned short* Bh, hipStream_t s);

@@ -9,6 +9,10 @@ Mirrors the two interfaces the reference reaches its SpMM through:
   stock PyTorch, so gcn1–5 run unchanged.
 * B1 — the ``flexspmm`` autograd Function of pygcn/gcn6.py:34-62 (see dropin.py).
 
+Learnable edge weights: ``CsrAdjacency(..., mutable_values=True)`` and ``spmm(adj, dense, values=w)``; the gradient
+of the values is an SDDMM on the adjacency's pattern (``CsrAdjacency.sddmm``), and ``install(sparse_grad=True)`` routes
+``torch.sparse.mm`` for a grad-requiring COO operand through it.
+
 PyTorch is plumbing here (device memory, streams, autograd); the arithmetic is
 libgcnspmm.so.  There is no CPU fallback: CPU tensors raise.
 """
@@ -31,14 +35,20 @@ def _stream_ptr(device):
 class CsrAdjacency:
     """Device-resident CSR matrix (int32 rowptr / int32 col / fp32 val) + its cached
     SpMM plan.  The layout is the reference's own CSR hand-off (gcn6.py:302-311:
-    ``to_sparse_csr()``, crow/col cast to int32)."""
+    ``to_sparse_csr()``, crow/col cast to int32).
 
-    def __init__(self, rowptr, col, val, shape, symmetric=None, chunk_nnz=0, slices="auto", panels=0):
+    mutable_values=True: the values will change and the pattern will not (learned edge weights).  The plan keeps what
+    ``update_values`` needs to re-lay new values in place; it has no value factors and no panels (``panels`` is
+    ignored)."""
+
+    def __init__(self, rowptr, col, val, shape, symmetric=None, chunk_nnz=0, slices="auto", panels=0,
+                 mutable_values=False):
         if not (rowptr.is_cuda and col.is_cuda and val.is_cuda):
             raise _lib.GcnAmdError("CsrAdjacency needs CUDA/HIP tensors (no CPU path in gcn_amd)")
         self.rowptr = rowptr.to(torch.int32).contiguous()
         self.col = col.to(torch.int32).contiguous()
-        self.val = val.to(torch.float32).contiguous()
+        # (a mutable adjacency owns its values: update_values writes them, and they must never be the caller's tensor)
+        self.val = val.to(torch.float32).contiguous() if not mutable_values else val.detach().to(torch.float32, copy=True)
         self.m, self.n = int(shape[0]), int(shape[1])
         self.nnz = int(self.col.numel())
         if self.rowptr.numel() != self.m + 1:
@@ -51,8 +61,13 @@ class CsrAdjacency:
         # LDS-staged row panels: off unless asked for ("auto" = by measured window coverage) — on MI355X
         # the chunk kernel is still faster even on community-ordered graphs
         self.panels = -1 if panels == "auto" else int(bool(panels))
+        self.mutable_values = bool(mutable_values)
+        if self.mutable_values:
+            self.panels = 0
         self._plan = None
         self._transpose = None
+        self._tperm = None           # mutable transpose: its values are self.val[_tperm]
+        self._tstale = False         # ... once refreshed: update_values has changed self.val since
         self.device = self.val.device
 
     # -- constructors ---------------------------------------------------------
@@ -89,6 +104,11 @@ class CsrAdjacency:
             _lib.check(st, "gcn_spmm_plan_create")
             self._plan = handle
             weakref.finalize(self, _destroy_plan, handle)
+            if self.mutable_values:                  # (before the slicing: it is built once, as a weighted plan)
+                with torch.cuda.device(self.device):
+                    st = lib.gcn_spmm_plan_set_values_mutable(handle, _ptr(self.rowptr), _ptr(self.col), _ptr(self.val),
+                                                              _stream_ptr(self.device))
+                _lib.check(st, "gcn_spmm_plan_set_values_mutable")
             if self.panels != 0:
                 self.enable_panels(self.panels)
             if self.slices not in (0, 1) and self.panel_rows == 0:
@@ -302,9 +322,94 @@ class CsrAdjacency:
                    "gcn_spmm_profile_end")
         return [float(buf[i]) for i in range(cnt.value)]
 
+    @property
+    def values_mutable(self):
+        """the plan's own answer (gcn_spmm_plan_values_mutable)"""
+        return bool(_lib.load().gcn_spmm_plan_values_mutable(self.plan))
+
+    def _device_values(self, val, what):
+        if not isinstance(val, torch.Tensor) or val.dim() != 1 or val.numel() != self.nnz:
+            raise ValueError(f"{what}: values must be a 1-D tensor of nnz = {self.nnz} entries in CSR order")
+        if not val.is_cuda:
+            raise _lib.GcnAmdError(f"{what} needs a CUDA/HIP tensor (no CPU path in gcn_amd)")
+        return val.detach().to(device=self.device, dtype=torch.float32).contiguous()
+
+    def update_values(self, val):
+        """New values (nnz entries, CSR order) for a mutable adjacency: re-laid into the plan in place
+        (gcn_spmm_plan_update_values: no allocation, no synchronisation — legal inside a graph capture) and copied
+        into self.val (the adjacency's own copy: `val` itself is only read).  The transpose, if one exists, is refreshed
+        from them at its next use.  GcnAmdError on an adjacency not made mutable (nothing changes then)."""
+        v = self._device_values(val, "update_values")
+        with torch.cuda.device(self.device):
+            st = _lib.load().gcn_spmm_plan_update_values(self.plan, _ptr(v), _stream_ptr(self.device))
+        _lib.check(st, "gcn_spmm_plan_update_values")
+        if v.data_ptr() != self.val.data_ptr():
+            self.val.copy_(v)
+        self._tstale = self._transpose is not None
+        return self
+
+    def sddmm(self, A, B, out=None):
+        """out[e] = A[row(e)] . B[col(e)] for every stored entry e, in CSR order (gcn_sddmm_csr_f32): A is [m x k],
+        B is [n x k]; fp32 accumulation, fp32 result.  bf16 operands are widened to fp32 first (correct, not fast).
+        The gradient of Â·B with respect to Â's values, for grad_out = A.  A sliced plan with fixed values allocates its
+        map of the virtual rows at the first call with k >= 33: before a graph capture, call it once or prepare_width(k)."""
+        for t, rows, name in ((A, self.m, "A"), (B, self.n, "B")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda) or t.dtype not in (torch.float32, torch.bfloat16) or t.dim() != 2:
+                raise _lib.GcnAmdError(f"sddmm: {name} must be a 2-D fp32 or bf16 CUDA/HIP tensor")
+            if t.shape[0] != rows:
+                raise ValueError(f"sddmm: {name} needs {rows} rows, has {tuple(t.shape)}")
+        if A.shape[1] != B.shape[1]:
+            raise ValueError(f"sddmm: A and B need the same width, have {A.shape[1]} and {B.shape[1]}")
+        A = A.to(torch.float32).contiguous()
+        B = B.to(torch.float32).contiguous()
+        if out is None:
+            out = torch.empty(self.nnz, dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == self.nnz):
+            raise ValueError("sddmm: out must be a contiguous fp32 device tensor of nnz entries")
+        with torch.cuda.device(self.device):
+            st = _lib.load().gcn_sddmm_csr_f32(self.plan, _ptr(self.rowptr), _ptr(self.col), _ptr(A), _ptr(B), _ptr(out),
+                                               int(A.shape[1]), _stream_ptr(self.device))
+        _lib.check(st, "gcn_sddmm_csr_f32")
+        return out
+
+    def sddmm_kernel(self, k):
+        """name of the kernel a k-wide sddmm on this plan launches (gcn_spmm_plan_sddmm_kernel)"""
+        buf = ctypes.create_string_buffer(128)
+        _lib.check(_lib.load().gcn_spmm_plan_sddmm_kernel(self.plan, int(k), buf, 128), "gcn_spmm_plan_sddmm_kernel")
+        return buf.value.decode()
+
+    def _refresh_transpose(self, values):
+        """re-lay values (nnz, CSR order of this adjacency) into the mutable transpose: values[_tperm]"""
+        t = self._mutable_transpose()
+        t.update_values(values.detach().index_select(0, self._tperm))
+        return t
+
+    def _mutable_transpose(self):
+        """Âᵀ of a mutable adjacency: itself mutable, never Â (a symmetric pattern does not make learned values
+        symmetric); duplicates stay separate entries, so its values are exactly self.val[_tperm]."""
+        if self._transpose is None:
+            dev = self.device
+            rp = self.rowptr.long()
+            rows = torch.repeat_interleave(torch.arange(self.m, device=dev), rp[1:] - rp[:-1], output_size=self.nnz)
+            c = self.col.long()
+            perm = torch.argsort(c * max(self.m, 1) + rows, stable=True)
+            trp = torch.zeros(self.n + 1, dtype=torch.int64, device=dev)
+            trp[1:] = torch.cumsum(torch.bincount(c, minlength=self.n), 0)
+            t = CsrAdjacency(trp.to(torch.int32), rows[perm].to(torch.int32), self.val[perm], (self.n, self.m),
+                             symmetric=False, chunk_nnz=self.chunk_nnz, mutable_values=True)
+            self._tperm = perm
+            self._transpose = t
+        return self._transpose
+
     def transpose(self):
         """Âᵀ as a CsrAdjacency (cached); Â itself when flagged symmetric — the
-        reference's backward reuses Â because Â is symmetric (gcn6.py:50-62)."""
+        reference's backward reuses Â because Â is symmetric (gcn6.py:50-62).  A mutable adjacency's transpose is
+        a mutable adjacency of its own (refreshed from Â's values by the autograd of spmm(values=...))."""
+        if self.mutable_values:
+            if self._tstale:                         # (values changed since the transpose was last refreshed)
+                self._tstale = False
+                return self._refresh_transpose(self.val)
+            return self._mutable_transpose()
         if self.symmetric:
             return self
         if self._transpose is None:
@@ -395,12 +500,50 @@ class _SpmmFunction(torch.autograd.Function):
         return None, ctx.adj.transpose().matmul_raw(grad_out.contiguous())
 
 
-def spmm(adj, dense):
+class _SpmmValuesFunction(torch.autograd.Function):
+    """C = Â(values) · dense with learnable values: the forward re-lays `values` into the plan, the backward gives
+    grad_values = SDDMM(grad_out, dense) on Â's pattern and grad_dense = Âᵀ · grad_out, Âᵀ refreshed from the same values."""
+
+    @staticmethod
+    def forward(ctx, adj, dense, values):
+        adj.update_values(values)
+        ctx.adj = adj
+        ctx.save_for_backward(dense, values)
+        return adj.matmul_raw(dense)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        dense, values = ctx.saved_tensors
+        adj = ctx.adj
+        grad_out = grad_out.contiguous()
+        gd = gv = None
+        if ctx.needs_input_grad[2]:
+            gv = adj.sddmm(grad_out, dense)
+        if ctx.needs_input_grad[1]:
+            # (from the values of THIS forward: adj may have been given others since)
+            gd = adj._refresh_transpose(values).matmul_raw(grad_out)
+        return None, gd, gv
+
+
+def spmm(adj, dense, values=None):
     """C = adj @ dense on the HIP kernel.  `adj` is a CsrAdjacency or a torch sparse
-    (COO/CSR) fp32 tensor on the GPU (converted and cached per tensor object)."""
+    (COO/CSR) fp32 tensor on the GPU (converted and cached per tensor object).
+    values: nnz fp32 values in adj's CSR order that replace adj's own (and may require grad): adj must have been made
+    with mutable_values=True; they are re-laid into its plan at every call, so values changed in place between two
+    calls (an optimizer step) are picked up."""
     if not isinstance(adj, CsrAdjacency):
         adj = _cached_csr(adj)
-    return _SpmmFunction.apply(adj, dense)
+    if values is None:
+        return _SpmmFunction.apply(adj, dense)
+    if not isinstance(values, torch.Tensor) or values.dim() != 1 or values.numel() != adj.nnz:
+        raise ValueError(f"spmm: values must be a 1-D tensor of nnz = {adj.nnz} entries in CSR order")
+    if not values.is_cuda:
+        raise _lib.GcnAmdError("spmm: values must be a CUDA/HIP tensor (no CPU path in gcn_amd)")
+    if values.dtype != torch.float32:
+        raise _lib.GcnAmdError("spmm: values must be fp32")
+    if not adj.mutable_values:
+        raise _lib.GcnAmdError("spmm(values=...) needs an adjacency made with mutable_values=True")
+    return _SpmmValuesFunction.apply(adj, dense, values)
 
 
 # --- routing of torch.spmm / torch.sparse.mm (interface B2) -----------------------
@@ -426,9 +569,74 @@ def _routable(a, b):
             and not a.requires_grad)
 
 
-def install():
+# torch.sparse.mm with a grad-requiring COO operand (install(sparse_grad=True)): one mutable adjacency per pattern
+_pattern_cache = []      # [(indices tensor, shape, CsrAdjacency)], most recent first
+_route_sparse_grad = False
+_PATTERN_CACHE_SIZE = 4  # (each entry holds a plan and its transpose's: keep few)
+
+
+def _routable_grad(a, b):
+    return (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)
+            and a.layout == torch.sparse_coo and a.is_cuda and a.dtype == torch.float32 and a.dim() == 2
+            and a.requires_grad and a.is_coalesced()
+            and b.layout == torch.strided and b.is_cuda and b.dtype == torch.float32 and b.dim() == 2)
+
+
+def _pattern_csr(a):
+    """the mutable adjacency of a coalesced COO pattern (its indices are the CSR order): reused while the pattern is
+    the same — the same index storage, or equal indices — whatever the values"""
+    idx = a._indices()
+    shape = tuple(a.shape)
+    for i, (cidx, cshape, adj) in enumerate(_pattern_cache):
+        if cshape == shape and cidx.device == idx.device and cidx.shape == idx.shape and (
+                cidx.data_ptr() == idx.data_ptr() or torch.equal(cidx, idx)):
+            if i:
+                _pattern_cache.insert(0, _pattern_cache.pop(i))
+            return adj
+    m, n = shape
+    rowptr = torch.zeros(m + 1, dtype=torch.int64, device=idx.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(idx[0], minlength=m), 0)
+    adj = CsrAdjacency(rowptr.to(torch.int32), idx[1].to(torch.int32), a._values().detach(), shape, mutable_values=True)
+    _pattern_cache.insert(0, (idx, shape, adj))
+    del _pattern_cache[_PATTERN_CACHE_SIZE:]
+    return adj
+
+
+class _SparseMmGrad(torch.autograd.Function):
+    """torch.sparse.mm(a, b) for a coalesced COO `a` that requires grad: the gradient of `a` is a sparse COO tensor on
+    a's own pattern (an SDDMM), as stock PyTorch gives it"""
+
+    @staticmethod
+    def forward(ctx, a, b, adj):
+        vals = a._values().detach()
+        ctx.adj = adj
+        ctx.a_indices, ctx.a_shape = a._indices(), a.shape
+        ctx.save_for_backward(b, vals)
+        adj.update_values(vals)
+        return adj.matmul_raw(b)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        b, vals = ctx.saved_tensors
+        adj = ctx.adj
+        grad_out = grad_out.contiguous()
+        ga = gb = None
+        if ctx.needs_input_grad[0]:
+            gv = adj.sddmm(grad_out, b)
+            ga = torch.sparse_coo_tensor(ctx.a_indices, gv, ctx.a_shape, is_coalesced=True)
+        if ctx.needs_input_grad[1]:
+            gb = adj._refresh_transpose(vals).matmul_raw(grad_out)
+        return ga, gb, None
+
+
+def install(sparse_grad=False):
     """Route ``torch.spmm`` / ``torch.sparse.mm`` for (GPU sparse fp32) × (GPU dense fp32)
-    to the HIP kernel; anything else goes to the original callables."""
+    to the HIP kernel; anything else goes to the original callables.
+    sparse_grad=True: ``torch.sparse.mm`` also routes a coalesced GPU fp32 COO operand that requires grad (its gradient
+    is the sparse COO tensor on its pattern stock PyTorch gives, computed by an SDDMM; one plan per pattern).
+    ``torch.spmm``'s gradient of such an operand is a dense m×n tensor and stays with stock PyTorch, as do CSR operands."""
+    global _route_sparse_grad
+    _route_sparse_grad = bool(sparse_grad)
     if _orig:
         return
     _lib.load()  # fail loudly now, not at the first layer
@@ -443,6 +651,8 @@ def install():
     def routed_sparse_mm(a, b, *args, **kw):
         if not args and not kw and _routable(a, b):
             return spmm(a, b)
+        if not args and not kw and _route_sparse_grad and _routable_grad(a, b):
+            return _SparseMmGrad.apply(a, b, _pattern_csr(a))
         return _orig["sparse_mm"](a, b, *args, **kw)
 
     torch.spmm = routed_spmm
@@ -450,6 +660,9 @@ def install():
 
 
 def uninstall():
+    global _route_sparse_grad
+    _route_sparse_grad = False
+    _pattern_cache.clear()
     if not _orig:
         return
     torch.spmm = _orig.pop("spmm")

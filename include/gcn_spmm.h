@@ -187,7 +187,8 @@ int32_t gcn_spmm_plan_num_slices(const gcn_spmm_plan_t* plan);
  * many slices fill an L2, and the partial rows — whose cost goes with the slice count — halve (Reddit-shaped: 8
  * instead of 15). */
 int32_t gcn_spmm_plan_narrow_slices(const gcn_spmm_plan_t* plan, int32_t k);
-/* Build NOW whatever a k-wide call of this plan would build at its first use (the narrow slice set above: device
+/* Build NOW whatever a k-wide call of this plan would build at its first use (the narrow slice set above, the map of a
+ * sliced gcn_sddmm_csr_f32: device
  * allocations and a stream synchronisation), e.g. before a stream capture whose first k-wide call must only enqueue
  * kernels.  The matrix arrays must be the ones the plan was created for.  Idempotent; GCN_OK also when nothing is to build. */
 int gcn_spmm_plan_prepare_width(gcn_spmm_plan_t* plan, const int32_t* rowptr_dev, const int32_t* col_dev,
@@ -206,6 +207,31 @@ int gcn_spmm_plan_set_value_factors(gcn_spmm_plan_t* plan, const int32_t* rowptr
                                     const float* val_dev, const float* u_row_dev, const float* u_col_dev,
                                     void* stream);
 int32_t gcn_spmm_plan_has_value_factors(const gcn_spmm_plan_t* plan);   /* 1 / 0 */
+
+/* Mutable values (learned edge weights): the pattern stays, the values change.  Call before any stream capture (it
+ * allocates and synchronises).  Drops what exists only for fixed values — value factors, the value-free streams and
+ * panels — and builds the sliced copy again, once, as a weighted plan (an automatic slice count is re-chosen for one),
+ * keeping the CSR start of every virtual row.  Afterwards gcn_spmm_plan_set_value_factors and enabling panels return
+ * GCN_ERR_INVALID_ARG.  The matrix arrays must be the ones the plan was created for. */
+int gcn_spmm_plan_set_values_mutable(gcn_spmm_plan_t* plan, const int32_t* rowptr_dev, const int32_t* col_dev,
+                                     const float* val_dev, void* stream);
+int32_t gcn_spmm_plan_values_mutable(const gcn_spmm_plan_t* plan);        /* 1 / 0 */
+/* New values val_dev [nnz] (CSR order) into every value-bearing layout of a mutable plan: one O(nnz) kernel, no
+ * allocation, no host synchronisation (legal inside a stream capture).  Later SpMM calls must pass these same values as
+ * their val_dev (the unsliced paths read them there).  GCN_ERR_INVALID_ARG on a plan not made mutable. */
+int gcn_spmm_plan_update_values(gcn_spmm_plan_t* plan, const float* val_dev, void* stream);
+
+/* SDDMM on the plan's pattern: out_val[e] = sum_j A[row(e), j] * B[col(e), j] for every stored entry e, in CSR order.
+ * A is m x k, B is n x k, both row-major fp32 (device); fp32 accumulation.  Empty rows write nothing; duplicate (r, c)
+ * entries each get their own output.  k = 0 writes zeros.  Deterministic: the same (A, B, k) gives the same bits on
+ * every plan of the matrix and every call.  Works on any plan; from k = 33 a sliced plan walks its slice-major copy
+ * (the SpMM's L2 locality).  On a plan with fixed values its first such call ALLOCATES the map of the virtual rows
+ * (4*S*m bytes) and synchronises, so it must not be the first inside a stream capture: call it once before, or
+ * gcn_spmm_plan_prepare_width with that k.  Mutable plans have the map already. */
+int gcn_sddmm_csr_f32(gcn_spmm_plan_t* plan, const int32_t* rowptr_dev, const int32_t* col_dev, const float* A,
+                      const float* B, float* out_val, int32_t k, void* stream);
+/* name of the kernel a k-wide gcn_sddmm_csr_f32 on this plan launches (16-byte-aligned operands) */
+int gcn_spmm_plan_sddmm_kernel(const gcn_spmm_plan_t* plan, int32_t k, char* buf, int32_t buflen);
 
 /* LDS-staged row panels (optional): for matrices whose non-zeros sit near the diagonal (community
  * graphs after Rabbit / RCM / Gorder renumbering) a workgroup stages the feature rows of its panel's
