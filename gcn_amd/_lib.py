@@ -66,6 +66,13 @@ SIGNATURES = {
     "gcn_spmm_plan_values_mutable": (_c_i32, [_c_p]),
     "gcn_spmm_plan_update_values": (ctypes.c_int, [_c_p, _c_p, _c_p]),
     "gcn_sddmm_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_p]),
+    "gcn_edge_softmax_csr_f32": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_edge_softmax_backward_csr_f32": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_gat_edge_softmax_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p, ctypes.c_float, _c_p, _c_p,
+                                                    ctypes.c_size_t, _c_p]),
+    "gcn_gat_edge_softmax_backward_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p, ctypes.c_float, _c_p, _c_p,
+                                                             _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_segment_sum_csr_f32": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_spmm_plan_sddmm_kernel": (ctypes.c_int, [_c_p, _c_i32, ctypes.c_char_p, _c_i32]),
     "gcn_spmm_plan_enable_panels": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_p]),
     "gcn_spmm_plan_panel_rows": (_c_i32, [_c_p]),

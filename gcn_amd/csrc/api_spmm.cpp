@@ -214,6 +214,60 @@ int gcn_sddmm_csr_f32(gcn_spmm_plan_t* p, const int32_t* rowptr, const int32_t* 
   return launch_sddmm(s, st) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
 }
 
+// Edge softmax family (edge_softmax.hip): plan-free, on the caller's CSR.  Common argument check: sizes, the row pointer
+// and the workspace (GCN_EDGE_WS_BYTES(nnz)); 1 = nothing to do, 0 = go on, else the status to return.
+static int edge_args(const int32_t* rowptr, int32_t m, int32_t nnz, const void* ws, size_t ws_bytes, int* status) {
+  *status = GCN_OK;
+  if (m < 0 || nnz < 0) { *status = GCN_ERR_INVALID_ARG; return 1; }
+  if (m == 0 || nnz == 0) return 1;
+  if (!rowptr || !ws || ws_bytes < edge_workspace_bytes(nnz)) { *status = GCN_ERR_INVALID_ARG; return 1; }
+  return 0;
+}
+
+int gcn_edge_softmax_csr_f32(const int32_t* rowptr, int32_t m, int32_t nnz, const float* scores, float* p, void* ws,
+                             size_t ws_bytes, void* stream) {
+  int rc;
+  if (edge_args(rowptr, m, nnz, ws, ws_bytes, &rc)) return rc;
+  if (!scores || !p) return GCN_ERR_INVALID_ARG;
+  return launch_edge_softmax(rowptr, m, nnz, scores, p, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_edge_softmax_backward_csr_f32(const int32_t* rowptr, int32_t m, int32_t nnz, const float* p, const float* g,
+                                      float* ds, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (edge_args(rowptr, m, nnz, ws, ws_bytes, &rc)) return rc;
+  if (!p || !g || !ds) return GCN_ERR_INVALID_ARG;
+  return launch_edge_softmax_backward(rowptr, m, nnz, p, g, ds, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_gat_edge_softmax_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t nnz, const float* a_dst,
+                                 const float* a_src, float negative_slope, float* p, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (edge_args(rowptr, m, nnz, ws, ws_bytes, &rc)) return rc;
+  if (!col || !a_dst || !a_src || !p) return GCN_ERR_INVALID_ARG;
+  return launch_gat_edge_softmax(rowptr, col, m, nnz, a_dst, a_src, negative_slope, p, ws, (hipStream_t)stream) == hipSuccess
+             ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_gat_edge_softmax_backward_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t nnz,
+                                          const float* a_dst, const float* a_src, float negative_slope, const float* p,
+                                          const float* g, float* ds, float* grad_a_dst, void* ws, size_t ws_bytes,
+                                          void* stream) {
+  int rc;
+  if (edge_args(rowptr, m, nnz, ws, ws_bytes, &rc)) return rc;
+  if (!col || !a_dst || !a_src || !p || !g || !ds || !grad_a_dst) return GCN_ERR_INVALID_ARG;
+  return launch_gat_edge_softmax_backward(rowptr, col, m, nnz, a_dst, a_src, negative_slope, p, g, ds, grad_a_dst, ws,
+                                          (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_segment_sum_csr_f32(const int32_t* rowptr, int32_t m, int32_t nnz, const float* x, const int32_t* perm, float* out,
+                            void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (edge_args(rowptr, m, nnz, ws, ws_bytes, &rc)) return rc;
+  if (!x || !out) return GCN_ERR_INVALID_ARG;
+  return launch_segment_sum(rowptr, m, nnz, x, perm, out, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
 int gcn_spmm_plan_sddmm_kernel(const gcn_spmm_plan_t* p, int32_t k, char* buf, int32_t buflen) {
   if (!p || k <= 0 || !buf || buflen <= 0) return GCN_ERR_INVALID_ARG;
   snprintf(buf, (size_t)buflen, "gcn::sddmm_kernel<%s, %s>", sddmm_sliced(p, k) ? "true" : "false",

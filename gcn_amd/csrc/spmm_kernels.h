@@ -154,6 +154,22 @@ struct SddmmArgs {
 hipError_t launch_sddmm(const SddmmArgs& s, hipStream_t st);
 bool sddmm_vec(const float* A, const float* B, int k);   // 16-byte loads (k % 4 == 0, aligned operands)
 
+// edge_softmax.hip — softmax over the stored entries of each CSR row, its backward, the fused GAT-score forms and CSR row
+// sums (plan-free, capturable, no atomics: see the file's header).  ws: edge_workspace_bytes(nnz) bytes of device memory —
+// a flag and one partial per (chunk of kEdgeChunk entries, long row) — owned by the call while it runs.
+constexpr int kEdgeChunk = 8192;
+size_t edge_workspace_bytes(int nnz);
+hipError_t launch_edge_softmax(const int* rowptr, int m, int nnz, const float* s, float* p, void* ws, hipStream_t st);
+hipError_t launch_edge_softmax_backward(const int* rowptr, int m, int nnz, const float* p, const float* g, float* ds, void* ws,
+                                        hipStream_t st);
+hipError_t launch_gat_edge_softmax(const int* rowptr, const int* col, int m, int nnz, const float* a_dst, const float* a_src,
+                                   float slope, float* p, void* ws, hipStream_t st);
+hipError_t launch_gat_edge_softmax_backward(const int* rowptr, const int* col, int m, int nnz, const float* a_dst,
+                                            const float* a_src, float slope, const float* p, const float* g, float* ds,
+                                            float* grad_a_dst, void* ws, hipStream_t st);
+hipError_t launch_segment_sum(const int* rowptr, int m, int nnz, const float* x, const int* perm, float* out, void* ws,
+                              hipStream_t st);
+
 // slicing.hip — mutable values.  vsrc[s*m + r] = CSR position of the first entry of row r in slice s (from the sliced
 // row pointer; column-sorted rows make every (row, slice) part one contiguous run of the CSR row).
 hipError_t build_value_map(const int* rowptr, const int* vrowptr, int m, int S, int* vsrc, hipStream_t st);

@@ -22,7 +22,8 @@ import torch.nn.functional as F
 from torch.nn.parameter import Parameter
 
 from . import preprocess, reorder, timers
-from .spmm import CsrAdjacency, _SpmmFunction, dropout_rows, gather_rows
+from .attention import gat_edge_softmax
+from .spmm import CsrAdjacency, _SpmmFunction, dropout_rows, gather_rows, spmm
 
 
 def _spmm_operand(x):
@@ -112,6 +113,75 @@ class GraphConvolution2(_Layer):
             with self.timers.hc.bi:
                 output = output + self.bias
         return F.relu(output) if relu else output
+
+
+class GraphAttention(nn.Module):
+    """Graph attention layer (GAT, Velickovic et al. 2018) on the native kernels.  Per head k, with h = x·W_k:
+
+        a_dst = h·att_dst[k],  a_src = h·att_src[k]
+        p[e]  = softmax over the stored entries of row(e) of leaky_relu(a_dst[row(e)] + a_src[col(e)], negative_slope)
+        out_k = spmm(adj, h, values=p)                          (row r aggregates its stored columns, weighted by p)
+
+    and the heads are concatenated (``concat=True``: heads·out_features columns) or averaged, then the bias is added.
+    The scores are fused into the softmax kernel (gat_edge_softmax), the aggregation is the learnable-value SpMM with its
+    SDDMM backward; nothing nnz-sized but p and its gradient is ever stored.
+
+    ``adj``: a square CsrAdjacency made with ``mutable_values=True``; its pattern is the attention mask (self-loops
+    included or not, as the caller built it) and its own values are ignored — they are overwritten with p.  Heads are a
+    Python loop over that one plan: each head's backward re-lays the values its forward saved, so interleaving is safe.
+
+    Parameters: ``weight`` [in_features, heads·out_features], ``att_dst`` and ``att_src`` [heads, out_features] — Glorot
+    uniform, as in the paper's code — and ``bias`` [heads·out_features] (concat) or [out_features] (mean), zeros.
+    Under a bf16 autocast region x·W runs in bf16 like any matmul; the scores, the softmax and the weighted SpMM run in
+    fp32 (h is widened): there is no bf16 softmax kernel, and p's gradient comes from the fp32 SDDMM."""
+
+    def __init__(self, in_features, out_features, heads=1, concat=True, negative_slope=0.2, with_bias=True):
+        super().__init__()
+        self.in_features, self.out_features, self.heads = int(in_features), int(out_features), int(heads)
+        self.concat, self.negative_slope = bool(concat), float(negative_slope)
+        if self.heads < 1:
+            raise ValueError("heads must be at least 1")
+        self.weight = Parameter(torch.empty(self.in_features, self.heads * self.out_features))
+        self.att_dst = Parameter(torch.empty(self.heads, self.out_features))
+        self.att_src = Parameter(torch.empty(self.heads, self.out_features))
+        if with_bias:
+            self.bias = Parameter(torch.empty(self.heads * self.out_features if self.concat else self.out_features))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.xavier_uniform_(self.weight)
+        nn.init.xavier_uniform_(self.att_dst)
+        nn.init.xavier_uniform_(self.att_src)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def forward(self, input, adj):
+        if adj.m != adj.n or input.shape[0] != adj.n:
+            raise ValueError(f"GraphAttention needs a square adjacency over the rows of its input: adjacency {adj.m}x{adj.n}, "
+                             f"input {tuple(input.shape)}")
+        h = torch.mm(input, self.weight)                # (bf16 under a bf16 autocast region, like any matmul)
+        # everything after x·W runs with autocast off: inside the region it would cast torch.mv's operands back to
+        # bf16 (mv is on its lower-precision list), and the scores must be fp32 dot products of the widened h
+        with torch.autocast("cuda", enabled=False):
+            h = h.float()
+            outs = []
+            for k in range(self.heads):
+                hk = h[:, k * self.out_features:(k + 1) * self.out_features].contiguous()
+                a_dst = torch.mv(hk, self.att_dst[k].float())
+                a_src = torch.mv(hk, self.att_src[k].float())
+                p = gat_edge_softmax(adj, a_dst, a_src, self.negative_slope)
+                outs.append(spmm(adj, hk, values=p))
+            if self.heads == 1:
+                out = outs[0]
+            else:
+                out = torch.cat(outs, dim=1) if self.concat else torch.stack(outs).mean(0)
+            return out + self.bias.float() if self.bias is not None else out
+
+    def __repr__(self):
+        return (f"GraphAttention ({self.in_features} -> {self.out_features}, heads={self.heads}, "
+                f"{'concat' if self.concat else 'mean'})")
 
 
 class GCN(nn.Module):

@@ -233,6 +233,42 @@ int gcn_sddmm_csr_f32(gcn_spmm_plan_t* plan, const int32_t* rowptr_dev, const in
 /* name of the kernel a k-wide gcn_sddmm_csr_f32 on this plan launches (16-byte-aligned operands) */
 int gcn_spmm_plan_sddmm_kernel(const gcn_spmm_plan_t* plan, int32_t k, char* buf, int32_t buflen);
 
+/* Edge softmax family: softmax over the stored entries of each row of a CSR pattern, its backward, both fused with GAT
+ * scores, and CSR row sums of a per-entry array.  Plan-free: they work on the caller's CSR (rowptr_dev [m + 1], col_dev
+ * [nnz] where named), all per-entry arrays are fp32 [nnz] in CSR entry order.  They only enqueue (a 4-byte memset node and
+ * kernels): no allocation, no host synchronisation, no host read of device data — legal inside a stream capture.  No
+ * atomics: every output has one writer, results are bit-identical from call to call.  Any nnz an int32 holds is fine:
+ * entries are addressed as offsets from their row's start, never past its end.  Row lengths may be anything — short
+ * rows share a wave, a row of more than 8192 entries is spread over the chip, empty rows cost a row-pointer read.
+ * ws: device scratch of at least GCN_EDGE_WS_BYTES(nnz) bytes, 16-byte aligned, owned by the call until it has run
+ * (calls on different streams need different ones).  Null pointers, negative sizes or a short workspace:
+ * GCN_ERR_INVALID_ARG; m == 0 or nnz == 0: GCN_OK, nothing is launched and nothing written. */
+#define GCN_EDGE_WS_BYTES(nnz) (16 + 16 * (((size_t)(nnz) + 8191) / 8192))
+/* p[e] = exp(scores[e] - max_row) / sum_row exp(scores[e'] - max_row).  p may alias scores.  Empty rows write nothing.
+ * DELIBERATELY UNLIKE torch.softmax, so that masks work: a row whose entries are all -inf gets zeros, not NaN (an entry of
+ * -inf beside a finite one gets 0, as there).  A NaN makes every entry of its own row NaN and touches no other row. */
+int gcn_edge_softmax_csr_f32(const int32_t* rowptr_dev, int32_t m, int32_t nnz, const float* scores, float* p, void* ws,
+                             size_t ws_bytes, void* stream);
+/* ds[e] = p[e] * (g[e] - sum_row p[e'] g[e']) from the saved p and the incoming gradient g.  ds may alias g. */
+int gcn_edge_softmax_backward_csr_f32(const int32_t* rowptr_dev, int32_t m, int32_t nnz, const float* p, const float* g,
+                                      float* ds, void* ws, size_t ws_bytes, void* stream);
+/* The same softmax of s[e] = leaky_relu(a_dst[row(e)] + a_src[col(e)], negative_slope), computed on the fly: the score
+ * array is never written.  a_dst [m], a_src [n] (gathered by column). */
+int gcn_gat_edge_softmax_csr_f32(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz, const float* a_dst,
+                                 const float* a_src, float negative_slope, float* p, void* ws, size_t ws_bytes, void* stream);
+/* Its backward: recomputes the scores, writes ds[e] = p (g - sum_row p g) * (s_pre > 0 ? 1 : negative_slope) — the
+ * derivative at 0 is the slope, as in torch — and grad_a_dst[r] = sum_row ds (0 for an empty row).  ds may alias g.
+ * grad_a_src[c] = sum over col(e) = c of ds[e] is gcn_segment_sum_csr_f32 over the transpose's row pointer with the
+ * permutation that takes CSR order to the transpose's order. */
+int gcn_gat_edge_softmax_backward_csr_f32(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz,
+                                          const float* a_dst, const float* a_src, float negative_slope, const float* p,
+                                          const float* g, float* ds, float* grad_a_dst, void* ws, size_t ws_bytes,
+                                          void* stream);
+/* out[r] = sum of x[e] over the entries e of row r (0 for an empty row); with perm_dev (int32 [nnz], may be NULL) the
+ * entry read is x[perm_dev[e]]. */
+int gcn_segment_sum_csr_f32(const int32_t* rowptr_dev, int32_t m, int32_t nnz, const float* x, const int32_t* perm_dev,
+                            float* out, void* ws, size_t ws_bytes, void* stream);
+
 /* LDS-staged row panels (optional): for matrices whose non-zeros sit near the diagonal (community
  * graphs after Rabbit / RCM / Gorder renumbering) a workgroup stages the feature rows of its panel's
  * column window (512 rows x 64 columns = 128 KiB of LDS) once and sums the in-window non-zeros
