@@ -153,7 +153,16 @@ spmm_chunk_kernel(const int* __restrict__ g_rowptr, const int* __restrict__ g_co
 #pragma unroll
   for (int i = 0; i < VEC; ++i) bias[i] = 0.f;
   if (EPI) {
-    if (active && a.bias) load_vec<VEC>(a.bias + fcol, bias);
+    // float by float, once per wave: pick_vec looks at B, C and P, never at the bias pointer, which may sit at any
+    // 4-byte offset (k % VEC == 0, so an active lane's VEC columns are all below k).  Volatile keeps them dword loads:
+    // left alone, the compiler fuses them back into one 8- or 16-byte load from a 4-byte aligned address.  (A volatile
+    // access compiles to flat_load_dword sc0 sc1, past the caches: VEC loads per wave per launch, against the
+    // thousands of gathers that follow.)
+    if (active && a.bias) {
+      const volatile float* bp = a.bias + fcol;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) bias[i] = bp[i];
+    }
   }
 
   for (int c = c_lo + wave_in_xcd; c < c_hi; c += waves_per_xcd) {

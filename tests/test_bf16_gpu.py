@@ -16,7 +16,7 @@ import torch
 
 import gcn_amd
 from gcn_amd import graphgen
-from util import GOLDEN, oracle_spmm, random_csr, rel_err, sym_norm_graph
+from util import GOLDEN, bf16_assert_bound, bf16_reference, oracle_spmm, random_csr, rel_err, sym_norm_graph
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -32,20 +32,6 @@ def _bf16_features(n, k, seed):
     g = torch.Generator(device=DEV)
     g.manual_seed(seed)
     return torch.randn((n, k), generator=g, device=DEV, dtype=torch.float32).to(torch.bfloat16)
-
-
-def _reference(rowptr, col, val, B):
-    """(C*, |A|.|B|) in fp64 accumulation on the upcast bf16 operand"""
-    Bf = B.float().cpu().numpy()
-    return (oracle_spmm(rowptr, col, val, Bf).astype(np.float64),
-            oracle_spmm(rowptr, col, np.abs(val), np.abs(Bf)).astype(np.float64))
-
-
-def _assert_bound(C, Cref, absref, bf16_out, scale=1.0):
-    C = C.float().cpu().numpy().astype(np.float64)
-    bound = scale * (EPS * absref + (EPS * np.abs(Cref) if bf16_out else 0.0)) + 1e-6
-    excess = np.abs(C - Cref) - bound
-    assert excess.max() <= 0.0, f"bound exceeded by {excess.max():.3e} at {np.unravel_index(excess.argmax(), excess.shape)}"
 
 
 def _graphs():
@@ -73,12 +59,12 @@ def test_hot_path_value_free(name):
         B = _bf16_features(n, k, seed=k)
         kern = adj.main_kernel(k, dtype=torch.bfloat16)
         assert kern.startswith("gcn::spmm_group_bf16_kernel<"), (k, kern)
-        Cref, absref = _reference(rp, ci, va, B)
+        Cref, absref = bf16_reference(rp, ci, va, B)
         C16 = adj.matmul_raw(B)
         assert C16.dtype == torch.bfloat16 and C16.shape == (n, k)
-        _assert_bound(C16, Cref, absref, bf16_out=True)
+        bf16_assert_bound(C16, Cref, absref, bf16_out=True)
         C32 = adj.matmul_raw(B, out=torch.empty((n, k), dtype=torch.float32, device=DEV))
-        _assert_bound(C32, Cref, absref, bf16_out=False)
+        bf16_assert_bound(C32, Cref, absref, bf16_out=False)
         # the bf16 result is the fp32 one rounded once
         assert torch.equal(C16, C32.to(torch.bfloat16))
 
@@ -91,8 +77,8 @@ def test_hot_path_value_free_on_the_automatic_slice_sets():
         adj.enable_slicing(4)
     for k in (64, 128):
         B = _bf16_features(n, k, seed=11 + k)
-        Cref, absref = _reference(rp, ci, va, B)
-        _assert_bound(adj.matmul_raw(B), Cref, absref, bf16_out=True)
+        Cref, absref = bf16_reference(rp, ci, va, B)
+        bf16_assert_bound(adj.matmul_raw(B), Cref, absref, bf16_out=True)
         assert adj.main_kernel(k, dtype=torch.bfloat16).startswith("gcn::spmm_group_bf16_kernel<")
 
 
@@ -104,11 +90,11 @@ def test_hot_path_weighted():
         kern = adj.main_kernel(k, dtype=torch.bfloat16)
         assert kern.startswith("gcn::spmm_group_bf16_weighted_kernel<"), (k, kern)
         B = _bf16_features(n, k, seed=100 + k)
-        Cref, absref = _reference(rp, ci, va, B)
+        Cref, absref = bf16_reference(rp, ci, va, B)
         C32 = adj.matmul_raw(B, out=torch.empty((m, k), dtype=torch.float32, device=DEV))
         assert rel_err(C32.cpu().numpy(), Cref) <= 1e-5
         C16 = adj.matmul_raw(B)
-        _assert_bound(C16, Cref, absref, bf16_out=True)
+        bf16_assert_bound(C16, Cref, absref, bf16_out=True)
 
 
 def _fallback_cases():
@@ -129,11 +115,11 @@ def test_fallback_widths_and_plans(case):
     for k in (1, 8, 16, 40, 41, 100):
         assert not adj.main_kernel(k, dtype=torch.bfloat16).startswith("gcn::spmm_group_bf16")
         B = _bf16_features(shape[1], k, seed=200 + k)
-        Cref, absref = _reference(rp, ci, va, B)
+        Cref, absref = bf16_reference(rp, ci, va, B)
         C32 = adj.matmul_raw(B, out=torch.empty((shape[0], k), dtype=torch.float32, device=DEV))
         assert rel_err(C32.cpu().numpy(), Cref) <= 1e-5, (case, k)
         C16 = adj.matmul_raw(B)
-        _assert_bound(C16, Cref, absref, bf16_out=True)
+        bf16_assert_bound(C16, Cref, absref, bf16_out=True)
         assert torch.equal(C16, adj.matmul_raw(B))                   # deterministic
 
 
@@ -150,7 +136,7 @@ def test_epilogue_bias_relu_dropout(k):
     B = _bf16_features(n, k, seed=300 + k)
     bias = torch.randn(k, device=DEV) * 0.1
     p, seed, off = 0.3, 1234, 7
-    Cref, absref = _reference(rp, ci, va, B)
+    Cref, absref = bf16_reference(rp, ci, va, B)
     keep = _keep_mask(n * k, p, seed, off).reshape(n, k).cpu().numpy()
     # dropout without ReLU: the dropped positions are those of the fp32 epilogue
     C32 = adj.matmul_raw(B.float(), bias=bias, dropout=(p, seed, off))
@@ -165,7 +151,7 @@ def test_epilogue_bias_relu_dropout(k):
             if relu:
                 Z = np.maximum(Z, 0.0)
             E = np.where(keep, Z / (1.0 - p), 0.0)
-            _assert_bound(C, E, absref, bf16_out=out_dtype == torch.bfloat16, scale=1.0 / (1.0 - p) + 1e-3)
+            bf16_assert_bound(C, E, absref, bf16_out=out_dtype == torch.bfloat16, scale=1.0 / (1.0 - p) + 1e-3)
 
 
 def test_dropout_rows_bf16_matches_the_fp32_mask():
@@ -214,15 +200,15 @@ def test_autograd_non_symmetric():
     x = _bf16_features(n, k, seed=21).requires_grad_(True)
     y = gcn_amd.spmm(adj, x)
     assert y.dtype == torch.bfloat16
-    Cref, absref = _reference(rp, ci, va, x.detach())
-    _assert_bound(y.detach(), Cref, absref, bf16_out=True)
+    Cref, absref = bf16_reference(rp, ci, va, x.detach())
+    bf16_assert_bound(y.detach(), Cref, absref, bf16_out=True)
     g = _bf16_features(m, k, seed=22)
     y.backward(g)
     assert x.grad.dtype == torch.bfloat16
     At = sp.csr_matrix((va, ci, rp), shape=(m, n)).T.tocsr()
     At.sort_indices()
-    Gref, gabs = _reference(At.indptr.astype(np.int32), At.indices.astype(np.int32), At.data.astype(np.float32), g)
-    _assert_bound(x.grad, Gref, gabs, bf16_out=True)
+    Gref, gabs = bf16_reference(At.indptr.astype(np.int32), At.indices.astype(np.int32), At.data.astype(np.float32), g)
+    bf16_assert_bound(x.grad, Gref, gabs, bf16_out=True)
 
 
 def _sbm_problem():

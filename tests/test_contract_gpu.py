@@ -159,7 +159,7 @@ def test_duplicate_columns_sliced_virtual_csr_with_and_without_values():
 def test_duplicate_columns_lds_panels_and_mfma_panels():
     """spmm_panel_in_quad_kernel (LDS-staged window entries), spmm_panel_dense_mfma_kernel (dense tiles: duplicates
     ADD in the tile, spmm_panel.hip panel_split) and the accumulate pass over the out-of-window rest"""
-    from test_spmm_gpu import _banded_csr, _dense_band_csr
+    from util import banded_csr as _banded_csr, dense_band_csr as _dense_band_csr
     n = 3001
     rp, ci, va = _banded_csr(n, 150, 3, seed=5, hub=(777, 2600))
     rp, ci, va = with_duplicates(rp, ci, va, seed=6)

@@ -11,7 +11,7 @@ import torch
 
 import gcn_amd
 from gcn_amd import graphgen
-from util import oracle_spmm, random_csr, sym_norm_graph
+from util import check_sddmm, oracle_spmm, random_csr, sddmm_graph, sddmm_ref, sym_norm_graph, with_duplicate_entries
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -27,41 +27,8 @@ def _adj(rp, ci, va, shape, **kw):
     return gcn_amd.CsrAdjacency(_t(rp), _t(ci), _t(va), shape, **kw)
 
 
-def _with_duplicates(rp, ci, va, every=7):
-    """repeat every `every`-th entry in place (duplicate (r, c) entries; rows stay column-sorted)"""
-    rows = np.repeat(np.arange(len(rp) - 1), np.diff(rp))
-    rep = np.ones(len(ci), dtype=np.int64)
-    rep[::every] = 2
-    ci2, rows2 = np.repeat(ci, rep), np.repeat(rows, rep)
-    va2 = np.repeat(va, rep) * np.float32(0.5)
-    rp2 = np.zeros(len(rp), dtype=np.int32)
-    rp2[1:] = np.cumsum(np.bincount(rows2, minlength=len(rp) - 1))
-    return rp2, ci2.astype(np.int32), va2.astype(np.float32)
-
-
-_G = {}
-
-
-def _graph(name):
-    """(rowptr, col, val, m, n) numpy"""
-    if name not in _G:
-        if name == "rect":                                   # m != n, empty rows, hub rows, duplicates
-            rp, ci, va = random_csr(700, 1300, 30000, seed=5, empty_rows=0.1, long_rows=((3, 400), (10, 900)))
-            rp, ci, va = _with_duplicates(rp, ci, va)
-            _G[name] = (rp, ci, va, 700, 1300)
-        elif name == "sym":                                  # normalised: the values factor
-            rp, ci, va = sym_norm_graph(3000, 90000, seed=2)
-            _G[name] = (rp, ci, va, 3000, 3000)
-        else:                                                # runs the group kernels when sliced (slices=4)
-            rp, ci, va, n = graphgen.make_graph("reddit", device="cpu", seed=1, scale=0.02)
-            rp, ci, va = rp.numpy(), ci.numpy(), va.numpy()
-            rp, ci, va = _with_duplicates(rp, ci, va, every=101)
-            _G[name] = (rp, ci, va, n, n)
-    return _G[name]
-
-
 def _plans(name):
-    rp, ci, va, m, n = _graph(name)
+    rp, ci, va, m, n = sddmm_graph(name)
     yield "unsliced", _adj(rp, ci, va, (m, n), slices=0)
     if name != "rect":
         yield "auto", _adj(rp, ci, va, (m, n))
@@ -69,30 +36,9 @@ def _plans(name):
     yield "panels", _adj(rp, ci, va, (m, n), slices=0, panels=1)
 
 
-def _sddmm_ref(rp, ci, A, B):
-    """(d*, sum_j |A_rj B_cj|) in fp64, evaluated on the device in pieces"""
-    rows = torch.from_numpy(np.repeat(np.arange(len(rp) - 1), np.diff(rp))).to(DEV)
-    cols = torch.from_numpy(ci.astype(np.int64)).to(DEV)
-    Ad, Bd = _t(A).double(), _t(B).double()
-    ref, mag = [], []
-    for i in range(0, len(ci), 1 << 18):
-        p = Ad[rows[i:i + (1 << 18)]] * Bd[cols[i:i + (1 << 18)]]
-        ref.append(p.sum(1))
-        mag.append(p.abs().sum(1))
-    if not ref:
-        return np.zeros(0), np.zeros(0)
-    return torch.cat(ref).cpu().numpy(), torch.cat(mag).cpu().numpy()
-
-
-def _check_sddmm(out, ref, mag):
-    d = out.cpu().numpy().astype(np.float64)
-    excess = np.abs(d - ref) - (1e-5 * mag + 1e-30)
-    assert excess.max() <= 0.0, f"bound exceeded by {excess.max():.3e} at {excess.argmax()}"
-
-
 @pytest.mark.parametrize("name", ["rect", "sym", "reddit"])
 def test_sddmm_parity_fp64(name):
-    rp, ci, va, m, n = _graph(name)
+    rp, ci, va, m, n = sddmm_graph(name)
     rng = np.random.default_rng(7)
     plans = dict(_plans(name))
     if name == "reddit":                                     # the sliced walk on a plan that runs the group kernels
@@ -107,11 +53,11 @@ def test_sddmm_parity_fp64(name):
     for k in ks:
         A = rng.standard_normal((m, k)).astype(np.float32)
         B = rng.standard_normal((n, k)).astype(np.float32)
-        ref, mag = _sddmm_ref(rp, ci, A, B)
+        ref, mag = sddmm_ref(rp, ci, A, B, DEV)
         Ad, Bd = _t(A), _t(B)
         outs = {pn: adj.sddmm(Ad, Bd) for pn, adj in plans.items()}
         for pn, out in outs.items():
-            _check_sddmm(out, ref, mag)
+            check_sddmm(out, ref, mag)
         # one device function per entry: the same bits whatever plan walks it, and on a second call
         first = next(iter(outs.values()))
         for pn, out in outs.items():
@@ -120,7 +66,7 @@ def test_sddmm_parity_fp64(name):
 
 
 def test_sddmm_nan_stays_in_its_row():
-    rp, ci, va, m, n = _graph("reddit")
+    rp, ci, va, m, n = sddmm_graph("reddit")
     adj = _adj(rp, ci, va, (m, n), slices=4)
     k = 128
     A = torch.randn((m, k), device=DEV)
@@ -134,7 +80,7 @@ def test_sddmm_nan_stays_in_its_row():
 
 
 def test_sddmm_k0_and_bf16():
-    rp, ci, va, m, n = _graph("rect")
+    rp, ci, va, m, n = sddmm_graph("rect")
     adj = _adj(rp, ci, va, (m, n))
     assert torch.equal(adj.sddmm(torch.empty((m, 0), device=DEV), torch.empty((n, 0), device=DEV)),
                        torch.zeros(len(ci), device=DEV))
@@ -153,7 +99,7 @@ def _oracle(rp, ci, w, X):
 def test_refresh_matches_fresh_plan_and_oracle(name):
     """start from values that factor (a value-free plan if they stayed), refresh to new ones: every SpMM equals a fresh
     mutable plan on the new values bit for bit, and the fp64 oracle to 1e-5"""
-    rp, ci, va, m, n = _graph(name)
+    rp, ci, va, m, n = sddmm_graph(name)
     rng = np.random.default_rng(3)
     w2 = (rng.random(len(ci)) + 0.1).astype(np.float32)
     # ("panels_dropped": panels asked for; a mutable plan has none, so it runs unsliced — asserted below)
@@ -185,7 +131,7 @@ def test_refresh_matches_fresh_plan_and_oracle(name):
 
 
 def test_update_values_refused_on_fixed_plan():
-    rp, ci, va, m, n = _graph("reddit")
+    rp, ci, va, m, n = sddmm_graph("reddit")
     adj = _adj(rp, ci, va, (m, n))
     X = torch.randn((n, 128), device=DEV)
     before = adj.matmul_raw(X).clone()
@@ -207,7 +153,7 @@ def _cpu_grads(rp, ci, w, x, shape, weight):
 
 @pytest.mark.parametrize("name", ["rect", "sym-asym", "reddit"])
 def test_autograd_matches_cpu(name):
-    rp, ci, va, m, n = _graph("sym" if name == "sym-asym" else name)
+    rp, ci, va, m, n = sddmm_graph("sym" if name == "sym-asym" else name)
     rng = np.random.default_rng(11)
     w = (rng.random(len(ci)) + 0.1).astype(np.float32)     # (asymmetric learned values on a symmetric pattern)
     k = 48
@@ -248,7 +194,7 @@ def _train(adj_or_none, rp, ci, w0, x, tgt, steps, device):
 
 
 def test_training_loop_follows_cpu():
-    rp, ci, va, m, n = _graph("rect")
+    rp, ci, va, m, n = sddmm_graph("rect")
     rng = np.random.default_rng(5)
     x = rng.standard_normal((n, 32)).astype(np.float32)
     tgt = rng.standard_normal((m, 32)).astype(np.float32)
@@ -259,7 +205,7 @@ def test_training_loop_follows_cpu():
 
 
 def test_hip_graph_replay_equals_eager():
-    rp, ci, va, m, n = _graph("reddit")
+    rp, ci, va, m, n = sddmm_graph("reddit")
     rng = np.random.default_rng(9)
     k, steps = 64, 3
     x = _t(rng.standard_normal((n, k)).astype(np.float32))
@@ -298,7 +244,7 @@ def test_hip_graph_replay_equals_eager():
 
 
 def test_sparse_mm_routing_with_sparse_grad():
-    rp, ci, va, m, n = _graph("rect")
+    rp, ci, va, m, n = sddmm_graph("rect")
     rows = np.repeat(np.arange(m), np.diff(rp))
     # (duplicates would be summed by coalesce: use the distinct pattern)
     key = rows.astype(np.int64) * n + ci
@@ -341,7 +287,7 @@ def test_sparse_mm_routing_with_sparse_grad():
 @pytest.mark.parametrize("slices", [0, 4])
 def test_callers_values_are_never_written(slices):
     """a mutable adjacency owns its values: neither the tensor it was built from nor any values handed to it change"""
-    rp, ci, va, m, n = _graph("reddit")
+    rp, ci, va, m, n = sddmm_graph("reddit")
     rng = np.random.default_rng(21)
     w0 = _t(va)
     adj = gcn_amd.CsrAdjacency(_t(rp), _t(ci), w0, (m, n), mutable_values=True, slices=slices)
@@ -359,7 +305,7 @@ def test_callers_values_are_never_written(slices):
 
 
 def test_sparse_mm_routing_leaves_values_unchanged():
-    rp, ci, va, m, n = _graph("rect")
+    rp, ci, va, m, n = sddmm_graph("rect")
     rows = np.repeat(np.arange(m), np.diff(rp))
     key = rows.astype(np.int64) * n + ci
     keep = np.concatenate([[True], key[1:] != key[:-1]])
@@ -392,7 +338,7 @@ def test_sparse_mm_routing_leaves_values_unchanged():
 def test_plain_backward_after_update_values_uses_new_values(slices):
     """update_values(w2), then the values-free spmm: x.grad = Â(w2)ᵀ·g, against fp64 — also on
     a pattern flagged symmetric, whose learned values are not"""
-    rp, ci, va, m, n = _graph("sym")
+    rp, ci, va, m, n = sddmm_graph("sym")
     rng = np.random.default_rng(13)
     adj = _adj(rp, ci, va, (m, n), mutable_values=True, symmetric=True, slices=slices)
     x = torch.randn((n, 64), device=DEV, requires_grad=True)

@@ -15,7 +15,7 @@ import torch
 
 import gcn_amd
 from gcn_amd import _lib, dropin, graphgen
-from util import GOLDEN, oracle_spmm, random_csr, rel_err, sym_norm_graph
+from util import GOLDEN, banded_csr, dense_band_csr, oracle_spmm, random_csr, rel_err, sym_norm_graph
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -733,31 +733,12 @@ def test_wide_column_space_beyond_2_pow_24_and_4GiB_of_features():
     assert err <= TOL
 
 
-def _banded_csr(n, half_band, extra, seed, hub=None):
-    """near-diagonal matrix (what a renumbered community graph looks like) + a few far entries"""
-    rng = np.random.default_rng(seed)
-    rows, cols = [], []
-    for r in range(n):
-        lo, hi = max(0, r - half_band), min(n, r + half_band + 1)
-        c = rng.choice(np.arange(lo, hi), size=min(hi - lo, int(rng.integers(0, 2 * half_band // 3 + 2))), replace=False)
-        far = rng.integers(0, n, extra)
-        cc = np.unique(np.concatenate([c, far]))
-        if hub is not None and r == hub[0]:
-            cc = np.unique(rng.choice(n, hub[1], replace=False))
-        rows.append(np.full(len(cc), r)); cols.append(cc)
-    rows, cols = np.concatenate(rows), np.concatenate(cols)
-    import scipy.sparse as sp
-    A = sp.csr_matrix((rng.standard_normal(len(rows)).astype(np.float32), (rows, cols)), shape=(n, n))
-    A.sort_indices()
-    return A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float32)
-
-
 @pytest.mark.parametrize("k", [33, 64, 100, 128, 200])
 def test_parity_lds_staged_row_panels(k):
     """spmm_panel_kernel: window hits from LDS, misses from global, hub row by the whole workgroup,
     empty rows, last partial panel, epilogue; forced on and automatic"""
     n = 3001
-    rowptr, col, val = _banded_csr(n, 150, 3, seed=k, hub=(777, 2600))
+    rowptr, col, val = banded_csr(n, 150, 3, seed=k, hub=(777, 2600))
     rng = np.random.default_rng(k)
     B = rng.standard_normal((n, k)).astype(np.float32)
     bias = rng.standard_normal(k).astype(np.float32)
@@ -787,7 +768,7 @@ def test_panels_with_everything_staged_and_with_nothing_staged():
     """both degenerate splits: A_out empty (epilogue-only second phase) and A_in (almost) empty"""
     d = _dev()
     n, k = 2000, 96
-    rowptr, col, val = _banded_csr(n, 100, 0, seed=3)             # every entry inside its panel's window
+    rowptr, col, val = banded_csr(n, 100, 0, seed=3)             # every entry inside its panel's window
     rng = np.random.default_rng(4)
     B = rng.standard_normal((n, k)).astype(np.float32)
     bias = rng.standard_normal(k).astype(np.float32)
@@ -1020,24 +1001,6 @@ def test_value_free_pass_with_slices_wider_than_the_15_bit_stream():
     assert rel_err(adj2.matmul_raw(torch.from_numpy(B).to(_dev())).cpu().numpy(), oracle_spmm(rowptr, col, val2, B)) <= TOL
 
 
-def _dense_band_csr(n, half_band, density, seed, sparse_from=None):
-    """rows hold `density` of the columns within +-half_band of the diagonal (rows >= sparse_from: 3 % instead),
-    plus a few far entries: the 128 x 512 windows of the panels are 25-60 % dense"""
-    rng = np.random.default_rng(seed)
-    rows, cols = [], []
-    for r in range(n):
-        lo, hi = max(0, r - half_band), min(n, r + half_band + 1)
-        dens = density if sparse_from is None or r < sparse_from else 0.03
-        c = np.flatnonzero(rng.random(hi - lo) < dens) + lo
-        far = rng.integers(0, n, 2)
-        c = np.unique(np.concatenate([c, far]))
-        rows.append(np.full(len(c), r)); cols.append(c)
-    rows, cols = np.concatenate(rows), np.concatenate(cols)
-    A = sp.csr_matrix(((rng.standard_normal(len(rows)) * 0.5).astype(np.float32), (rows, cols)), shape=(n, n))
-    A.sort_indices()
-    return A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float32)
-
-
 @pytest.mark.parametrize("k", [64, 128, 100, 36])
 def test_dense_panels_run_on_the_matrix_cores(k):
     """panels whose 128 x 512 window is >= 25 % dense are stored as dense fp32 tiles and contracted with
@@ -1045,7 +1008,7 @@ def test_dense_panels_run_on_the_matrix_cores(k):
     kernel, entries outside the windows the accumulate pass; last partial panel, window clipped at the matrix
     edge, bias + ReLU"""
     n = 2500                                              # 19.5 panels; the last window ends at the matrix edge
-    rowptr, col, val = _dense_band_csr(n, 200, 0.6, seed=k, sparse_from=1700)
+    rowptr, col, val = dense_band_csr(n, 200, 0.6, seed=k, sparse_from=1700)
     d = _dev()
     adj = _adj(rowptr, col, val, n, n, panels=1)
     assert adj.panel_rows == 128 and 10 <= adj.dense_panels <= 14        # rows < 1700 dense, the rest sparse
@@ -1068,7 +1031,7 @@ def test_dense_panels_keep_non_finite_features_out_of_rows_that_do_not_reference
     """a dense contraction would multiply the zeros of A with an Inf feature value (0 * Inf = NaN) and poison the
     whole panel; a window that holds a non-finite value is summed entry by entry instead"""
     n, k = 1536, 64
-    rowptr, col, val = _dense_band_csr(n, 200, 0.5, seed=3)
+    rowptr, col, val = dense_band_csr(n, 200, 0.5, seed=3)
     adj = _adj(rowptr, col, val, n, n, panels=1)
     assert adj.dense_panels == 12
     B = np.random.default_rng(3).standard_normal((n, k)).astype(np.float32)

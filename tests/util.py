@@ -116,3 +116,191 @@ def sampled_rows_oracle_err(rowptr_dev, col_dev, val_dev, B_dev, C_dev, rows):
     sub_rp[1:] = np.cumsum(lens.cpu().numpy())
     Cref = oracle_spmm(sub_rp, inv.to(torch.int32).cpu().numpy(), val_dev[e].cpu().numpy(), B_dev[uniq].cpu().numpy())
     return rel_err(C_dev[r].cpu().numpy(), Cref), int(e.numel())
+
+
+# ---- operands at chosen alignments, and the dropout mask's reference ----
+SENTINEL = {4: 0x7FC12345, 2: 0x7FC1}                   # NaN payloads (fp32 / bf16), compared as integers
+_INT_VIEW = {4: "int32", 2: "int16"}
+
+
+def _as_int(t):
+    import torch
+    return t.view(getattr(torch, _INT_VIEW[t.element_size()]))
+
+
+def offset_view(t_or_shape, off, dtype, device, guard=64):
+    """A contiguous tensor whose first element lies `off` elements past a 16-byte boundary, with `guard` sentinel
+    elements on either side: → (view, flat).  `t_or_shape`: a tensor / array to copy in, or a shape (the view then
+    holds sentinels too: an output that must be written everywhere)."""
+    import torch
+    src = None
+    if isinstance(t_or_shape, (tuple, list, torch.Size)):
+        shape = tuple(int(s) for s in t_or_shape)
+    elif isinstance(t_or_shape, int):
+        shape = (t_or_shape,)
+    else:
+        src = t_or_shape if isinstance(t_or_shape, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t_or_shape))
+        shape = tuple(src.shape)
+    numel = int(np.prod(shape, dtype=np.int64)) if shape else 1
+    itemsize = torch.empty((), dtype=dtype).element_size()
+    assert (guard * itemsize) % 16 == 0, "guard must keep the buffer's 16-byte phase"
+    flat = torch.empty(guard + off + numel + guard, dtype=dtype, device=device)
+    assert flat.data_ptr() % 16 == 0
+    _as_int(flat).fill_(SENTINEL[itemsize])              # (int32 index arrays too: no valid index is that large)
+    view = flat[guard + off: guard + off + numel].view(shape)
+    if src is not None:
+        view.copy_(src.to(device=device, dtype=dtype))
+    assert view.data_ptr() % 16 == (off * itemsize) % 16
+    assert view.is_contiguous()
+    return view, flat
+
+
+def guards_intact(flat, view):
+    """every element of `flat` outside `view` still holds the sentinel's bits"""
+    import torch
+    itemsize = flat.element_size()
+    lo = (view.data_ptr() - flat.data_ptr()) // itemsize
+    hi = lo + view.numel()
+    f, want = _as_int(flat), SENTINEL[itemsize]
+    return bool(torch.all(f[:lo] == want)) and bool(torch.all(f[hi:] == want))
+
+
+def philox4x32_10(counter_words, key_words):
+    """Philox4x32-10 (Salmon et al., SC'11) on arrays: counter_words = (c0, c1, c2, c3), key_words = (k0, k1), each an
+    array (or scalar) of 32-bit values → the four result words as uint64 arrays holding 32-bit values."""
+    M0, M1, W0, W1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+    mask, sh = np.uint64(0xFFFFFFFF), np.uint64(32)
+    c0, c1, c2, c3, k0, k1 = np.broadcast_arrays(*[np.asarray(w, dtype=np.uint64) for w in (*counter_words, *key_words)])
+    for _ in range(10):
+        p0, p1 = M0 * c0, M1 * c2                        # 32 x 32 -> 64 bits: no overflow in uint64
+        hi0, lo0, hi1, lo1 = p0 >> sh, p0 & mask, p1 >> sh, p1 & mask
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + W0) & mask, (k1 + W1) & mask
+    return c0, c1, c2, c3
+
+
+def dropout_threshold(p):
+    """keep iff word >= threshold (include/gcn_spmm.h): p as the float32 the C ABI receives"""
+    t = float(np.float32(p)) * 4294967296.0
+    return 0xFFFFFFFF if t >= 4294967295.0 else int(np.floor(t))
+
+
+def dropout_keep(count, p, seed, offset):
+    """keep[i] of the dropout contract of include/gcn_spmm.h: word i % 4 of Philox4x32-10 with counter (i / 4, offset)
+    and key seed, kept iff >= p * 2^32"""
+    seed, offset = int(seed), int(offset)
+    j = np.arange((count + 3) // 4, dtype=np.uint64)
+    words = philox4x32_10((j & np.uint64(0xFFFFFFFF), j >> np.uint64(32), offset & 0xFFFFFFFF, offset >> 32),
+                          (seed & 0xFFFFFFFF, seed >> 32))
+    w = np.stack(words, axis=1).reshape(-1)[:count]
+    return w >= np.uint64(dropout_threshold(p))
+
+
+# ---- builders, references and bounds that more than one test module uses ----
+def banded_csr(n, half_band, extra, seed, hub=None):
+    """near-diagonal matrix (what a renumbered community graph looks like) + a few far entries"""
+    rng = np.random.default_rng(seed)
+    rows, cols = [], []
+    for r in range(n):
+        lo, hi = max(0, r - half_band), min(n, r + half_band + 1)
+        c = rng.choice(np.arange(lo, hi), size=min(hi - lo, int(rng.integers(0, 2 * half_band // 3 + 2))), replace=False)
+        far = rng.integers(0, n, extra)
+        cc = np.unique(np.concatenate([c, far]))
+        if hub is not None and r == hub[0]:
+            cc = np.unique(rng.choice(n, hub[1], replace=False))
+        rows.append(np.full(len(cc), r)); cols.append(cc)
+    rows, cols = np.concatenate(rows), np.concatenate(cols)
+    A = sp.csr_matrix((rng.standard_normal(len(rows)).astype(np.float32), (rows, cols)), shape=(n, n))
+    A.sort_indices()
+    return A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float32)
+
+
+def dense_band_csr(n, half_band, density, seed, sparse_from=None):
+    """rows hold `density` of the columns within +-half_band of the diagonal (rows >= sparse_from: 3 % instead),
+    plus a few far entries: the 128 x 512 windows of the panels are 25-60 % dense"""
+    rng = np.random.default_rng(seed)
+    rows, cols = [], []
+    for r in range(n):
+        lo, hi = max(0, r - half_band), min(n, r + half_band + 1)
+        dens = density if sparse_from is None or r < sparse_from else 0.03
+        c = np.flatnonzero(rng.random(hi - lo) < dens) + lo
+        far = rng.integers(0, n, 2)
+        c = np.unique(np.concatenate([c, far]))
+        rows.append(np.full(len(c), r)); cols.append(c)
+    rows, cols = np.concatenate(rows), np.concatenate(cols)
+    A = sp.csr_matrix(((rng.standard_normal(len(rows)) * 0.5).astype(np.float32), (rows, cols)), shape=(n, n))
+    A.sort_indices()
+    return A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float32)
+
+
+def with_duplicate_entries(rp, ci, va, every=7):
+    """repeat every `every`-th entry in place (duplicate (r, c) entries; rows stay column-sorted)"""
+    rows = np.repeat(np.arange(len(rp) - 1), np.diff(rp))
+    rep = np.ones(len(ci), dtype=np.int64)
+    rep[::every] = 2
+    ci2, rows2 = np.repeat(ci, rep), np.repeat(rows, rep)
+    va2 = np.repeat(va, rep) * np.float32(0.5)
+    rp2 = np.zeros(len(rp), dtype=np.int32)
+    rp2[1:] = np.cumsum(np.bincount(rows2, minlength=len(rp) - 1))
+    return rp2, ci2.astype(np.int32), va2.astype(np.float32)
+
+
+_SDDMM_GRAPHS = {}
+
+
+def sddmm_graph(name):
+    """the graphs of tests/test_sddmm_gpu.py: (rowptr, col, val, m, n) numpy"""
+    from gcn_amd import graphgen
+    if name not in _SDDMM_GRAPHS:
+        if name == "rect":                                   # m != n, empty rows, hub rows, duplicates
+            rp, ci, va = random_csr(700, 1300, 30000, seed=5, empty_rows=0.1, long_rows=((3, 400), (10, 900)))
+            rp, ci, va = with_duplicate_entries(rp, ci, va)
+            _SDDMM_GRAPHS[name] = (rp, ci, va, 700, 1300)
+        elif name == "sym":                                  # normalised: the values factor
+            rp, ci, va = sym_norm_graph(3000, 90000, seed=2)
+            _SDDMM_GRAPHS[name] = (rp, ci, va, 3000, 3000)
+        else:                                                # runs the group kernels when sliced (slices=4)
+            rp, ci, va, n = graphgen.make_graph("reddit", device="cpu", seed=1, scale=0.02)
+            rp, ci, va = rp.numpy(), ci.numpy(), va.numpy()
+            rp, ci, va = with_duplicate_entries(rp, ci, va, every=101)
+            _SDDMM_GRAPHS[name] = (rp, ci, va, n, n)
+    return _SDDMM_GRAPHS[name]
+
+
+def sddmm_ref(rp, ci, A, B, device):
+    """(d*, sum_j |A_rj B_cj|) in fp64, evaluated on the device in pieces"""
+    import torch
+    rows = torch.from_numpy(np.repeat(np.arange(len(rp) - 1), np.diff(rp))).to(device)
+    cols = torch.from_numpy(ci.astype(np.int64)).to(device)
+    Ad, Bd = (torch.from_numpy(np.ascontiguousarray(x)).to(device).double() for x in (A, B))
+    ref, mag = [], []
+    for i in range(0, len(ci), 1 << 18):
+        p = Ad[rows[i:i + (1 << 18)]] * Bd[cols[i:i + (1 << 18)]]
+        ref.append(p.sum(1))
+        mag.append(p.abs().sum(1))
+    if not ref:
+        return np.zeros(0), np.zeros(0)
+    return torch.cat(ref).cpu().numpy(), torch.cat(mag).cpu().numpy()
+
+
+def check_sddmm(out, ref, mag):
+    d = out.cpu().numpy().astype(np.float64)
+    excess = np.abs(d - ref) - (1e-5 * mag + 1e-30)
+    assert excess.max() <= 0.0, f"bound exceeded by {excess.max():.3e} at {excess.argmax()}"
+
+
+BF16_EPS = 2.0 ** -8
+
+
+def bf16_reference(rowptr, col, val, B):
+    """(C*, |A|.|B|) in fp64 accumulation on the upcast bf16 operand"""
+    Bf = B.float().cpu().numpy()
+    return (oracle_spmm(rowptr, col, val, Bf).astype(np.float64),
+            oracle_spmm(rowptr, col, np.abs(val), np.abs(Bf)).astype(np.float64))
+
+
+def bf16_assert_bound(C, Cref, absref, bf16_out, scale=1.0):
+    C = C.float().cpu().numpy().astype(np.float64)
+    bound = scale * (BF16_EPS * absref + (BF16_EPS * np.abs(Cref) if bf16_out else 0.0)) + 1e-6
+    excess = np.abs(C - Cref) - bound
+    assert excess.max() <= 0.0, f"bound exceeded by {excess.max():.3e} at {np.unravel_index(excess.argmax(), excess.shape)}"
