@@ -16,7 +16,7 @@ import torch
 
 import gcn_amd
 from gcn_amd import dropin
-from util import oracle_spmm, random_csr, rel_err, sym_norm_graph
+from util import oracle_spmm, random_csr, rel_err, sym_norm_graph, with_duplicates
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -31,34 +31,6 @@ def _adj(rowptr, col, val, m, n, **kw):
     d = _dev()
     return gcn_amd.CsrAdjacency(torch.from_numpy(rowptr).to(d), torch.from_numpy(col).to(d),
                                 torch.from_numpy(val).to(d), (m, n), **kw)
-
-
-def with_duplicates(rowptr, col, val, seed, frac_rows=0.5, u_row=None, u_col=None):
-    """the same pattern with 2-5 copies of some entries (copies sit next to the original: rows stay column-sorted).
-    Values of the copies: random (the matrix then does not factor), or u_row[r]*u_col[c] when factors are given."""
-    rng = np.random.default_rng(seed)
-    m = len(rowptr) - 1
-    lens = np.diff(rowptr)
-    rep = np.ones(len(col), np.int64)
-    rows_of = np.repeat(np.arange(m), lens)
-    pick_rows = rng.random(m) < frac_rows
-    cand = np.flatnonzero(pick_rows[rows_of] & (rng.random(len(col)) < 0.15))
-    rep[cand] = rng.integers(2, 6, len(cand))
-    if len(col):                                        # the first and the last entry of the matrix too (chunk edges)
-        rep[0], rep[-1] = 3, 5
-    col2 = np.repeat(col, rep)
-    rows2 = np.repeat(rows_of, rep)
-    if u_row is not None:
-        val2 = (u_row[rows2].astype(np.float64) * u_col[col2].astype(np.float64)).astype(np.float32)
-    else:
-        val2 = np.repeat(val, rep)
-        extra = np.ones(len(col2), bool)
-        extra[np.cumsum(rep) - rep] = False             # the first copy keeps the original value
-        val2[extra] = (rng.standard_normal(int(extra.sum())) * 0.5).astype(np.float32)
-    rp2 = np.zeros(m + 1, np.int64)
-    np.add.at(rp2, rows2 + 1, 1)
-    rp2 = np.cumsum(rp2)
-    return rp2.astype(np.int32), col2.astype(np.int32), val2.astype(np.float32)
 
 
 def _check(adj, rowptr, col, val, n, k, seed=0, epilogue=True):

@@ -304,3 +304,295 @@ def bf16_assert_bound(C, Cref, absref, bf16_out, scale=1.0):
     bound = scale * (BF16_EPS * absref + (BF16_EPS * np.abs(Cref) if bf16_out else 0.0)) + 1e-6
     excess = np.abs(C - Cref) - bound
     assert excess.max() <= 0.0, f"bound exceeded by {excess.max():.3e} at {np.unravel_index(excess.argmax(), excess.shape)}"
+
+
+# ---- exact-arithmetic and element-wise checks of the fp32 / bf16 SpMM (test_exact_cpu.py, test_exact_gpu.py) ----
+# Leg 1: operands whose every fp32 partial sum is exact in any order, so the result must EQUAL the fp64 oracle.
+# Leg 2: operands spanning 2^+-34 in scale, every element within (L_i + 16) u of its own |A|.|B| (u = 2^-24).
+def with_duplicates(rowptr, col, val, seed, frac_rows=0.5, u_row=None, u_col=None):
+    """the same pattern with 2-5 copies of some entries (copies sit next to the original: rows stay column-sorted).
+    Values of the copies: random (the matrix then does not factor), or u_row[r]*u_col[c] when factors are given."""
+    rng = np.random.default_rng(seed)
+    m = len(rowptr) - 1
+    lens = np.diff(rowptr)
+    rep = np.ones(len(col), np.int64)
+    rows_of = np.repeat(np.arange(m), lens)
+    pick_rows = rng.random(m) < frac_rows
+    cand = np.flatnonzero(pick_rows[rows_of] & (rng.random(len(col)) < 0.15))
+    rep[cand] = rng.integers(2, 6, len(cand))
+    if len(col):                                        # the first and the last entry of the matrix too (chunk edges)
+        rep[0], rep[-1] = 3, 5
+    col2 = np.repeat(col, rep)
+    rows2 = np.repeat(rows_of, rep)
+    if u_row is not None:
+        val2 = (u_row[rows2].astype(np.float64) * u_col[col2].astype(np.float64)).astype(np.float32)
+    else:
+        val2 = np.repeat(val, rep)
+        extra = np.ones(len(col2), bool)
+        extra[np.cumsum(rep) - rep] = False             # the first copy keeps the original value
+        val2[extra] = (rng.standard_normal(int(extra.sum())) * 0.5).astype(np.float32)
+    rp2 = np.zeros(m + 1, np.int64)
+    np.add.at(rp2, rows2 + 1, 1)
+    rp2 = np.cumsum(rp2)
+    return rp2.astype(np.int32), col2.astype(np.int32), val2.astype(np.float32)
+
+
+def reshape_rows(rowptr, col, n, seed, empty=0.05, hub=None, keep_diagonal=False, spare=()):
+    """pattern only: a fraction `empty` of the rows (row 1 and the last row among them) loses its entries — all but the
+    diagonal with keep_diagonal — and row hub[0] gets hub[1] distinct random columns instead of its own (and keeps its
+    diagonal with keep_diagonal); the rows `spare` stay as they are -> (rowptr, col), rows column-sorted"""
+    rng = np.random.default_rng(seed)
+    m = len(rowptr) - 1
+    rows = np.repeat(np.arange(m), np.diff(rowptr))
+    drop = rng.random(m) < empty
+    drop[[1, m - 1]] = True
+    drop[list(spare)] = False
+    if hub is not None:
+        drop[hub[0]] = True                             # (its own entries go, the hub's come below)
+    keep = ~drop[rows]
+    if keep_diagonal:
+        keep |= col == rows
+    rows, cols = rows[keep], col[keep].astype(np.int64)
+    if hub is not None:
+        hc = rng.choice(n, hub[1], replace=False)
+        if keep_diagonal:
+            hc = hc[hc != hub[0]]
+        rows, cols = np.concatenate([rows, np.full(len(hc), hub[0])]), np.concatenate([cols, hc])
+    order = np.lexsort((cols, rows))
+    rp = np.zeros(m + 1, np.int64)
+    rp[1:] = np.cumsum(np.bincount(rows, minlength=m))
+    return rp.astype(np.int32), cols[order].astype(np.int32)
+
+
+def random_rows_csr(m, n, lens, seed):
+    """pattern with the given row lengths, columns drawn with replacement (so some repeat), rows column-sorted; vectorised
+    (the matrices of millions of entries)"""
+    rng = np.random.default_rng(seed)
+    lens = np.asarray(lens, np.int64)
+    rows = np.repeat(np.arange(m), lens)
+    cols = rng.integers(0, n, len(rows))
+    order = np.lexsort((cols, rows))
+    rp = np.zeros(m + 1, np.int64)
+    rp[1:] = np.cumsum(lens)
+    return rp.astype(np.int32), cols[order].astype(np.int32)
+
+
+def _rows_of(rowptr):
+    return np.repeat(np.arange(len(rowptr) - 1), np.diff(rowptr))
+
+
+def int_features(n, k, seed, top=8):
+    """integers in [-top, top] (top <= 8)"""
+    assert 0 < top <= 8
+    return np.random.default_rng(seed).integers(-top, top + 1, (n, k)).astype(np.float32)
+
+
+def int_values(nnz, seed):
+    """non-zero integers in [-4, 4]"""
+    rng = np.random.default_rng(seed)
+    return (rng.integers(1, 5, nnz) * rng.choice([-1, 1], nnz)).astype(np.float32)
+
+
+def pow2_factors(n, seed):
+    """u = 2^-e, e in {0, 1, 2, 3}"""
+    return (2.0 ** -np.random.default_rng(seed).integers(0, 4, n)).astype(np.float32)
+
+
+def factored_values(rowptr, col, u_row, u_col):
+    """val[r, c] = u_row[r] * u_col[c], the exact product rounded once to fp32 (what the fp32 product gives too)"""
+    return (u_row[_rows_of(rowptr)].astype(np.float64) * u_col[col].astype(np.float64)).astype(np.float32)
+
+
+def wide_features(n, k, seed):
+    """standard_normal * 2^(p_c + q_j): an exponent in [-12, 12] per row of B and one per column"""
+    rng = np.random.default_rng(seed)
+    p, q = rng.integers(-12, 13, n), rng.integers(-12, 13, k)
+    return (rng.standard_normal((n, k)) * 2.0 ** (p[:, None] + q[None, :])).astype(np.float32)
+
+
+def wide_values(rowptr, seed):
+    """N(0, 0.5) * 2^s_r, s_r in [-10, 10] per row"""
+    rng = np.random.default_rng(seed)
+    s = rng.integers(-10, 11, len(rowptr) - 1)
+    return (rng.standard_normal(int(rowptr[-1])) * 0.5 * 2.0 ** s[_rows_of(rowptr)]).astype(np.float32)
+
+
+def wide_factors(n, seed):
+    """(0.5 + rand) * 2^a, a in [-10, 10]"""
+    rng = np.random.default_rng(seed)
+    return ((0.5 + rng.random(n)) * 2.0 ** rng.integers(-10, 11, n)).astype(np.float32)
+
+
+def _granule_log2(x):
+    """the smallest g >= 0 with x * 2^g all integers (asserted to exist below 2^-24)"""
+    x = np.asarray(x, np.float64).ravel()
+    for g in range(0, 25):
+        y = x * 2.0 ** g
+        if np.array_equal(y, np.rint(y)):
+            return g
+    raise AssertionError("operand is not a multiple of 2^-24")
+
+
+def assert_exact_inputs(rowptr, col, val, B, extra=None, scale=1.0):
+    """The precondition of the exact leg, on the test's own inputs: every product val*B is a multiple of 2^-g (g <= 6 for
+    the operands of the issue: 2^-6 value products, integer features), every row holds fewer than 32768 entries and
+    max_ij (|A|.|B|)_ij * 2^g < 2^24 — so every partial sum, in any order and any grouping, is an fp32 number.
+    extra [k]: a bias added to every row (joins the magnitude); scale: a power of two the result is multiplied with.
+    -> (the left side, the longest row)"""
+    g = _granule_log2(val) + _granule_log2(B)
+    if extra is not None:
+        g = max(g, _granule_log2(extra))
+    mag = oracle_spmm(rowptr, col, np.abs(val), np.abs(B)).astype(np.float64)
+    if extra is not None:
+        mag = mag + np.abs(np.asarray(extra, np.float64))[None, :]
+    lhs = float(mag.max()) * scale * 2.0 ** g if mag.size else 0.0
+    longest = int(np.diff(rowptr).max()) if len(rowptr) > 1 else 0
+    assert longest < 32768, longest
+    assert lhs < 2.0 ** 24, (lhs, g)
+    return lhs, longest
+
+
+def assert_exact(C, Cref, what=""):
+    """value equality on every element (values, not bits: the sign of a zero may differ)"""
+    C = np.asarray(C)
+    Cref = np.asarray(Cref)
+    assert C.shape == Cref.shape, (C.shape, Cref.shape, what)
+    if not np.array_equal(C, Cref):
+        bad = np.argwhere(C != Cref)
+        i = tuple(bad[0])
+        raise AssertionError(f"{what}: {len(bad)} of {C.size} elements differ, first at {i}: got {C[i]!r}, want {Cref[i]!r}")
+
+
+U24 = 2.0 ** -24
+BOUND_SLACK = 16      # 8u value-factor check + u_col*b + u_row scaling + bias add + the oracle's own rounding = 12, rounded up
+
+
+def elementwise_bound(rowptr, mag, slack=BOUND_SLACK):
+    """1.01 * (L_i + slack) * 2^-24 * mag_ij + 1e-37, L_i the stored length of row i (duplicates included)"""
+    L = np.diff(rowptr).astype(np.float64)[:, None]
+    return 1.01 * (L + slack) * U24 * np.asarray(mag, np.float64) + 1e-37
+
+
+def elementwise_ratio(C, Cref, mag, rowptr, slack=BOUND_SLACK):
+    """max_ij |C - C*|_ij / bound_ij (<= 1: inside the bound) and where it is reached"""
+    err = np.abs(np.asarray(C, np.float64) - np.asarray(Cref, np.float64))
+    ratio = err / elementwise_bound(rowptr, mag, slack)
+    if ratio.size == 0:
+        return 0.0, (0, 0)
+    at = np.unravel_index(int(np.nanargmax(ratio)), ratio.shape)
+    assert np.all(np.isfinite(np.asarray(C))), "non-finite result"
+    return float(ratio[at]), tuple(int(x) for x in at)
+
+
+def assert_elementwise(C, Cref, mag, rowptr, what="", slack=BOUND_SLACK):
+    ratio, at = elementwise_ratio(C, Cref, mag, rowptr, slack)
+    print(f"elementwise bound ratio {what}: {ratio:.4f} at {at}")
+    assert ratio <= 1.0, f"{what}: |C - C*| is {ratio:.3f} x the bound at {at} (row length {int(np.diff(rowptr)[at[0]])})"
+    return ratio
+
+
+def spmm_references(rowptr, col, val, B, bias=None, relu=False):
+    """(C*, mag) of act(A.B + bias): the fp64 oracle and oracle(|A|, |B|) (+ |bias|: the bias is one more term of every
+    row, [A 1].[B; bias], and its addition rounds relative to a sum that holds it)"""
+    Cref = oracle_spmm(rowptr, col, val, B).astype(np.float64)
+    mag = oracle_spmm(rowptr, col, np.abs(val), np.abs(B)).astype(np.float64)
+    if bias is not None:
+        Cref = Cref + np.asarray(bias, np.float64)[None, :]
+        mag = mag + np.abs(np.asarray(bias, np.float64))[None, :]
+    if relu:
+        Cref = np.maximum(Cref, 0.0)
+    return Cref, mag
+
+
+_EXACT_PATTERNS = {}
+HUB_MIN = 1000                                         # every pattern below holds a row at least this long, and empty rows
+
+
+def exact_pattern(name):
+    """the sparsity patterns of the exact / element-wise tests -> (rowptr, col, m, n); each has empty rows and one hub row
+    (the *_diag ones keep a stored diagonal in every row, single-entry rows in place of the empty ones: what the
+    detection of u[r]*u[c] values needs)"""
+    if name in _EXACT_PATTERNS:
+        return _EXACT_PATTERNS[name]
+    dup = lambda rp, ci, seed: with_duplicates(rp, ci, np.zeros(len(ci), np.float32), seed=seed)[:2]
+    if name == "unsliced":                               # every unsliced family: 10 % empty rows, a 2000-entry row, duplicates
+        m, n = 2500, 3000
+        rp, ci, _ = random_csr(m, n, 50000, seed=41, empty_rows=0.1, long_rows=[(3, 2000)])
+        rp, ci = dup(rp, ci, 42)
+    elif name in ("group", "group_dup", "group_diag", "group_diag_dup"):   # the 15-bit slice-major stream (slices=3)
+        m = n = 6000
+        rp, ci, _ = sym_norm_graph(n, 260000, seed=3)
+        rp, ci = reshape_rows(rp, ci, n, seed=43, hub=(4321, 2000), keep_diagonal="diag" in name)
+        if name.endswith("_dup"):
+            rp, ci = dup(rp, ci, 44)
+    elif name == "vcsr":                                 # slices wider than the 15-bit stream: the virtual CSR, with values
+        m, n = 3000, 140000
+        rp, ci, _ = random_csr(m, n, 400000, seed=7, empty_rows=0.05, long_rows=[(11, 8000)])
+        rp, ci = dup(rp, ci, 8)
+    elif name == "col16":                                # ... value-free on the 16-bit column stream: >= 48 entries per column
+        m, n = 20000, 70000
+        lens = np.random.default_rng(45).poisson(180, m)
+        lens[np.random.default_rng(46).random(m) < 0.03] = 0
+        lens[[1, m - 1]] = 0
+        lens[777] = 5000
+        rp, ci = random_rows_csr(m, n, lens, seed=47)
+    elif name == "lds":
+        m = n = 3001
+        rp, ci, _ = banded_csr(n, 150, 3, seed=5, hub=(777, 2600))
+        rp, ci = reshape_rows(rp, ci, n, seed=48, spare=(777,))
+        rp, ci = dup(rp, ci, 6)
+    elif name == "mfma":
+        m = n = 2500
+        rp, ci, _ = dense_band_csr(n, 200, 0.6, seed=4, sparse_from=1700)
+        rp, ci = reshape_rows(rp, ci, n, seed=49, hub=(2100, 1500))
+        rp, ci = dup(rp, ci, 7)
+    elif name == "dropin_csr":                           # csr2tile's plain-CSR packing
+        m = n = 3000
+        rp, ci, _ = sym_norm_graph(n, 40000, seed=4)
+        rp, ci = reshape_rows(rp, ci, n, seed=50, hub=(1234, 2000))
+        rp, ci = dup(rp, ci, 1)
+    elif name in ("dropin_group", "dropin_group_diag"):  # ... and its group packing (mean degree >= 128, table > one L2)
+        m = n = 17000
+        rp, ci, _ = sym_norm_graph(n, 1200000, seed=12)
+        rp, ci = reshape_rows(rp, ci, n, seed=51, empty=0.02, hub=(9999, 3000), keep_diagonal=name.endswith("_diag"))
+        rp, ci = dup(rp, ci, 2)
+    else:
+        raise KeyError(name)
+    lens = np.diff(rp)
+    assert lens.max() >= HUB_MIN and lens.max() < 32768 and (lens <= (1 if "diag" in name else 0)).sum() >= 2, name
+    _EXACT_PATTERNS[name] = (rp, ci, m, n)
+    return _EXACT_PATTERNS[name]
+
+
+def exact_operands(pattern, kind, seed=0):
+    """values for a pattern -> dict(rp, ci, va, m, n, u_row, u_col).  kind: "int" (non-zero integers in [-4, 4]: no
+    factors), "pow2" (u[r]*u[c], u = 2^-e; one u when square), "pow2_row" (row-constant 2^-e_r), "wide" (N(0, 0.5) * 2^s_r),
+    "wide_factored" ((0.5 + rand) * 2^a per row and per column)"""
+    rp, ci, m, n = exact_pattern(pattern)
+    u_row = u_col = None
+    if kind == "int":
+        va = int_values(len(ci), seed + 100)
+    elif kind == "wide":
+        va = wide_values(rp, seed + 101)
+    elif kind == "pow2_row":
+        u_row, u_col = pow2_factors(m, seed + 102), np.ones(n, np.float32)
+        va = factored_values(rp, ci, u_row, u_col)
+    else:
+        gen = pow2_factors if kind == "pow2" else wide_factors
+        u_col = gen(n, seed + 103)
+        u_row = u_col if m == n and kind == "pow2" else gen(m, seed + 104)
+        va = factored_values(rp, ci, u_row, u_col)
+    return dict(rp=rp, ci=ci, va=va, m=m, n=n, u_row=u_row, u_col=u_col)
+
+
+# (pattern, kind, widths) of every case test_exact_gpu.py runs: test_exact_cpu.py checks each generator without a GPU
+EXACT_CASES = [("unsliced", "int", (4, 8, 15, 16, 36, 100, 128, 256)),
+               ("group", "int", (16, 32, 40, 41, 64, 100, 128)), ("group_dup", "int", (16, 32, 40, 41, 64, 100, 128)),
+               ("group", "pow2", (16, 32, 40, 41, 64, 100, 128, 136)), ("group_dup", "pow2", (16, 32, 40, 41, 64, 100, 128)),
+               ("group_diag", "pow2", (16, 41, 128)), ("group", "pow2_row", (16, 41, 128)),
+               ("vcsr", "int", (64,)), ("col16", "pow2", (64,)), ("lds", "int", (64, 100)), ("mfma", "int", (36, 64, 128)),
+               ("dropin_csr", "int", (16, 41, 128)), ("dropin_group", "int", (16, 41, 128)),
+               ("dropin_group_diag", "pow2", (16, 41, 128))]
+WIDE_CASES = [("unsliced", "wide", (4, 8, 15, 16, 36, 100, 128, 256)),
+              ("group", "wide", (16, 41, 128)), ("group_dup", "wide_factored", (16, 41, 128)),
+              ("vcsr", "wide", (64,)), ("col16", "wide_factored", (64,)), ("lds", "wide", (64, 100)), ("mfma", "wide", (36, 128))]
