@@ -268,6 +268,48 @@ int gcn_segment_sum_csr_f32(const int32_t* rowptr, int32_t m, int32_t nnz, const
   return launch_segment_sum(rowptr, m, nnz, x, perm, out, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
 }
 
+// k, op / dtype and the sizes first; then what an empty problem still needs; 1 = return *status
+static int aggregate_args(int32_t rows_out, int32_t rows_in, int32_t nnz, int32_t dtype, int32_t k, int* status) {
+  *status = GCN_OK;
+  if (rows_out < 0 || rows_in < 0 || nnz < 0 || k < 1 || (dtype != GCN_DTYPE_F32 && dtype != GCN_DTYPE_BF16)) {
+    *status = GCN_ERR_INVALID_ARG;
+    return 1;
+  }
+  if (k > 16 * 65535) { *status = GCN_ERR_INVALID_ARG; return 1; }       // (column tiles ride in gridDim.y)
+  return rows_out == 0;
+}
+
+int gcn_aggregate_csr(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t n, int32_t nnz, const void* x, int32_t dtype,
+                      int32_t k, int32_t op, void* out, int32_t* arg, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (op != GCN_REDUCE_MAX && op != GCN_REDUCE_MIN) return GCN_ERR_INVALID_ARG;
+  if (aggregate_args(m, n, nnz, dtype, k, &rc)) return rc;
+  if (!out || !arg) return GCN_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t elems = (size_t)m * (size_t)k, esize = dtype == GCN_DTYPE_BF16 ? 2 : 4;
+  if (nnz == 0) {                                       // every row is empty: zeros and -1, as memset nodes
+    if (hipMemsetAsync(out, 0, elems * esize, st) != hipSuccess) return GCN_ERR_HIP;
+    return hipMemsetAsync(arg, 0xff, elems * 4, st) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+  }
+  if (!rowptr || !col || !x || !ws || ws_bytes < aggregate_workspace_bytes(nnz, k)) return GCN_ERR_INVALID_ARG;
+  return launch_aggregate(rowptr, col, m, nnz, x, dtype == GCN_DTYPE_BF16, k, op == GCN_REDUCE_MAX ? kAggMax : kAggMin, out, arg, ws,
+                          st) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_aggregate_backward_csr(const int32_t* trowptr, const int32_t* trow, const int32_t* tperm, int32_t n, int32_t m, int32_t nnz,
+                               const void* g, int32_t dtype, const int32_t* arg, int32_t k, void* gx, void* ws, size_t ws_bytes,
+                               void* stream) {
+  int rc;
+  if (aggregate_args(n, m, nnz, dtype, k, &rc)) return rc;
+  if (!gx) return GCN_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (nnz == 0)
+    return hipMemsetAsync(gx, 0, (size_t)n * (size_t)k * (dtype == GCN_DTYPE_BF16 ? 2 : 4), st) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+  if (!trowptr || !trow || !tperm || !g || !arg || !ws || ws_bytes < aggregate_workspace_bytes(nnz, k)) return GCN_ERR_INVALID_ARG;
+  return launch_aggregate_backward(trowptr, trow, tperm, n, nnz, g, dtype == GCN_DTYPE_BF16, arg, k, gx, ws, st) == hipSuccess
+             ? GCN_OK : GCN_ERR_HIP;
+}
+
 int gcn_spmm_plan_sddmm_kernel(const gcn_spmm_plan_t* p, int32_t k, char* buf, int32_t buflen) {
   if (!p || k <= 0 || !buf || buflen <= 0) return GCN_ERR_INVALID_ARG;
   snprintf(buf, (size_t)buflen, "gcn::sddmm_kernel<%s, %s>", sddmm_sliced(p, k) ? "true" : "false",

@@ -170,6 +170,18 @@ hipError_t launch_gat_edge_softmax_backward(const int* rowptr, const int* col, i
 hipError_t launch_segment_sum(const int* rowptr, int m, int nnz, const float* x, const int* perm, float* out, void* ws,
                               hipStream_t st);
 
+// aggregate.hip — element-wise max / min over each CSR row's stored entries with the winning entry index, and its backward
+// as a walk of the transposed pattern (plan-free, capturable, no atomics: see the file's header).  x / out / g / gx are
+// fp32 or bf16 (bf16 != 0) row-major with row stride k.  ws: aggregate_workspace_bytes(nnz, k) bytes of device memory — a
+// flag and one (value, entry) pair per (chunk of kAggChunk entries, long row, column) — owned by the call while it runs.
+constexpr int kAggChunk = 4096;
+constexpr int kAggMax = 0, kAggMin = 1;                // GCN_REDUCE_MAX / GCN_REDUCE_MIN
+size_t aggregate_workspace_bytes(int nnz, int k);
+hipError_t launch_aggregate(const int* rowptr, const int* col, int m, int nnz, const void* x, int bf16, int k, int op, void* out,
+                            int* arg, void* ws, hipStream_t st);
+hipError_t launch_aggregate_backward(const int* trowptr, const int* trow, const int* tperm, int n, int nnz, const void* g, int bf16,
+                                     const int* arg, int k, void* gx, void* ws, hipStream_t st);
+
 // slicing.hip — mutable values.  vsrc[s*m + r] = CSR position of the first entry of row r in slice s (from the sliced
 // row pointer; column-sorted rows make every (row, slice) part one contiguous run of the CSR row).
 hipError_t build_value_map(const int* rowptr, const int* vrowptr, int m, int S, int* vsrc, hipStream_t st);

@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from torch.nn.parameter import Parameter
 
 from . import preprocess, reorder, timers
+from .aggregate import aggregate
 from .attention import gat_edge_softmax
 from .spmm import CsrAdjacency, _SpmmFunction, dropout_rows, gather_rows, spmm
 
@@ -182,6 +183,59 @@ class GraphAttention(nn.Module):
     def __repr__(self):
         return (f"GraphAttention ({self.in_features} -> {self.out_features}, heads={self.heads}, "
                 f"{'concat' if self.concat else 'mean'})")
+
+
+class SAGEConv(nn.Module):
+    """GraphSAGE layer (Hamilton et al. 2017; PyG's ``SAGEConv``) on the native aggregators:
+
+        out = aggregate(adj, x, aggr) · weight_neigh  (+ x · weight_root)  (+ bias)
+
+    ``aggr``: "mean", "max", "min" or "sum" over the stored entries of each row of ``adj`` (pattern only: the values of
+    ``adj`` are ignored, see ``gcn_amd.aggregate``).  Sum and mean commute with the linear map, so they aggregate at the
+    narrower of ``in_features`` and ``out_features`` — aggregate(x · W) when the layer narrows, the rule of
+    ``GCN(layer_order="auto")``; max and min always aggregate x itself.  ``root_weight=True`` adds the vertex's own
+    features through a second matrix and needs a square adjacency.
+
+    Parameters: ``weight_neigh`` and ``weight_root`` [in_features, out_features] and ``bias`` [out_features], uniform in
+    +-1/sqrt(out_features) like the GCN layers.  Under a bf16 autocast region the aggregated operand is bf16 like the
+    dense products around it; max and min run on bf16 directly (a selection: exact)."""
+
+    def __init__(self, in_features, out_features, aggr="mean", root_weight=True, with_bias=True):
+        super().__init__()
+        if aggr not in ("mean", "max", "min", "sum"):
+            raise ValueError(f"aggr must be 'mean', 'max', 'min' or 'sum', not {aggr!r}")
+        self.in_features, self.out_features, self.aggr = int(in_features), int(out_features), aggr
+        self.weight_neigh = Parameter(torch.empty(self.in_features, self.out_features))
+        if root_weight:
+            self.weight_root = Parameter(torch.empty(self.in_features, self.out_features))
+        else:
+            self.register_parameter("weight_root", None)
+        if with_bias:
+            self.bias = Parameter(torch.empty(self.out_features))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        stdv = 1.0 / math.sqrt(self.out_features)
+        for p in (self.weight_neigh, self.weight_root, self.bias):
+            if p is not None:
+                p.data.uniform_(-stdv, stdv)
+
+    def forward(self, input, adj):
+        if input.dim() != 2 or input.shape[0] != adj.n or (self.weight_root is not None and adj.m != adj.n):
+            raise ValueError(f"SAGEConv: adjacency {adj.m}x{adj.n} (square with root_weight), input {tuple(input.shape)}")
+        if self.aggr in ("sum", "mean") and self.out_features < self.in_features:
+            out = aggregate(adj, _spmm_operand(torch.mm(input, self.weight_neigh)), self.aggr)
+        else:
+            out = torch.mm(aggregate(adj, _spmm_operand(input), self.aggr), self.weight_neigh)
+        if self.weight_root is not None:
+            out = out + torch.mm(input, self.weight_root)
+        return out + self.bias if self.bias is not None else out
+
+    def __repr__(self):
+        return (f"SAGEConv ({self.in_features} -> {self.out_features}, aggr={self.aggr}"
+                f"{'' if self.weight_root is not None else ', no root weight'})")
 
 
 class GCN(nn.Module):

@@ -384,18 +384,25 @@ class CsrAdjacency:
         t.update_values(values.detach().index_select(0, self._tperm))
         return t
 
+    def _transposed_pattern(self):
+        """(rowptr int32 [n+1], row of each entry int32 [nnz], perm int64 [nnz]) of the transposed pattern, built with
+        torch ops: entry t of the transpose is entry perm[t] of this adjacency; duplicates stay separate entries, in
+        their CSR order (a stable sort by (column, row))."""
+        dev = self.device
+        rp = self.rowptr.long()
+        rows = torch.repeat_interleave(torch.arange(self.m, device=dev), rp[1:] - rp[:-1], output_size=self.nnz)
+        c = self.col.long()
+        perm = torch.argsort(c * max(self.m, 1) + rows, stable=True)
+        trp = torch.zeros(self.n + 1, dtype=torch.int64, device=dev)
+        trp[1:] = torch.cumsum(torch.bincount(c, minlength=self.n), 0)
+        return trp.to(torch.int32), rows[perm].to(torch.int32), perm
+
     def _mutable_transpose(self):
         """Âᵀ of a mutable adjacency: itself mutable, never Â (a symmetric pattern does not make learned values
         symmetric); duplicates stay separate entries, so its values are exactly self.val[_tperm]."""
         if self._transpose is None:
-            dev = self.device
-            rp = self.rowptr.long()
-            rows = torch.repeat_interleave(torch.arange(self.m, device=dev), rp[1:] - rp[:-1], output_size=self.nnz)
-            c = self.col.long()
-            perm = torch.argsort(c * max(self.m, 1) + rows, stable=True)
-            trp = torch.zeros(self.n + 1, dtype=torch.int64, device=dev)
-            trp[1:] = torch.cumsum(torch.bincount(c, minlength=self.n), 0)
-            t = CsrAdjacency(trp.to(torch.int32), rows[perm].to(torch.int32), self.val[perm], (self.n, self.m),
+            trp, trow, perm = self._transposed_pattern()
+            t = CsrAdjacency(trp, trow, self.val[perm], (self.n, self.m),
                              symmetric=False, chunk_nnz=self.chunk_nnz, mutable_values=True)
             self._tperm = perm
             self._transpose = t

@@ -269,6 +269,36 @@ int gcn_gat_edge_softmax_backward_csr_f32(const int32_t* rowptr_dev, const int32
 int gcn_segment_sum_csr_f32(const int32_t* rowptr_dev, int32_t m, int32_t nnz, const float* x, const int32_t* perm_dev,
                             float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* Neighbourhood max / min ("pooling" aggregation: GraphSAGE, PyG aggr="max", DGL copy_u_max) over the stored entries of
+ * each row of a CSR pattern, and its backward.  Plan-free like the edge softmax family: the caller's CSR, only memset nodes
+ * and kernels (no allocation, no host synchronisation, no host read of device data: legal inside a stream capture), no
+ * atomics, the same bits at every call.  The stored VALUES of the matrix are not used; every stored entry is a candidate
+ * of its own, duplicated (row, column) pairs included.  Row lengths may be anything: a row of more than 4096 entries is
+ * spread over the chip, empty rows cost a row-pointer read and their stores.
+ *   out[r, j] = max (min) over the entries e of row r of x[col[e], j],   arg[r, j] = that e (its index into col_dev)
+ * x [n x k], out [m x k] row-major, both fp32 (GCN_DTYPE_F32) or both bf16 (GCN_DTYPE_BF16); arg [m x k] int32.
+ * An empty row gets out = 0, arg = -1.  Equal values (-0.0 equals +0.0): the lowest entry index wins and its bits are
+ * stored.  A NaN beats every number and the first NaN entry of the row is the arg.  +-inf are ordinary values.  The result
+ * is exact (a selection: nothing is rounded).  Any k >= 1; 16-byte loads and stores are used when x, out and arg are
+ * 16-byte aligned and k is a multiple of 4 (bf16: 8), element accesses otherwise.
+ * ws: device scratch of at least GCN_AGGREGATE_WS_BYTES(nnz, k) bytes, 16-byte aligned, owned by the call until it has run
+ * (calls on different streams need different ones).  Null pointers, negative sizes, k < 1, an unknown op or dtype or a
+ * short workspace: GCN_ERR_INVALID_ARG.  m == 0: GCN_OK, nothing written; nnz == 0: out is zeroed and arg set to -1. */
+#define GCN_AGGREGATE_WS_BYTES(nnz, k) (16 + 16 * (size_t)(k) * (((size_t)(nnz) + 4095) / 4096))
+#define GCN_REDUCE_MAX 0
+#define GCN_REDUCE_MIN 1
+int gcn_aggregate_csr(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t n, int32_t nnz, const void* x,
+                      int32_t dtype, int32_t k, int32_t op, void* out, int32_t* arg, void* ws, size_t ws_bytes, void* stream);
+/* Its backward, as a walk of the TRANSPOSED pattern (no atomics, one writer per element): trowptr_dev [n + 1], trow_dev
+ * [nnz] (the row of each entry of the transpose, i.e. the forward's row) and tperm_dev [nnz] (the entry's index in the
+ * forward's CSR order) describe the transpose of the m x n pattern, duplicates kept as separate entries.
+ *   gx[c, j] = sum of g[trow[t], j] over the entries t of transposed row c with arg[trow[t], j] == tperm[t]
+ * g [m x k] and gx [n x k] of `dtype`, arg as the forward wrote it.  Sums are fp32 in a fixed order (bf16: rounded once at
+ * the store).  n == 0: nothing written; nnz == 0: gx is zeroed.  Same workspace rule (the forward's workspace will do). */
+int gcn_aggregate_backward_csr(const int32_t* trowptr_dev, const int32_t* trow_dev, const int32_t* tperm_dev, int32_t n,
+                               int32_t m, int32_t nnz, const void* g, int32_t dtype, const int32_t* arg, int32_t k, void* gx,
+                               void* ws, size_t ws_bytes, void* stream);
+
 /* LDS-staged row panels (optional): for matrices whose non-zeros sit near the diagonal (community
  * graphs after Rabbit / RCM / Gorder renumbering) a workgroup stages the feature rows of its panel's
  * column window (512 rows x 64 columns = 128 KiB of LDS) once and sums the in-window non-zeros
