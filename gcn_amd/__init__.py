@@ -11,7 +11,8 @@ from ._lib import GcnAmdError, LIB_PATH, DROPIN_DIR, load as load_library  # noq
 from .spmm import CsrAdjacency, spmm, gather_rows, dropout_rows, install, uninstall  # noqa: F401
 from .attention import edge_softmax, gat_edge_softmax, segment_sum  # noqa: F401
 from .aggregate import aggregate  # noqa: F401
+from .sampling import Block, NeighborLoader, sample_blocks, sample_neighbors  # noqa: F401
 from . import reorder, dropin  # noqa: F401
-from .layers import GCN, GraphAttention, GraphConvolution, GraphConvolution2, SAGEConv  # noqa: F401
+from .layers import GCN, GraphAttention, GraphConvolution, GraphConvolution2, GraphSAGE, SAGEConv  # noqa: F401
 
 __version__ = "0.3.0"

@@ -20,6 +20,8 @@ ERR_NOT_FACTORED = 6         # GCN_ERR_NOT_FACTORED
 ERR_INTERNAL = 7             # GCN_ERR_INTERNAL (a consistency guard tripped: gcn_order_rabbit_device)
 DTYPE_F32, DTYPE_BF16 = 0, 1 # GCN_DTYPE_F32 / GCN_DTYPE_BF16 (gcn_spmm_csr_bf16_epilogue)
 REDUCE_MAX, REDUCE_MIN = 0, 1 # GCN_REDUCE_MAX / GCN_REDUCE_MIN (gcn_aggregate_csr)
+SAMPLE_LONG_ROW = 2048       # GCN_SAMPLE_LONG_ROW: longer rows get a workgroup, not a wave (gcn_sample_neighbors_csr)
+SAMPLE_WS_BYTES = 16         # GCN_SAMPLE_WS_BYTES
 
 
 _c_i32 = ctypes.c_int32
@@ -78,7 +80,9 @@ SIGNATURES = {
                                          ctypes.c_size_t, _c_p]),
     "gcn_aggregate_backward_csr": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_p,
                                                   ctypes.c_size_t, _c_p]),
-    "gcn_spmm_plan_sddmm_kernel": (ctypes.c_int, [_c_p, _c_i32, ctypes.c_char_p, _c_i32]),
+    "gcn_sample_neighbors_csr": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_i32, ctypes.c_uint64, ctypes.c_uint64,
+                                                _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_spmm_plan_sddmm_kernel":(ctypes.c_int, [_c_p, _c_i32, ctypes.c_char_p, _c_i32]),
     "gcn_spmm_plan_enable_panels": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_p]),
     "gcn_spmm_plan_panel_rows": (_c_i32, [_c_p]),
     "gcn_spmm_plan_panel_coverage": (ctypes.c_double, [_c_p]),

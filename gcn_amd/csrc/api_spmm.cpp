@@ -310,6 +310,20 @@ int gcn_aggregate_backward_csr(const int32_t* trowptr, const int32_t* trow, cons
              ? GCN_OK : GCN_ERR_HIP;
 }
 
+int gcn_sample_neighbors_csr(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t nnz, const int32_t* seeds, int32_t n_seeds,
+                             int32_t fanout, uint64_t seed, uint64_t offset, const int32_t* out_rowptr, int32_t* out_col,
+                             int32_t* out_eid, void* ws, size_t ws_bytes, void* stream) {
+  if (m < 0 || nnz < 0 || n_seeds < 0 || fanout == 0) return GCN_ERR_INVALID_ARG;
+  if (n_seeds == 0) return GCN_OK;
+  if (!seeds || !out_rowptr) return GCN_ERR_INVALID_ARG;
+  if (m == 0 || nnz == 0) return GCN_OK;                // (no seed is in range / every row is empty: nothing to write)
+  if (!rowptr || !col || !out_col || !out_eid || !ws || ws_bytes < kSampleWsBytes) return GCN_ERR_INVALID_ARG;
+  return launch_sample_neighbors(rowptr, col, m, nnz, seeds, n_seeds, fanout, seed, offset, out_rowptr, out_col, out_eid, ws,
+                                 (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+static_assert(kSampleLongRow == GCN_SAMPLE_LONG_ROW && kSampleWsBytes == GCN_SAMPLE_WS_BYTES, "include/gcn_spmm.h");
+
 int gcn_spmm_plan_sddmm_kernel(const gcn_spmm_plan_t* p, int32_t k, char* buf, int32_t buflen) {
   if (!p || k <= 0 || !buf || buflen <= 0) return GCN_ERR_INVALID_ARG;
   snprintf(buf, (size_t)buflen, "gcn::sddmm_kernel<%s, %s>", sddmm_sliced(p, k) ? "true" : "false",

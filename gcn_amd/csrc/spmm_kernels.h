@@ -182,6 +182,16 @@ hipError_t launch_aggregate(const int* rowptr, const int* col, int m, int nnz, c
 hipError_t launch_aggregate_backward(const int* trowptr, const int* trow, const int* tperm, int n, int nnz, const void* g, int bf16,
                                      const int* arg, int k, void* gx, void* ws, hipStream_t st);
 
+// sample.hip — uniform neighbour sampling without replacement from the rows of seeds[n_seeds], a pure function of (seed,
+// offset, entry index) (plan-free, no global atomics: see the file's header and include/gcn_spmm.h).  fanout < 0: every entry.
+// out_rowptr [n_seeds + 1] is an INPUT (row i holds min(row length, fanout) entries); ws: kSampleWsBytes of device memory (a
+// flag).  A row of more than kSampleLongRow entries gets a 256-thread workgroup instead of a wave.
+constexpr int kSampleLongRow = 2048;
+constexpr size_t kSampleWsBytes = 16;
+hipError_t launch_sample_neighbors(const int* rowptr, const int* col, int m, int nnz, const int* seeds, int n_seeds, int fanout,
+                                   unsigned long long seed, unsigned long long offset, const int* out_rowptr, int* out_col,
+                                   int* out_eid, void* ws, hipStream_t st);
+
 // slicing.hip — mutable values.  vsrc[s*m + r] = CSR position of the first entry of row r in slice s (from the sliced
 // row pointer; column-sorted rows make every (row, slice) part one contiguous run of the CSR row).
 hipError_t build_value_map(const int* rowptr, const int* vrowptr, int m, int S, int* vsrc, hipStream_t st);

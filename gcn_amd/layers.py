@@ -196,6 +196,9 @@ class SAGEConv(nn.Module):
     ``GCN(layer_order="auto")``; max and min always aggregate x itself.  ``root_weight=True`` adds the vertex's own
     features through a second matrix and needs a square adjacency.
 
+    ``forward((x_src, x_dst), adj)`` takes a bipartite ``adj`` (a sampled block, ``gcn_amd.sample_blocks``): ``x_src`` has
+    ``adj.n`` rows and feeds the neighbour term, ``x_dst`` has ``adj.m`` rows and feeds the root term.
+
     Parameters: ``weight_neigh`` and ``weight_root`` [in_features, out_features] and ``bias`` [out_features], uniform in
     +-1/sqrt(out_features) like the GCN layers.  Under a bf16 autocast region the aggregated operand is bf16 like the
     dense products around it; max and min run on bf16 directly (a selection: exact)."""
@@ -223,19 +226,76 @@ class SAGEConv(nn.Module):
                 p.data.uniform_(-stdv, stdv)
 
     def forward(self, input, adj):
-        if input.dim() != 2 or input.shape[0] != adj.n or (self.weight_root is not None and adj.m != adj.n):
-            raise ValueError(f"SAGEConv: adjacency {adj.m}x{adj.n} (square with root_weight), input {tuple(input.shape)}")
+        if isinstance(input, (tuple, list)):               # a bipartite block: (x_src [adj.n rows], x_dst [adj.m rows])
+            if len(input) != 2:
+                raise ValueError("SAGEConv: a bipartite input is the pair (x_src, x_dst)")
+            input, root = input
+            if input.dim() != 2 or input.shape[0] != adj.n or root.dim() != 2 or root.shape[0] != adj.m:
+                raise ValueError(f"SAGEConv: adjacency {adj.m}x{adj.n}, input ({tuple(input.shape)}, {tuple(root.shape)})")
+        else:
+            if input.dim() != 2 or input.shape[0] != adj.n or (self.weight_root is not None and adj.m != adj.n):
+                raise ValueError(f"SAGEConv: adjacency {adj.m}x{adj.n} (square with root_weight), input {tuple(input.shape)}")
+            root = input
         if self.aggr in ("sum", "mean") and self.out_features < self.in_features:
             out = aggregate(adj, _spmm_operand(torch.mm(input, self.weight_neigh)), self.aggr)
         else:
             out = torch.mm(aggregate(adj, _spmm_operand(input), self.aggr), self.weight_neigh)
         if self.weight_root is not None:
-            out = out + torch.mm(input, self.weight_root)
+            out = out + torch.mm(root, self.weight_root)
         return out + self.bias if self.bias is not None else out
 
     def __repr__(self):
         return (f"SAGEConv ({self.in_features} -> {self.out_features}, aggr={self.aggr}"
                 f"{'' if self.weight_root is not None else ', no root weight'})")
+
+
+class GraphSAGE(nn.Module):
+    """A stack of ``num_layers`` SAGEConv layers with ReLU and dropout between them (Hamilton et al. 2017), for the whole
+    graph or for sampled mini-batches:
+
+        logits = model(x, adj)                         # adj: one CsrAdjacency, used by every layer
+        blocks, input_ids = gcn_amd.sample_blocks(adj, seeds, fanouts)
+        logits = model(x[input_ids], blocks)           # one row per seed; len(blocks) == num_layers
+
+    With blocks, layer i runs on ``(h, h[:blocks[i].num_dst])``: a block's first ``num_dst`` src vertices are its rows.
+    The output is the last layer's (no softmax).  There is no ``fit``: the training loop stays with the caller."""
+
+    def __init__(self, in_features, hidden, out_features, num_layers=2, aggr="mean", dropout=0.5, root_weight=True):
+        super().__init__()
+        if isinstance(num_layers, bool) or not isinstance(num_layers, int) or num_layers < 1:
+            raise ValueError(f"GraphSAGE: num_layers must be an int >= 1, not {num_layers!r}")
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f"GraphSAGE: dropout must lie in [0, 1), not {dropout!r}")
+        widths = [int(in_features)] + [int(hidden)] * (num_layers - 1) + [int(out_features)]
+        self.layers = nn.ModuleList(SAGEConv(widths[i], widths[i + 1], aggr=aggr, root_weight=root_weight)
+                                    for i in range(num_layers))
+        self.dropout = float(dropout)
+
+    def reset_parameters(self):
+        for layer in self.layers:
+            layer.reset_parameters()
+
+    def forward(self, x, adjs):
+        blocks = None
+        if not isinstance(adjs, CsrAdjacency):
+            blocks = list(adjs)
+            if len(blocks) != len(self.layers):
+                raise ValueError(f"GraphSAGE: {len(self.layers)} layers need {len(self.layers)} blocks, not {len(blocks)}")
+        h = x
+        for i, layer in enumerate(self.layers):
+            if blocks is None:
+                h = layer(h, adjs)
+            else:
+                h = layer((h, h[:blocks[i].num_dst]), blocks[i].adj)
+            if i + 1 < len(self.layers):
+                h = F.dropout(F.relu(h), self.dropout, training=self.training)
+        return h
+
+    def __repr__(self):
+        first, last = self.layers[0], self.layers[-1]
+        hidden = f" -> {first.out_features}" if len(self.layers) > 1 else ""
+        return (f"GraphSAGE ({first.in_features}{hidden} -> {last.out_features}, layers={len(self.layers)}, "
+                f"aggr={first.aggr}, dropout={self.dropout})")
 
 
 class GCN(nn.Module):

@@ -299,6 +299,34 @@ int gcn_aggregate_backward_csr(const int32_t* trowptr_dev, const int32_t* trow_d
                                int32_t m, int32_t nnz, const void* g, int32_t dtype, const int32_t* arg, int32_t k, void* gx,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* Uniform neighbour sampling without replacement from the rows of a CSR matrix (GraphSAGE's mini-batch sampler).  Plan-free
+ * like the aggregation family: the caller's CSR, one memset node and kernels, no allocation, no host read of device data, no
+ * global atomics; every output element has one writer, so a call gives the same bits every time.  The stored values are
+ * not used.  The contract, exact and meant to be re-implemented (tests/sampling_ref.py is the numpy twin):
+ *   Output row i belongs to the vertex v = seeds_dev[i] (seeds in any order, repeats allowed).  Its entries are
+ *   e in [rowptr[v], rowptr[v + 1]); d is their number, f = fanout.
+ *   Selection.  fanout < 0 or d <= f: all d entries.  Otherwise key(e) = word (e & 3) of Philox4x32-10 with counter
+ *   (lo32(e >> 2), hi32(e >> 2), lo32(offset), hi32(offset)) and key (lo32(seed), hi32(seed)) — the word and counter
+ *   convention of the dropout mask above with the entry index e (the index into col_dev) in the place of the element
+ *   index — and the f entries with the smallest (key(e), e) in lexicographic order are selected: among equal keys the lower
+ *   entry index wins.
+ *   Order.  The selected entries of a row are written in ascending e (the CSR's own order: a column-sorted row stays
+ *   sorted): out_col[out_rowptr[i] + t] = col[e_t] and out_eid[out_rowptr[i] + t] = e_t for t = 0 .. min(d, f) - 1.
+ * Consequences: the keys are i.i.d. words, so the f smallest are a uniform subset — the sample is uniform without
+ * replacement; the neighbours drawn for a vertex depend on (seed, offset) only, not on the batch it is in or on its place
+ * there — so two hops of one batch, and successive batches, must use different offsets.
+ * out_rowptr_dev [n_seeds + 1] is an INPUT: out_rowptr[i + 1] - out_rowptr[i] = min(d_i, f) (d_i for fanout < 0), computed
+ * by the caller, who needs the total to size out_col / out_eid anyway.  A seed outside [0, m), or a row whose out_rowptr
+ * length is not that number, writes nothing.  Every row length from 0 to nnz works and the host never reads one: a row of
+ * at most GCN_SAMPLE_LONG_ROW entries is taken by one wave, a longer one by a 256-thread workgroup.
+ * ws: GCN_SAMPLE_WS_BYTES of device scratch, owned by the call until it has run.  fanout == 0, negative sizes, a null
+ * pointer or a short workspace: GCN_ERR_INVALID_ARG; n_seeds == 0, m == 0 or nnz == 0: GCN_OK, nothing written. */
+#define GCN_SAMPLE_WS_BYTES 16
+#define GCN_SAMPLE_LONG_ROW 2048
+int gcn_sample_neighbors_csr(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz, const int32_t* seeds_dev,
+                             int32_t n_seeds, int32_t fanout, uint64_t seed, uint64_t offset, const int32_t* out_rowptr_dev,
+                             int32_t* out_col_dev, int32_t* out_eid_dev, void* ws, size_t ws_bytes, void* stream);
+
 /* LDS-staged row panels (optional): for matrices whose non-zeros sit near the diagonal (community
  * graphs after Rabbit / RCM / Gorder renumbering) a workgroup stages the feature rows of its panel's
  * column window (512 rows x 64 columns = 128 KiB of LDS) once and sums the in-window non-zeros
