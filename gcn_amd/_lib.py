@@ -22,6 +22,7 @@ DTYPE_F32, DTYPE_BF16 = 0, 1 # GCN_DTYPE_F32 / GCN_DTYPE_BF16 (gcn_spmm_csr_bf16
 REDUCE_MAX, REDUCE_MIN = 0, 1 # GCN_REDUCE_MAX / GCN_REDUCE_MIN (gcn_aggregate_csr)
 SAMPLE_LONG_ROW = 2048       # GCN_SAMPLE_LONG_ROW: longer rows get a workgroup, not a wave (gcn_sample_neighbors_csr)
 SAMPLE_WS_BYTES = 16         # GCN_SAMPLE_WS_BYTES
+SUBGRAPH_WS_BYTES = 16       # GCN_SUBGRAPH_WS_BYTES (gcn_induced_subgraph_count_csr / _fill_csr)
 
 
 _c_i32 = ctypes.c_int32
@@ -82,6 +83,12 @@ SIGNATURES = {
                                                   ctypes.c_size_t, _c_p]),
     "gcn_sample_neighbors_csr": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_i32, ctypes.c_uint64, ctypes.c_uint64,
                                                 _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_induced_subgraph_count_csr": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_p, _c_p, ctypes.c_size_t,
+                                                      _c_p]),
+    "gcn_induced_subgraph_fill_csr": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                                     ctypes.c_size_t, _c_p]),
+    "gcn_random_walk_csr": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_i32, ctypes.c_uint64, ctypes.c_uint64, _c_p,
+                                           _c_p]),
     "gcn_spmm_plan_sddmm_kernel":(ctypes.c_int, [_c_p, _c_i32, ctypes.c_char_p, _c_i32]),
     "gcn_spmm_plan_enable_panels": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_p]),
     "gcn_spmm_plan_panel_rows": (_c_i32, [_c_p]),

@@ -324,6 +324,50 @@ int gcn_sample_neighbors_csr(const int32_t* rowptr, const int32_t* col, int32_t 
 
 static_assert(kSampleLongRow == GCN_SAMPLE_LONG_ROW && kSampleWsBytes == GCN_SAMPLE_WS_BYTES, "include/gcn_spmm.h");
 
+// sizes first; then what an empty problem still needs; 1 = return *status
+static int subgraph_args(int32_t m, int32_t nnz, int32_t n_nodes, const int32_t* nodes, int* status) {
+  *status = GCN_OK;
+  if (m < 0 || nnz < 0 || n_nodes < 0) { *status = GCN_ERR_INVALID_ARG; return 1; }
+  if (n_nodes == 0) return 1;
+  if (!nodes) { *status = GCN_ERR_INVALID_ARG; return 1; }
+  return 0;
+}
+
+int gcn_induced_subgraph_count_csr(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t nnz, const int32_t* nodes,
+                                   int32_t n_nodes, const int32_t* vmap, int32_t* out_len, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  int rc;
+  if (subgraph_args(m, nnz, n_nodes, nodes, &rc)) return rc;
+  if (!out_len) return GCN_ERR_INVALID_ARG;
+  if (m == 0 || nnz == 0) return GCN_OK;                // (no node is in range / every row is empty: nothing to write)
+  if (!rowptr || !col || !vmap || !ws || ws_bytes < kSubgraphWsBytes) return GCN_ERR_INVALID_ARG;
+  return launch_induced_subgraph_count(rowptr, col, m, nnz, nodes, n_nodes, vmap, out_len, ws, (hipStream_t)stream) == hipSuccess
+             ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_induced_subgraph_fill_csr(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t nnz, const int32_t* nodes,
+                                  int32_t n_nodes, const int32_t* vmap, const int32_t* out_rowptr, int32_t* out_col,
+                                  int32_t* out_eid, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (subgraph_args(m, nnz, n_nodes, nodes, &rc)) return rc;
+  if (!out_rowptr) return GCN_ERR_INVALID_ARG;
+  if (m == 0 || nnz == 0) return GCN_OK;
+  if (!rowptr || !col || !vmap || !out_col || !out_eid || !ws || ws_bytes < kSubgraphWsBytes) return GCN_ERR_INVALID_ARG;
+  return launch_induced_subgraph_fill(rowptr, col, m, nnz, nodes, n_nodes, vmap, out_rowptr, out_col, out_eid, ws,
+                                      (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+static_assert(kSubgraphWsBytes == GCN_SUBGRAPH_WS_BYTES, "include/gcn_spmm.h");
+
+int gcn_random_walk_csr(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t nnz, const int32_t* starts, int32_t n_walks,
+                        int32_t length, uint64_t seed, uint64_t offset, int32_t* out_walks, void* stream) {
+  if (m < 0 || nnz < 0 || n_walks < 0 || length < 0) return GCN_ERR_INVALID_ARG;
+  if (n_walks == 0) return GCN_OK;
+  if (!starts || !out_walks || (m > 0 && !rowptr) || (m > 0 && nnz > 0 && !col)) return GCN_ERR_INVALID_ARG;
+  return launch_random_walk(rowptr, col, m, nnz, starts, n_walks, length, seed, offset, out_walks, (hipStream_t)stream) == hipSuccess
+             ? GCN_OK : GCN_ERR_HIP;
+}
+
 int gcn_spmm_plan_sddmm_kernel(const gcn_spmm_plan_t* p, int32_t k, char* buf, int32_t buflen) {
   if (!p || k <= 0 || !buf || buflen <= 0) return GCN_ERR_INVALID_ARG;
   snprintf(buf, (size_t)buflen, "gcn::sddmm_kernel<%s, %s>", sddmm_sliced(p, k) ? "true" : "false",

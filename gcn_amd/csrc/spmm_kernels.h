@@ -192,6 +192,19 @@ hipError_t launch_sample_neighbors(const int* rowptr, const int* col, int m, int
                                    unsigned long long seed, unsigned long long offset, const int* out_rowptr, int* out_col,
                                    int* out_eid, void* ws, hipStream_t st);
 
+// subgraph.hip — the vertex-induced subgraph of nodes[n_nodes] (count, the caller's scan, fill) and uniform random walks
+// (plan-free, no global atomics: see the file's header and include/gcn_spmm.h).  vmap [n]: a vertex's position in nodes or
+// -1; out_rowptr [n_nodes + 1] is an INPUT of the fill; ws: kSubgraphWsBytes of device memory (a flag).  Rows of more than
+// kSampleLongRow entries get a 256-thread workgroup instead of a wave.  out_walks [length + 1][n_walks].
+constexpr size_t kSubgraphWsBytes = 16;
+hipError_t launch_induced_subgraph_count(const int* rowptr, const int* col, int m, int nnz, const int* nodes, int n_nodes,
+                                         const int* vmap, int* out_len, void* ws, hipStream_t st);
+hipError_t launch_induced_subgraph_fill(const int* rowptr, const int* col, int m, int nnz, const int* nodes, int n_nodes,
+                                        const int* vmap, const int* out_rowptr, int* out_col, int* out_eid, void* ws,
+                                        hipStream_t st);
+hipError_t launch_random_walk(const int* rowptr, const int* col, int m, int nnz, const int* starts, int n_walks, int length,
+                              unsigned long long seed, unsigned long long offset, int* out_walks, hipStream_t st);
+
 // slicing.hip — mutable values.  vsrc[s*m + r] = CSR position of the first entry of row r in slice s (from the sliced
 // row pointer; column-sorted rows make every (row, slice) part one contiguous run of the CSR row).
 hipError_t build_value_map(const int* rowptr, const int* vrowptr, int m, int S, int* vsrc, hipStream_t st);

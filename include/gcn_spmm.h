@@ -327,6 +327,63 @@ int gcn_sample_neighbors_csr(const int32_t* rowptr_dev, const int32_t* col_dev, 
                              int32_t n_seeds, int32_t fanout, uint64_t seed, uint64_t offset, const int32_t* out_rowptr_dev,
                              int32_t* out_col_dev, int32_t* out_eid_dev, void* ws, size_t ws_bytes, void* stream);
 
+/* The vertex-induced subgraph of a CSR matrix (the mini-batch of Cluster-GCN and of GraphSAINT's samplers: the square
+ * adjacency over a vertex set that a GCN layer needs), as two calls with the caller's prefix sum between them.  Plan-free
+ * like the sampling call and under the same rules: the caller's CSR, one memset node and kernels, no allocation, no host
+ * read of device data, no global atomics; every output element has one writer, so a call gives the same bits every time.
+ * The stored values are not used.  Every access is a 4-byte one: no pointer needs more than 4-byte alignment.  The
+ * contract, exact and meant to be re-implemented (tests/subgraph_ref.py is the numpy twin):
+ *   nodes_dev [n_nodes]: vertex ids in any order (row ids in [0, m)).  vmap_dev [n], n the number of columns: vmap[c] is
+ *   the position of column c in the vertex set, or -1 (any negative number) when c is not in it.  The caller fills it
+ *   before the calls and clears it afterwards; the calls only read it.  Every col[e] must lie in [0, n), as for the SpMM.
+ *   Output row i belongs to the vertex v = nodes_dev[i].  Its entries are the e in [rowptr[v], rowptr[v + 1]) with
+ *   vmap[col[e]] >= 0, e_0 < e_1 < ... (the parent's entry order: a column-sorted row stays sorted by parent column).
+ *   Count:  out_len_dev[i] = the number of those entries.
+ *   Fill:   out_col_dev[out_rowptr[i] + t] = vmap[col[e_t]] and out_eid_dev[out_rowptr[i] + t] = e_t.
+ * out_rowptr_dev [n_nodes + 1] is an INPUT of the fill: the exclusive prefix sum of out_len, computed by the caller, who
+ * needs its last element to size out_col / out_eid anyway — which is why there are two calls.
+ * These write nothing for their row: a node outside [0, m), a row pointer outside [0, nnz], and in the fill a row whose
+ * out_rowptr length differs from its count (or whose out_rowptr[i] is negative).  Every row length from 0 to nnz works and
+ * the host never reads one: a row of at most GCN_SAMPLE_LONG_ROW entries is taken by one wave, a longer one by a
+ * 256-thread workgroup.
+ * ws: GCN_SUBGRAPH_WS_BYTES of device scratch, owned by the call until it has run.  Negative sizes, a null pointer or a
+ * short workspace: GCN_ERR_INVALID_ARG; n_nodes == 0, m == 0 or nnz == 0: GCN_OK, nothing written (out_len keeps what it
+ * held: a caller who may pass nnz == 0 zeroes it first).  A caller whose counts sum to 0 has nothing to fill and skips the
+ * second call (its empty outputs may have no address, and a null output is refused). */
+#define GCN_SUBGRAPH_WS_BYTES 16
+int gcn_induced_subgraph_count_csr(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz,
+                                   const int32_t* nodes_dev, int32_t n_nodes, const int32_t* vmap_dev, int32_t* out_len_dev,
+                                   void* ws, size_t ws_bytes, void* stream);
+int gcn_induced_subgraph_fill_csr(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz,
+                                  const int32_t* nodes_dev, int32_t n_nodes, const int32_t* vmap_dev,
+                                  const int32_t* out_rowptr_dev, int32_t* out_col_dev, int32_t* out_eid_dev, void* ws,
+                                  size_t ws_bytes, void* stream);
+
+/* Uniform random walks on a square CSR pattern (GraphSAINT's random-walk sampler; DeepWalk's walks), a pure function of
+ * (seed, offset, walk index, step).  One kernel, no workspace, no allocation, no host read of device data, no atomics;
+ * every output element has one writer.  The stored values are not used; 4-byte accesses only.  The contract:
+ *   out_walks_dev is int32 [length + 1][n_walks], STEP-major: element (t, i) at out_walks_dev[t * n_walks + i] (the index
+ *   is computed in 64 bits).  Row 0 is the starts: out_walks[0][i] = starts_dev[i].
+ *   Step t = 0 .. length - 1 of walk i, at the vertex v = out_walks[t][i], d = rowptr[v + 1] - rowptr[v]:
+ *     d == 0 (a dead end), or a row pointer outside [0, nnz]: the walk stays, out_walks[t + 1][i] = v.  Otherwise let
+ *     L4 = 4 * ceil(length / 4) and j = i * L4 + t as a 64-bit integer;
+ *     key  = word (j & 3) of Philox4x32-10 with counter (lo32(j >> 2), hi32(j >> 2), lo32(offset), hi32(offset)) and key
+ *            (lo32(seed), hi32(seed)) — the word and counter convention of the dropout mask and of the sampling call;
+ *     pick = (key * d) >> 32, the high word of the 32 x 32-bit product, in [0, d);
+ *     c    = col[rowptr[v] + pick];  out_walks[t + 1][i] = c, or v when c is outside [0, m) (the walk stays).
+ *   L4 is a multiple of 4, so the four steps 4q .. 4q + 3 of a walk share the counter i * L4 / 4 + q: one Philox call
+ *   serves four consecutive steps.
+ * Uniformity: key is a uniform 32-bit word, so pick takes each value in [0, d) with probability floor or ceil of 2^32 / d
+ * over 2^32: uniform up to a bias below d / 2^32 per entry (relative), e.g. 2^-19 for a row of 8192 entries.  A stored
+ * entry that is repeated in a row is chosen in proportion to its multiplicity.
+ * A walk depends on its own index i, its start, length (through L4), seed and offset only — not on n_walks or on the other
+ * walks of the call; successive batches must use different offsets.
+ * A start outside [0, m) fills that walk with -1, row 0 included.  Negative sizes or a null pointer: GCN_ERR_INVALID_ARG
+ * (rowptr_dev may be null when m == 0, col_dev when nnz == 0); n_walks == 0: GCN_OK, nothing written; length == 0 writes
+ * row 0. */
+int gcn_random_walk_csr(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz, const int32_t* starts_dev,
+                        int32_t n_walks, int32_t length, uint64_t seed, uint64_t offset, int32_t* out_walks_dev, void* stream);
+
 /* LDS-staged row panels (optional): for matrices whose non-zeros sit near the diagonal (community
  * graphs after Rabbit / RCM / Gorder renumbering) a workgroup stages the feature rows of its panel's
  * column window (512 rows x 64 columns = 128 KiB of LDS) once and sums the in-window non-zeros
