@@ -23,6 +23,16 @@ REDUCE_MAX, REDUCE_MIN = 0, 1 # GCN_REDUCE_MAX / GCN_REDUCE_MIN (gcn_aggregate_c
 SAMPLE_LONG_ROW = 2048       # GCN_SAMPLE_LONG_ROW: longer rows get a workgroup, not a wave (gcn_sample_neighbors_csr)
 SAMPLE_WS_BYTES = 16         # GCN_SAMPLE_WS_BYTES
 SUBGRAPH_WS_BYTES = 16       # GCN_SUBGRAPH_WS_BYTES (gcn_induced_subgraph_count_csr / _fill_csr)
+BUCKET_WAVE_MAX = 256        # GCN_BUCKET_WAVE_MAX: longer buckets are ordered by a workgroup in LDS, not a wave (gcn_bucket_fill_i32)
+BUCKET_BLOCK_MAX = 8192      # GCN_BUCKET_BLOCK_MAX: longer buckets are ordered in place in global memory
+
+
+def bucket_ws_bytes(count, nbuckets):
+    """bytes of device scratch gcn_bucket_fill_i32 needs (the rule written out in include/gcn_spmm.h): four counters, a
+    cursor per bucket, and a list for each ordering tier as long as the number of buckets that can reach the tier"""
+    count, nbuckets = int(count), int(nbuckets)
+    ints = 4 + nbuckets + sum(min(nbuckets, count // (above + 1)) for above in (1, BUCKET_WAVE_MAX, BUCKET_BLOCK_MAX))
+    return (ints * 4 + 15) // 16 * 16
 
 
 _c_i32 = ctypes.c_int32
@@ -89,6 +99,9 @@ SIGNATURES = {
                                                      ctypes.c_size_t, _c_p]),
     "gcn_random_walk_csr": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_i32, ctypes.c_uint64, ctypes.c_uint64, _c_p,
                                            _c_p]),
+    "gcn_bucket_count_i32": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p]),
+    "gcn_bucket_fill_i32": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_csr_transpose_gather": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "gcn_spmm_plan_sddmm_kernel":(ctypes.c_int, [_c_p, _c_i32, ctypes.c_char_p, _c_i32]),
     "gcn_spmm_plan_enable_panels": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_p]),
     "gcn_spmm_plan_panel_rows": (_c_i32, [_c_p]),

@@ -45,8 +45,8 @@ def _workspace(adj, k, device):
 def _transpose_pattern(adj):
     """(rowptr, row of each entry, int32 permutation) of the transposed pattern, duplicates kept as separate entries;
     entry t of the transpose is entry perm[t] of adj.  A mutable adjacency has all three already (its transpose and
-    ``_tperm``); otherwise they are built once by the same construction (``CsrAdjacency._transposed_pattern``) — never
-    the coalescing ``transpose()``, which merges duplicates and keeps no permutation."""
+    ``_tperm``); otherwise they are built once by the same construction (``CsrAdjacency._transposed_pattern``) — not
+    by ``transpose()``, which keeps no permutation."""
     if adj.mutable_values:
         t = adj._mutable_transpose()
         perm = getattr(adj, "_tperm32", None)

@@ -368,6 +368,29 @@ int gcn_random_walk_csr(const int32_t* rowptr, const int32_t* col, int32_t m, in
              ? GCN_OK : GCN_ERR_HIP;
 }
 
+static_assert(kBucketWaveMax == GCN_BUCKET_WAVE_MAX && kBucketBlockMax == GCN_BUCKET_BLOCK_MAX, "include/gcn_spmm.h");
+
+int gcn_bucket_count_i32(const int32_t* keys, int32_t count, int32_t nbuckets, int32_t* offsets, void* stream) {
+  if (count < 0 || nbuckets < 0 || !offsets || (count > 0 && nbuckets > 0 && !keys)) return GCN_ERR_INVALID_ARG;
+  return launch_bucket_count(keys, count, nbuckets, offsets, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_bucket_fill_i32(const int32_t* keys, int32_t count, int32_t nbuckets, const int32_t* offsets, int32_t* perm, void* ws,
+                        size_t ws_bytes, void* stream) {
+  if (count < 0 || nbuckets < 0) return GCN_ERR_INVALID_ARG;
+  if (count == 0 || nbuckets == 0) return GCN_OK;
+  if (!keys || !offsets || !perm || !ws || ws_bytes < bucket_workspace_bytes(count, nbuckets)) return GCN_ERR_INVALID_ARG;
+  return launch_bucket_fill(keys, count, nbuckets, offsets, perm, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_csr_transpose_gather(const int32_t* rowptr, int32_t m, int32_t nnz, const int32_t* perm, const float* val, int32_t* trow,
+                             float* tval, void* stream) {
+  if (m < 0 || nnz < 0 || (val == nullptr) != (tval == nullptr)) return GCN_ERR_INVALID_ARG;
+  if (nnz == 0) return GCN_OK;
+  if (m == 0 || !rowptr || !perm || !trow) return GCN_ERR_INVALID_ARG;
+  return launch_transpose_gather(rowptr, m, nnz, perm, val, trow, tval, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
 int gcn_spmm_plan_sddmm_kernel(const gcn_spmm_plan_t* p, int32_t k, char* buf, int32_t buflen) {
   if (!p || k <= 0 || !buf || buflen <= 0) return GCN_ERR_INVALID_ARG;
   snprintf(buf, (size_t)buflen, "gcn::sddmm_kernel<%s, %s>", sddmm_sliced(p, k) ? "true" : "false",

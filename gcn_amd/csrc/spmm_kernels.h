@@ -205,6 +205,18 @@ hipError_t launch_induced_subgraph_fill(const int* rowptr, const int* col, int m
 hipError_t launch_random_walk(const int* rowptr, const int* col, int m, int nnz, const int* starts, int n_walks, int length,
                               unsigned long long seed, unsigned long long offset, int* out_walks, hipStream_t st);
 
+// construct.hip — stable bucketing of the indices 0 .. count - 1 by an int key in [0, nbuckets) (count, the caller's scan,
+// fill) and the gather that turns the bucketing of a CSR's entries by column into its transpose (see the file's header and
+// include/gcn_spmm.h).  A bucket of at most kBucketWaveMax entries is ordered by a wave, one of at most kBucketBlockMax by a
+// workgroup in LDS, a longer one by a workgroup in place.  ws: bucket_workspace_bytes(count, nbuckets) of device memory.
+constexpr int kBucketWaveMax = 256;
+constexpr int kBucketBlockMax = 8192;
+size_t bucket_workspace_bytes(int count, int nbuckets);
+hipError_t launch_bucket_count(const int* keys, int count, int nbuckets, int* offsets, hipStream_t st);
+hipError_t launch_bucket_fill(const int* keys, int count, int nbuckets, const int* offsets, int* perm, void* ws, hipStream_t st);
+hipError_t launch_transpose_gather(const int* rowptr, int m, int nnz, const int* perm, const float* val, int* trow, float* tval,
+                                   hipStream_t st);
+
 // slicing.hip — mutable values.  vsrc[s*m + r] = CSR position of the first entry of row r in slice s (from the sliced
 // row pointer; column-sorted rows make every (row, slice) part one contiguous run of the CSR row).
 hipError_t build_value_map(const int* rowptr, const int* vrowptr, int m, int S, int* vsrc, hipStream_t st);

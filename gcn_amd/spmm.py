@@ -385,17 +385,12 @@ class CsrAdjacency:
         return t
 
     def _transposed_pattern(self):
-        """(rowptr int32 [n+1], row of each entry int32 [nnz], perm int64 [nnz]) of the transposed pattern, built with
-        torch ops: entry t of the transpose is entry perm[t] of this adjacency; duplicates stay separate entries, in
-        their CSR order (a stable sort by (column, row))."""
-        dev = self.device
-        rp = self.rowptr.long()
-        rows = torch.repeat_interleave(torch.arange(self.m, device=dev), rp[1:] - rp[:-1], output_size=self.nnz)
-        c = self.col.long()
-        perm = torch.argsort(c * max(self.m, 1) + rows, stable=True)
-        trp = torch.zeros(self.n + 1, dtype=torch.int64, device=dev)
-        trp[1:] = torch.cumsum(torch.bincount(c, minlength=self.n), 0)
-        return trp.to(torch.int32), rows[perm].to(torch.int32), perm
+        """(rowptr int32 [n+1], row of each entry int32 [nnz], perm int64 [nnz]) of the transposed pattern, built on the
+        device (construct.py): entry t of the transpose is entry perm[t] of this adjacency; duplicates stay separate
+        entries, in their CSR order (a stable bucketing by column of entries that are already in row order)."""
+        from .construct import _transpose_arrays
+        trp, trow, _, eid = _transpose_arrays(self, with_values=False)
+        return trp, trow, eid.long()
 
     def _mutable_transpose(self):
         """Âᵀ of a mutable adjacency: itself mutable, never Â (a symmetric pattern does not make learned values
@@ -420,12 +415,8 @@ class CsrAdjacency:
         if self.symmetric:
             return self
         if self._transpose is None:
-            csr = torch.sparse_csr_tensor(self.rowptr.long(), self.col.long(), self.val,
-                                          size=(self.m, self.n))
-            t = csr.to_sparse_coo().t().coalesce().to_sparse_csr()
-            self._transpose = CsrAdjacency(t.crow_indices(), t.col_indices(), t.values(),
-                                           (self.n, self.m), symmetric=False,
-                                           chunk_nnz=self.chunk_nnz)
+            from .construct import transpose_csr
+            self._transpose = transpose_csr(self)[0]       # (repeated entries stay separate: the same matrix)
             self._transpose._transpose = self
         return self._transpose
 

@@ -384,6 +384,47 @@ int gcn_induced_subgraph_fill_csr(const int32_t* rowptr_dev, const int32_t* col_
 int gcn_random_walk_csr(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz, const int32_t* starts_dev,
                         int32_t n_walks, int32_t length, uint64_t seed, uint64_t offset, int32_t* out_walks_dev, void* stream);
 
+/* Stable bucketing of the indices 0 .. count - 1 by an integer key: the primitive under the device CSR transpose and under
+ * building a CSR from an edge list (gcn_amd/construct.py).  Two calls with the caller's prefix sum between them, as for the
+ * induced subgraph, and plan-free under the same rules: the caller's arrays, memset / copy nodes and kernels, no allocation,
+ * no host read of device data; the calls only enqueue on the given stream.  4-byte accesses only: no pointer needs more than
+ * 4-byte alignment.  The contract, exact and meant to be re-implemented (tests/construct_ref.py is the numpy twin):
+ *   keys_dev [count]: int32, every key in [0, nbuckets) — a precondition: a key outside the range is not counted and not
+ *   placed (nothing is written out of bounds), and the result is then not a permutation.
+ *   Count:  offsets_dev[0] = 0 and offsets_dev[b + 1] = the number of i with keys[i] == b, for b in [0, nbuckets).
+ *   The caller then turns offsets_dev [nbuckets + 1] into its inclusive prefix sum IN PLACE (offsets[b] = the start of
+ *   bucket b, offsets[nbuckets] = count).
+ *   Fill:   perm_dev[offsets[b] .. offsets[b + 1]) = the i with keys[i] == b, IN ASCENDING i.
+ * That is perm = argsort(keys, stable) and offsets = the prefix sum of bincount(keys, minlength = nbuckets), bit for bit
+ * and the same at every call: the counts are integer atomic adds, which commute, and the fill scatters the indices to
+ * their buckets with atomic cursors and then sorts every bucket of two or more entries, which takes the order the atomics
+ * landed in out of the result.  Every bucket length from 0 to count works and the host never reads one: a bucket of at most
+ * GCN_BUCKET_WAVE_MAX entries is ordered by one wave, one of at most GCN_BUCKET_BLOCK_MAX by a workgroup in LDS, a longer
+ * one by a workgroup in place; buckets of 0 or 1 entries get no per-bucket work.
+ * ws: device scratch owned by the fill until it has run, at least
+ *   16 + 4 * (nbuckets + min(nbuckets, count / 2) + min(nbuckets, count / (GCN_BUCKET_WAVE_MAX + 1))
+ *                      + min(nbuckets, count / (GCN_BUCKET_BLOCK_MAX + 1)))  bytes, rounded up to a multiple of 16
+ * (integer divisions; `gcn_amd._lib.bucket_ws_bytes`).  Negative sizes, a null pointer where data is required or a short
+ * workspace: GCN_ERR_INVALID_ARG.  count == 0 or nbuckets == 0: GCN_OK and no kernel is launched; the count call still
+ * zeroes offsets_dev [nbuckets + 1] (offsets[0] = 0 and empty buckets), the fill writes nothing and takes null pointers. */
+#define GCN_BUCKET_WAVE_MAX  256
+#define GCN_BUCKET_BLOCK_MAX 8192
+int gcn_bucket_count_i32(const int32_t* keys_dev, int32_t count, int32_t nbuckets, int32_t* offsets_dev, void* stream);
+int gcn_bucket_fill_i32(const int32_t* keys_dev, int32_t count, int32_t nbuckets, const int32_t* offsets_dev /* scanned */,
+                        int32_t* perm_dev, void* ws, size_t ws_bytes, void* stream);
+
+/* The arrays of a CSR transpose from the bucketing of its entries by column (keys = col_dev, nbuckets = n: the scanned
+ * offsets ARE the transpose's row pointer and perm maps its entries to the source's).  One lane per transposed entry t:
+ *   trow_dev[t] = the row r of source entry e = perm_dev[t], i.e. rowptr[r] <= e < rowptr[r + 1] (a binary search in
+ *   rowptr_dev [m + 1]); tval_dev[t] = val_dev[e] when val_dev is given.
+ * Entries of a transposed row come out in ascending e: ascending source row, repeated (row, column) pairs in source order;
+ * they stay separate entries.  An e outside [0, nnz) writes trow = -1, tval = 0 and reads nothing.
+ * val_dev and tval_dev are both null (pattern only) or both set.  Negative sizes, a null pointer where data is required,
+ * or nnz > 0 with m == 0: GCN_ERR_INVALID_ARG; nnz == 0: GCN_OK, nothing launched. */
+int gcn_csr_transpose_gather(const int32_t* rowptr_dev, int32_t m, int32_t nnz, const int32_t* perm_dev,
+                             const float* val_dev /* may be NULL */, int32_t* trow_dev, float* tval_dev /* NULL iff val is */,
+                             void* stream);
+
 /* LDS-staged row panels (optional): for matrices whose non-zeros sit near the diagonal (community
  * graphs after Rabbit / RCM / Gorder renumbering) a workgroup stages the feature rows of its panel's
  * column window (512 rows x 64 columns = 128 KiB of LDS) once and sums the in-window non-zeros
