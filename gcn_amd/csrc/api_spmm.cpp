@@ -44,6 +44,30 @@ struct Epilogue {                                      // C = dropout(act(A*B + 
   int gap_w = 0;
 };
 
+// The group walk of one call (spmm_group.hip; table: the sliced copy of B, fp32 or bf16, rows ld elements apart) into
+// p->cv, between the events of the live kernel timing (gcn_spmm_profile_begin; null: off), and what its cut rows need.
+// Rows cut by chunk ends: their later pieces are added by the caller's reduction itself (*cuts: the lists per output row),
+// or — GCN_AMD_GROUP_FUSED_FIXUP=0, or a plan without the lists — by a pass of their own here, in front of it.
+// (Both passes on a high-priority stream of their own, and the main kernels of two plans taking turns, were built and
+//  measured for the two planes of the multi-GPU layer in r04: 0.417 / 0.450 ms against 0.377 — DESIGN §6; removed again.)
+int run_group_walk(gcn_spmm_plan* p, const SliceSet& ss, bool weighted, const void* table, int elem_bytes, int ld, int k,
+                   hipEvent_t ev0, hipEvent_t ev1, hipStream_t st, CutLists* cuts) {
+  const GroupStream& G = *ss.g;
+  GroupArgs ga;
+  ga.stream = G.stream; ga.chunk_meta = G.chunk_meta;
+  ga.vals = weighted ? G.vals.get() : nullptr;
+  ga.Bp = table; ga.elem_bytes = elem_bytes; ga.Cv = p->cv; ga.P = p->ws;
+  ga.nchunks = G.nchunks; ga.T = G.T; ga.k = k; ga.ldb = ld;
+  ga.table_rows = ss.table_rows();
+  ga.narrow8 = group8_enabled() ? 1 : 0;
+  if (ev0 && hipEventRecord(ev0, st) != hipSuccess) return GCN_ERR_HIP;
+  if (launch_spmm_group(ga, st) != hipSuccess) return GCN_ERR_HIP;
+  if (ev1 && hipEventRecord(ev1, st) != hipSuccess) return GCN_ERR_HIP;
+  if (group_fused_fixup() && G.cutptr) { cuts->ptr = G.cutptr; cuts->chunk = G.cutchunk; cuts->P = p->ws; }
+  else if (launch_group_fixup(G.fix, G.nfix, p->ws, p->cv, k, st) != hipSuccess) return GCN_ERR_HIP;
+  return GCN_OK;
+}
+
 // b_ld: row stride of B in floats when the caller of this function has already re-laid it, 0 = k;
 // b_scaled: that copy's rows are already scaled by u_col (value-free pass).
 // *dropped: set when the dropout mask has been applied by a pass of this function (the slice reduction carries
@@ -128,24 +152,8 @@ int spmm_impl(gcn_spmm_plan* p, const SliceSet& ss, const int32_t* rowptr, const
   *dropped = epi.drop.on();
   if (grp) {
     // four independent 16-lane row engines per wave on the 15-bit slice-major stream (spmm_group.hip)
-    const GroupStream& G = *ss.g;
-    GroupArgs ga;
-    ga.stream = G.stream; ga.chunk_meta = G.chunk_meta;
-    ga.vals = weighted ? G.vals.get() : nullptr;
-    ga.Bp = a.B; ga.Cv = p->cv; ga.P = p->ws;
-    ga.nchunks = G.nchunks; ga.T = G.T; ga.k = k; ga.ldb = a.ldb;
-    ga.table_rows = ss.table_rows();
-    ga.narrow8 = group8_enabled() ? 1 : 0;
-    if (ev0 && hipEventRecord(ev0, st) != hipSuccess) return GCN_ERR_HIP;
-    if (launch_spmm_group(ga, st) != hipSuccess) return GCN_ERR_HIP;
-    if (ev1 && hipEventRecord(ev1, st) != hipSuccess) return GCN_ERR_HIP;
-    // rows cut by chunk ends: their later pieces are added by the reduction itself (cut lists per output row), or —
-    // GCN_AMD_GROUP_FUSED_FIXUP=0, or a plan without the lists — by a pass of their own in front of it
-    // (Both passes on a high-priority stream of their own, and the main kernels of two plans taking turns, were built and
-    //  measured for the two planes of the multi-GPU layer in r04: 0.417 / 0.450 ms against 0.377 — DESIGN §6; removed again.)
     CutLists cuts;
-    if (group_fused_fixup() && G.cutptr) { cuts.ptr = G.cutptr; cuts.chunk = G.cutchunk; cuts.P = p->ws; }
-    else if (launch_group_fixup(G.fix, G.nfix, p->ws, p->cv, k, st) != hipSuccess) return GCN_ERR_HIP;
+    if (const int rc = run_group_walk(p, ss, weighted, a.B, 4, a.ldb, k, ev0, ev1, st, &cuts); rc != GCN_OK) return rc;
     return launch_slice_reduce(p->cv, C, bias, relu, p->m, S_run, k, st, 0, weighted ? nullptr : p->factors.u_row.get(),
                                epi.drop, nullptr, epi.outscale, epi.gap_w, cuts) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
   }
@@ -539,20 +547,10 @@ int gcn_spmm_csr_bf16_epilogue(gcn_spmm_plan_t* p, const int32_t* rowptr, const 
     return GCN_ERR_HIP;
   if (grow(p->ws, ws_elems(p, k)) != GCN_OK) return GCN_ERR_ALLOC;
   if (grow(p->cv, (size_t)ss.S * (size_t)p->m * (size_t)k) != GCN_OK) return GCN_ERR_ALLOC;
-  GroupArgs ga;
-  ga.stream = G.stream; ga.chunk_meta = G.chunk_meta;
-  ga.vals = rt.weighted ? G.vals.get() : nullptr;
-  ga.Bp = nullptr; ga.Cv = p->cv; ga.P = p->ws;
-  ga.nchunks = G.nchunks; ga.T = G.T; ga.k = k; ga.ldb = rt.ldh;
-  ga.table_rows = ss.table_rows();
   hipEvent_t ev0 = nullptr, ev1 = nullptr;             // live timing of the main kernel (gcn_spmm_profile_begin)
   if (p->prof.armed()) { const auto pr = p->prof.next(); ev0 = pr.first; ev1 = pr.second; }
-  if (ev0 && hipEventRecord(ev0, st) != hipSuccess) return GCN_ERR_HIP;
-  if (launch_spmm_group_bf16(ga, table, st) != hipSuccess) return GCN_ERR_HIP;
-  if (ev1 && hipEventRecord(ev1, st) != hipSuccess) return GCN_ERR_HIP;
-  CutLists cuts;                                       // (as spmm_impl)
-  if (group_fused_fixup() && G.cutptr) { cuts.ptr = G.cutptr; cuts.chunk = G.cutchunk; cuts.P = p->ws; }
-  else if (launch_group_fixup(G.fix, G.nfix, p->ws, p->cv, k, st) != hipSuccess) return GCN_ERR_HIP;
+  CutLists cuts;
+  if (const int rc = run_group_walk(p, ss, rt.weighted, table, 2, rt.ldh, k, ev0, ev1, st, &cuts); rc != GCN_OK) return rc;
   DropoutSpec drop;
   drop.p = dropout_p; drop.seed = seed; drop.offset = offset;
   const float* rowscale = rt.weighted ? nullptr : p->factors.u_row.get();

@@ -311,7 +311,7 @@ Bf16Route bf16_route(gcn_spmm_plan* p, int k, bool build, const int32_t* rowptr,
   }
   const GroupStream* g = ss.g;
   if (!g || !g->ready() || g->nchunks % 32 != 0 || g->T < 64 || g->T % 64 != 0) return r;
-  if (spmm_group_bf16_needs_big(ss.table_rows(), ldh) && ldh * 2 >= (1 << 17)) return r;
+  if (spmm_group_needs_big(ss.table_rows(), ldh * 2LL) && ldh * 2 >= (1 << 17)) return r;
   r.group = true; r.weighted = weighted; r.ss = ss; r.ldh = ldh;
   return r;
 }
@@ -362,7 +362,7 @@ int gcn_spmm_plan_main_kernel(const gcn_spmm_plan_t* p, int32_t k, int32_t epilo
     // everything reported — stride, table size, addressing mode, chunk count — from THAT set
     bool relay = false;
     const SliceSet ss = pick_slice_set(const_cast<gcn_spmm_plan*>(p), a.k, &ld_eff, &relay, /*build=*/false, nullptr, nullptr, nullptr, nullptr);
-    const bool big = spmm_group_needs_big(ss.table_rows(), ld_eff);
+    const bool big = spmm_group_needs_big(ss.table_rows(), ld_eff * 4LL);
     const char* bigs = big ? "true" : "false";
     GroupArgs probe{};
     probe.k = a.k; probe.ldb = ld_eff; probe.table_rows = ss.table_rows();
@@ -371,15 +371,15 @@ int gcn_spmm_plan_main_kernel(const gcn_spmm_plan_t* p, int32_t k, int32_t epilo
     else if (spmm_group12_applies(probe))
       snprintf(buf, (size_t)buflen, "gcn::spmm_group12_kernel");
     else
-      snprintf(buf, (size_t)buflen, "gcn::spmm_group_ring_kernel<2, %s>", bigs);
+      snprintf(buf, (size_t)buflen, "gcn::spmm_group_ring_kernel<%s>", bigs);
     return GCN_OK;
   }
   if (!a.valless && weighted_pass(p, a.k, ld_eff)) {
-    const char* bigs = spmm_group_needs_big(group_table_rows(p), ld_eff) ? "true" : "false";
+    const char* bigs = spmm_group_needs_big(group_table_rows(p), ld_eff * 4LL) ? "true" : "false";
     if (group8_enabled() && a.k <= 32 && p->group.nchunks % 64 == 0)
       snprintf(buf, (size_t)buflen, "gcn::spmm_group8_weighted_kernel<%s>", bigs);
     else
-      snprintf(buf, (size_t)buflen, "gcn::spmm_group_weighted_kernel<2, %s>", bigs);
+      snprintf(buf, (size_t)buflen, "gcn::spmm_group_weighted_kernel<%s>", bigs);
     return GCN_OK;
   }
   describe_main_kernel(a, buf, (size_t)buflen);
@@ -391,7 +391,7 @@ int gcn_spmm_plan_main_kernel_bf16(const gcn_spmm_plan_t* p, int32_t k, int32_t 
   // (the slice set only as it exists: nothing is built here)
   const Bf16Route r = bf16_route(const_cast<gcn_spmm_plan*>(p), k, /*build=*/false, nullptr, nullptr, nullptr, nullptr);
   if (!r.group) return gcn_spmm_plan_main_kernel(p, k, epilogue, buf, buflen);    // the fallback runs the fp32 entry
-  const char* bigs = spmm_group_bf16_needs_big(r.ss.table_rows(), r.ldh) ? "true" : "false";
+  const char* bigs = spmm_group_needs_big(r.ss.table_rows(), r.ldh * 2LL) ? "true" : "false";
   snprintf(buf, (size_t)buflen, r.weighted ? "gcn::spmm_group_bf16_weighted_kernel<%s>" : "gcn::spmm_group_bf16_kernel<%s>", bigs);
   return GCN_OK;
 }
@@ -417,7 +417,7 @@ int32_t gcn_spmm_auto_slices(int64_t m, int64_t n, int64_t nnz, int32_t value_fr
 int32_t gcn_spmm_group_addressing(int64_t table_rows, int32_t ld_floats) {
   if (table_rows <= 0 || ld_floats <= 0) return -1;
   if (!spmm_group_eligible(ld_floats, ld_floats, table_rows, nullptr, nullptr, nullptr)) return -1;
-  return spmm_group_needs_big(table_rows, ld_floats) ? 1 : 0;
+  return spmm_group_needs_big(table_rows, ld_floats * 4LL) ? 1 : 0;
 }
 
 }  // extern "C"

@@ -96,16 +96,17 @@ bool spmm_quad_eligible(const SpmmArgs& a);
 int spmm_quad_lanes(int k);
 hipError_t launch_spmm_quad(const SpmmArgs& a, int nblocks, bool epi, hipStream_t s);
 
-// spmm_group.hip — value-free sliced main pass, four independent 16-lane row engines per wave
+// spmm_group.hip — sliced main pass, four independent 16-lane row engines per wave (the walk itself: group_walk.h)
 struct GroupArgs {
   const unsigned short* stream;  // [nchunks*T]: bits 0..14 column offset inside the slice, bit 15 = row end
   const float* vals = nullptr;   // [nchunks*T] matrix values in stream order (0 at padding entries); nullptr: every entry counts 1
   const int* chunk_meta;         // int2 [nchunks]: {2 * (virtual row holding entry c*T) + (it began in an earlier chunk),
                                  //                  first row of the chunk's slice in Bp}
-  const float* Bp;               // scaled copy of B: slice s at rows [s*(w+1), (s+1)*(w+1)), row w all zero
+  const void* Bp;                // the table: scaled copy of B, slice s at rows [s*(w+1), (s+1)*(w+1)), row w all zero
+  int elem_bytes = 4;            // ... of fp32 (4) or bf16 (2: k % 8 == 0, ldb % 8 == 0, no dyn; walked 128 columns per tile)
   float* Cv;                     // partial outputs [S*m x k]
   float* P;                      // partial slab [2*nchunks x k]
-  int nchunks, T, k, ldb;        // T = entries per chunk (of ONE 16-lane group), ldb = row stride of Bp (0 = k)
+  int nchunks, T, k, ldb;        // T = entries per chunk (of ONE 16-lane group), ldb = row stride of Bp in elements (0 = k)
   const int* dyn = nullptr;      // drop-in flexspmm: device words {buffers recognised, chunk count, cut rows}; nchunks is then an
                                  // upper bound that sizes the grid (dropin_guard_kernel, api_dropin.cpp)
   long long table_rows = 0;      // rows of Bp, S * (w + 1): decides 32-bit or 64-bit (BIG) slice-base addressing
@@ -115,8 +116,12 @@ struct GroupArgs {
   //  64-column tile in one launch: the alternatives were measured in round 2 and are no longer built)
 };
 bool spmm_group_eligible(int k, int ldb, long long table_rows, const void* B, const void* C, const void* P);
-bool spmm_group_needs_big(long long table_rows, int ldb);
-hipError_t launch_spmm_group(const GroupArgs& a, hipStream_t s);
+bool spmm_group_needs_big(long long table_rows, long long row_bytes);
+hipError_t launch_spmm_group(const GroupArgs& a, hipStream_t s);      // the single entry: every format, every kernel
+// grid and order of one group launch (group_grid, spmm_group.hip)
+struct GroupGrid { int blocks_per_tile, nblocks, stream_nt, seg_blocks; };
+// spmm_group_bf16.hip holds the bf16 instantiations of the walk; launch_spmm_group has checked the arguments
+hipError_t launch_group_walk_bf16(const GroupArgs& a, int ld, const GroupGrid& g, bool big, hipStream_t s);
 bool spmm_group8_applies(const GroupArgs& a);
 bool spmm_group12_applies(const GroupArgs& a);
 // the slice-major 15-bit stream the group kernel walks (S slices of width w = ceil(n/S) <= 32767): every virtual
@@ -225,10 +230,7 @@ hipError_t build_value_map(const int* rowptr, const int* vrowptr, int m, int S, 
 hipError_t launch_refresh_values(const int* vrowptr, const int* vsrc, const int* vrowptr_g, int m, int S, const float* val,
                                  float* vval, float* gvals, hipStream_t st);
 
-// spmm_group_bf16.hip — bf16 feature operands, fp32 accumulation.  The group walk on a bf16 table Bh (the layout of
-// GroupArgs::Bp, rows a.ldb bf16 apart, a.ldb % 8 == 0; a.Bp is not read), k % 8 == 0, partial rows into the fp32 Cv / P.
-hipError_t launch_spmm_group_bf16(const GroupArgs& a, const unsigned short* Bh, hipStream_t s);
-bool spmm_group_bf16_needs_big(long long table_rows, int ldh);   // BIG addressing for a bf16 table (counted in bytes)
+// spmm_group_bf16.hip — bf16 feature operands, fp32 accumulation: the element-wise passes around the walk.
 // the bf16 table: rowscale nullptr copies the bits (weighted pass), else bf16(rowscale[c] * src[c, :]) with one RNE rounding
 hipError_t launch_relay_bf16_sliced(unsigned short* dst, const unsigned short* src, const float* rowscale, int n, int k, int ld,
                                     int S, int w, hipStream_t s);

@@ -118,9 +118,9 @@ int gcn_dropout_f32(float* dst_dev, const float* src_dev, int64_t count, float d
  * bf16 C is rounded once (round to nearest even).  Values and bias stay fp32.
  *   Hot path: k % 8 == 0, k >= 64, on a plan whose k-wide call would run a group kernel (column slicing, no panels): B is
  *   re-laid as a bf16 table in the group kernels' slice layout — value-free pass: bf16(u_col[c] * B[c, :]), rounded once
- *   (relative error <= 2^-9 per entry); weighted pass: the bits of B — and walked by spmm_group_bf16[_weighted]_kernel, one
- *   128-column tile per pass, into the same fp32 partial rows the fp32 path reduces.  The slice set is the one an fp32
- *   call with the same row bytes (k / 2 columns) takes.
+ *   (relative error <= 2^-9 per entry); weighted pass: the bits of B — and walked by spmm_group_bf16[_weighted]_kernel (the
+ *   group walk of the fp32 kernels on rows of bf16), one 128-column tile per pass, into the same fp32 partial rows the
+ *   fp32 path reduces.  The slice set is the one an fp32 call with the same row bytes (k / 2 columns) takes.
  *   Fallback, every other plan and width: B widened to fp32 in a plan buffer, the fp32 entry, C narrowed.  Correct, not
  *   fast: three passes and fp32 traffic.
  * A plan is shared with the fp32 calls (its re-laid copy of B serves both); like the fp32 calls, the calls of one plan

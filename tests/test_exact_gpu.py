@@ -98,7 +98,7 @@ def _assert_group_kernel(adj, k, weighted):
     elif k <= 32 or weighted:
         assert name.startswith("gcn::spmm_group_weighted_kernel<" if weighted else "gcn::spmm_group_ring_kernel<"), (k, name)
     elif 33 <= k <= 48:                                              # five 12-lane engines (GCN_AMD_GROUP12=0: the ring kernel)
-        assert name in ("gcn::spmm_group12_kernel", "gcn::spmm_group_ring_kernel<2, false>"), (k, name)
+        assert name in ("gcn::spmm_group12_kernel", "gcn::spmm_group_ring_kernel<false>"), (k, name)
     else:                                                            # four 16-lane engines
         assert name.startswith("gcn::spmm_group_ring_kernel<"), (k, name)
     return name

@@ -10,7 +10,7 @@ import scipy.sparse as sp
 import torch
 
 import gcn_amd
-from util import oracle_spmm, rel_err
+from util import bf16_assert_bound, bf16_reference, oracle_spmm, rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -127,9 +127,16 @@ def test_group12_kernel_random(seed):
 
 def _big_child():
     """runs in a child process with GCN_AMD_GROUP_BIG=1 (the knob is read once per process): every group kernel in
-    its 64-bit slice-base variant — what tables of 4 GiB and more get — against the fp64 oracle"""
+    its 64-bit slice-base variant — what tables of 4 GiB and more get — against the fp64 oracle; fp32 tables, and bf16
+    ones (the same walk on 128-column tiles) at k = 64 (half the lanes of the one tile hold no column), 200 (a partial last
+    tile) and 320 (three tiles) within the bf16 bound of test_bf16_gpu.py.  Prints a digest of every result; without the
+    knob (a second child) the same calls run the 32-bit variants and print the same digest: BIG is addressing only."""
+    import hashlib
     d = torch.device("cuda:0")
+    big = os.environ.get("GCN_AMD_GROUP_BIG") == "1"
+    h = hashlib.sha256()
     seen = set()
+    n_bf16 = 0
     for seed in range(12):
         n, rowptr, col, val, rng = _graph(seed)
         S = int(rng.choice([2, 3, 5, 8, 13, 16]))
@@ -141,29 +148,54 @@ def _big_child():
         for k in (int(rng.choice([36, 64, 100, 128, 41, 192])), int(rng.choice([12, 16, 20, 24, 32]))):
             name = adj.main_kernel(k)
             if name.startswith("gcn::spmm_group"):
-                assert name.endswith("true>"), name                          # the BIG instantiation
+                assert name.endswith("true>") == big, name                   # the BIG instantiation
                 seen.add(name.split("<")[0])
             B = rng.standard_normal((n, k)).astype(np.float32)
-            C = adj.matmul_raw(torch.from_numpy(B).to(d))
-            err = rel_err(C.cpu().numpy(), oracle_spmm(rowptr, col, val, B))
+            C = adj.matmul_raw(torch.from_numpy(B).to(d)).cpu().numpy()
+            err = rel_err(C, oracle_spmm(rowptr, col, val, B))
             assert err <= TOL, (seed, n, S, k, name, err)
-    want = {"gcn::spmm_group_ring_kernel", "gcn::spmm_group_weighted_kernel", "gcn::spmm_group8_kernel"}
+            h.update(C.tobytes())
+        if weighted and seed != 2:
+            continue
+        # bf16 operands: the value-free seeds take the three widths in turn, the weighted seed all of them
+        for k in ((64, 200, 320) if weighted else ((64, 200, 320)[n_bf16 % 3],)):
+            name = adj.main_kernel(k, dtype=torch.bfloat16)
+            assert name.startswith("gcn::spmm_group_bf16") and name.endswith("true>") == big, name
+            assert not weighted or "weighted" in name, name
+            seen.add(name.split("<")[0])
+            B = torch.from_numpy(rng.standard_normal((n, k)).astype(np.float32)).to(d).to(torch.bfloat16)
+            Cref, absref = bf16_reference(rowptr, col, val, B)
+            C16 = adj.matmul_raw(B)
+            C32 = adj.matmul_raw(B, out=torch.empty((n, k), dtype=torch.float32, device=d))
+            bf16_assert_bound(C16, Cref, absref, bf16_out=True)
+            bf16_assert_bound(C32, Cref, absref, bf16_out=False)
+            h.update(C16.view(torch.int16).cpu().numpy().tobytes())
+            h.update(C32.cpu().numpy().tobytes())
+        n_bf16 += 1
+    want = {"gcn::spmm_group_ring_kernel", "gcn::spmm_group_weighted_kernel", "gcn::spmm_group8_kernel",
+            "gcn::spmm_group_bf16_kernel", "gcn::spmm_group_bf16_weighted_kernel"}
     if os.environ.get("GCN_AMD_GROUP8", "1") == "0":
         want.discard("gcn::spmm_group8_kernel")                 # (the switch that keeps narrow widths off the eight-engine kernel)
-    assert want <= seen, seen
+    assert not big or want <= seen, seen
     print("big ok", sorted(seen))
+    print("big digest", h.hexdigest())
 
 
 def test_group_kernels_with_64_bit_slice_bases():
-    """the BIG variants of the group kernels (slice base added in 64 bits; tables past 4 GiB or 2^24 rows use them,
-    gcn_spmm_group_addressing) forced on small graphs through the development knob, in ONE child process"""
+    """the BIG variants of the group kernels, fp32 and bf16 tables (slice base added in 64 bits; tables past 4 GiB or 2^24
+    rows use them, gcn_spmm_group_addressing) forced on small graphs through the development knob, in ONE child process;
+    a second child without the knob computes the same bits (trivially so when the suite itself runs under the knob)"""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, GCN_AMD_GROUP_BIG="1", PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--big-child"], env=env, capture_output=True, text=True,
-                         timeout=600, cwd=os.path.dirname(os.path.abspath(__file__)))
-    assert out.returncode == 0 and "big ok" in out.stdout, out.stdout[-1500:] + out.stderr[-1500:]
+    digests = []
+    for knob in ({"GCN_AMD_GROUP_BIG": "1"}, {}):
+        env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""), **knob)
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--big-child"], env=env, capture_output=True, text=True,
+                             timeout=600, cwd=os.path.dirname(os.path.abspath(__file__)))
+        assert out.returncode == 0 and "big ok" in out.stdout, out.stdout[-1500:] + out.stderr[-1500:]
+        digests.append(out.stdout.split("big digest")[1].split()[0])
+    assert digests[0] == digests[1], digests
 
 
 def _fixup_child():
@@ -200,7 +232,8 @@ def test_group_kernels_with_the_fix_up_pass_of_its_own():
 def _segments_child():
     """runs in a child process with GCN_AMD_GROUP_SEGMENTS=<runs per XCD>: the (column tile, block) order inside the merged
     launch is placement only — prints a digest of the results of several plans and widths (incl. widths of 3-8 tiles, runs
-    that do not divide an XCD's blocks, a weighted plan); the parent compares the digests of different orders"""
+    that do not divide an XCD's blocks, a weighted plan; fp32 tables, and bf16 ones at 2, 3 and 4 tiles of 128 columns);
+    the parent compares the digests of different orders"""
     import hashlib
     d = torch.device("cuda:0")
     h = hashlib.sha256()
@@ -226,12 +259,32 @@ def _segments_child():
         C = adj.matmul_raw(torch.from_numpy(B).to(d)).cpu().numpy()
         assert adj.main_kernel(k).startswith("gcn::spmm_group_ring") and rel_err(C, oracle_spmm(rowptr, col, val, B)) <= TOL
         h.update(C.tobytes())
+    # bf16 tables: the same order arithmetic on 128-column tiles, value-free on this plan and weighted on a copy whose values
+    # do not factor.  An order other than tile-major needs more than one block per tile and XCD, i.e. more than 128 chunks in
+    # the group stream; the stream holds every stored entry and a chunk at most 1024 of them (group_chunk, plan_policy.cpp),
+    # and the plan's own chunks say how many entries there are.  (None of the small graphs above has enough: the results are
+    # compared with each other here, the bf16 bound is test_bf16_gpu.py's and the 64-bit child's.)
+    wval = (val * (1.0 + 0.5 * np.random.default_rng(5).random(len(val)))).astype(np.float32)
+    wadj = gcn_amd.CsrAdjacency(torch.from_numpy(rowptr).to(d), torch.from_numpy(col).to(d), torch.from_numpy(wval).to(d), (n, n),
+                                slices=adj.num_slices)
+    for a, weighted in ((adj, False), (wadj, True)):
+        assert (a.num_chunks - 1) * a.chunk_size // 1024 > 128, (a.num_chunks, a.chunk_size)
+        for k in (256, 320, 512):
+            name = a.main_kernel(k, dtype=torch.bfloat16)
+            assert name.startswith("gcn::spmm_group_bf16") and ("weighted" in name) == weighted, name
+            B = torch.from_numpy(np.random.default_rng(k + 1).standard_normal((n, k)).astype(np.float32)).to(d).to(torch.bfloat16)
+            C16 = a.matmul_raw(B)
+            C32 = a.matmul_raw(B, out=torch.empty((n, k), dtype=torch.float32, device=d))
+            assert torch.equal(C16, C32.to(torch.bfloat16))              # (the bf16 result is the fp32 one rounded once)
+            h.update(C16.view(torch.int16).cpu().numpy().tobytes())
+            h.update(C32.cpu().numpy().tobytes())
     print("segments digest", h.hexdigest())
 
 
 def test_tile_order_inside_the_merged_launch_is_placement_only():
     """GCN_AMD_GROUP_SEGMENTS = 1 (tile-major), 2, 3, 7 runs per XCD: bit-identical results (and each within 1e-5 of the
-    oracle) — the order in which a launch walks its (tile, block) pairs (spmm_group.hip, launch_group_t) never shows"""
+    oracle) — the order in which a launch walks its (tile, block) pairs (group_tile_block, group_walk.h; one rule for
+    fp32 and bf16 tables: group_grid, spmm_group.hip) never shows"""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
