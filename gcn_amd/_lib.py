@@ -25,6 +25,10 @@ SAMPLE_WS_BYTES = 16         # GCN_SAMPLE_WS_BYTES
 SUBGRAPH_WS_BYTES = 16       # GCN_SUBGRAPH_WS_BYTES (gcn_induced_subgraph_count_csr / _fill_csr)
 BUCKET_WAVE_MAX = 256        # GCN_BUCKET_WAVE_MAX: longer buckets are ordered by a workgroup in LDS, not a wave (gcn_bucket_fill_i32)
 BUCKET_BLOCK_MAX = 8192      # GCN_BUCKET_BLOCK_MAX: longer buckets are ordered in place in global memory
+COALESCE_WS_BYTES = 16       # GCN_COALESCE_WS_BYTES (gcn_csr_coalesce_count / _fill)
+COALESCE_SUM, COALESCE_MAX, COALESCE_MIN, COALESCE_FIRST = 0, 1, 2, 3   # GCN_COALESCE_*: the value of a merged run
+DIAG_KEEP, DIAG_DROP, DIAG_FILL, DIAG_ADD = 0, 1, 2, 3                   # GCN_DIAG_*: what the merge does to the diagonal
+NORM_SYM, NORM_ROW = 0, 1    # GCN_NORM_SYM / GCN_NORM_ROW (gcn_csr_normalize_f32)
 
 
 def bucket_ws_bytes(count, nbuckets):
@@ -102,6 +106,11 @@ SIGNATURES = {
     "gcn_bucket_count_i32": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p]),
     "gcn_bucket_fill_i32": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_csr_transpose_gather": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "gcn_csr_coalesce_count": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_csr_coalesce_fill": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, ctypes.c_float, _c_p, _c_p,
+                                             _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_csr_degree_f64": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p]),
+    "gcn_csr_normalize_f32": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_p]),
     "gcn_spmm_plan_sddmm_kernel":(ctypes.c_int, [_c_p, _c_i32, ctypes.c_char_p, _c_i32]),
     "gcn_spmm_plan_enable_panels": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_p]),
     "gcn_spmm_plan_panel_rows": (_c_i32, [_c_p]),

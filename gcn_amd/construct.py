@@ -113,7 +113,8 @@ def csr_from_edges(rows, cols, shape, values=None, sort_columns=True):
     bucketings, by column and then by row, i.e. ``np.lexsort((cols, rows))``.  False: one bucketing by row, the entries of
     a row keep their input order.
     REPEATED EDGES ARE NOT MERGED: they stay separate entries, and every kernel of this library adds them (a repeated edge
-    weighs twice).  Symmetrising and inserting missing self-loops are out of scope; both need a merge step.
+    weighs twice).  Symmetrising and inserting missing self-loops are out of scope here; both need a merge step, which
+    lives in coalesce.py: ``coalesce_csr``, ``symmetrize``, and ``gcn_adjacency`` for the whole way from an edge list to Â.
     The result is flagged ``symmetric=False`` (nothing here checks symmetry; pass the arrays to ``CsrAdjacency`` with
     ``symmetric=True`` when it is known).  One host synchronisation (the range of the ids): not capturable.
     ValueError for a bad dtype, shape, length, values or an id out of range, GcnAmdError for CPU tensors."""

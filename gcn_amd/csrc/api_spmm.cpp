@@ -399,6 +399,49 @@ int gcn_csr_transpose_gather(const int32_t* rowptr, int32_t m, int32_t nnz, cons
   return launch_transpose_gather(rowptr, m, nnz, perm, val, trow, tval, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
 }
 
+static_assert(kCoalesceWsBytes == GCN_COALESCE_WS_BYTES && kCoalesceSum == GCN_COALESCE_SUM && kCoalesceMax == GCN_COALESCE_MAX &&
+              kCoalesceMin == GCN_COALESCE_MIN && kCoalesceFirst == GCN_COALESCE_FIRST && kDiagKeep == GCN_DIAG_KEEP &&
+              kDiagDrop == GCN_DIAG_DROP && kDiagFill == GCN_DIAG_FILL && kDiagAdd == GCN_DIAG_ADD && kNormSym == GCN_NORM_SYM &&
+              kNormRow == GCN_NORM_ROW, "include/gcn_spmm.h");
+
+int gcn_csr_coalesce_count(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t n, int32_t nnz, int32_t diagonal,
+                           int32_t* out_len, void* ws, size_t ws_bytes, void* stream) {
+  if (m < 0 || n < 0 || nnz < 0 || diagonal < GCN_DIAG_KEEP || diagonal > GCN_DIAG_ADD) return GCN_ERR_INVALID_ARG;
+  if (m == 0) return GCN_OK;
+  if (!rowptr || (nnz > 0 && !col) || !out_len || !ws || ws_bytes < kCoalesceWsBytes) return GCN_ERR_INVALID_ARG;
+  return launch_csr_coalesce_count(rowptr, col, m, n, nnz, diagonal, out_len, ws, (hipStream_t)stream) == hipSuccess
+             ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_csr_coalesce_fill(const int32_t* rowptr, const int32_t* col, const float* val, int32_t m, int32_t n, int32_t nnz,
+                          int32_t reduce, int32_t diagonal, float diag_value, const int32_t* out_rowptr, int32_t* out_col,
+                          float* out_val, int32_t* out_first, int32_t* seg, void* ws, size_t ws_bytes, void* stream) {
+  if (m < 0 || n < 0 || nnz < 0 || reduce < GCN_COALESCE_SUM || reduce > GCN_COALESCE_FIRST || diagonal < GCN_DIAG_KEEP ||
+      diagonal > GCN_DIAG_ADD || (val == nullptr) != (out_val == nullptr))
+    return GCN_ERR_INVALID_ARG;
+  if (m == 0) return GCN_OK;
+  if (!rowptr || (nnz > 0 && !col) || !out_rowptr || !out_col || !ws || ws_bytes < kCoalesceWsBytes) return GCN_ERR_INVALID_ARG;
+  return launch_csr_coalesce_fill(rowptr, col, val, m, n, nnz, reduce, diagonal, diag_value, out_rowptr, out_col, out_val,
+                                  out_first, seg, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_csr_degree_f64(const int32_t* rowptr, const float* val, int32_t m, int32_t nnz, double* deg, void* stream) {
+  if (m < 0 || nnz < 0) return GCN_ERR_INVALID_ARG;
+  if (m == 0) return GCN_OK;
+  if (!rowptr || !deg) return GCN_ERR_INVALID_ARG;
+  return launch_csr_degree(rowptr, val, m, nnz, deg, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_csr_normalize_f32(const int32_t* rowptr, const int32_t* col, const float* val, int32_t m, int32_t n, int32_t nnz,
+                          const double* deg, int32_t mode, float* out_val, void* stream) {
+  if (m < 0 || n < 0 || nnz < 0 || (mode != GCN_NORM_SYM && mode != GCN_NORM_ROW) || (mode == GCN_NORM_SYM && m != n))
+    return GCN_ERR_INVALID_ARG;
+  if (m == 0 || nnz == 0) return GCN_OK;
+  if (!rowptr || !col || !deg || !out_val) return GCN_ERR_INVALID_ARG;
+  return launch_csr_normalize(rowptr, col, val, m, n, nnz, deg, mode, out_val, (hipStream_t)stream) == hipSuccess ? GCN_OK
+                                                                                                                  : GCN_ERR_HIP;
+}
+
 int gcn_spmm_plan_sddmm_kernel(const gcn_spmm_plan_t* p, int32_t k, char* buf, int32_t buflen) {
   if (!p || k <= 0 || !buf || buflen <= 0) return GCN_ERR_INVALID_ARG;
   snprintf(buf, (size_t)buflen, "gcn::sddmm_kernel<%s, %s>", sddmm_sliced(p, k) ? "true" : "false",

@@ -222,6 +222,24 @@ hipError_t launch_bucket_fill(const int* keys, int count, int nbuckets, const in
 hipError_t launch_transpose_gather(const int* rowptr, int m, int nnz, const int* perm, const float* val, int* trow, float* tval,
                                    hipStream_t st);
 
+// coalesce.hip — merging the runs of equal columns of a CSR's rows (count, the caller's scan, fill), with the diagonal
+// dropped, filled or added to on the way, and the two kernels of the normalisation: row sums in fp64 and the scaled values
+// (plan-free, no global atomics: see the file's header and include/gcn_spmm.h).  out_rowptr [m + 1] is an INPUT of the
+// fill; ws: kCoalesceWsBytes of device memory (a flag).  Rows of more than kSampleLongRow entries get a 256-thread workgroup
+// instead of a wave, in all four.
+constexpr size_t kCoalesceWsBytes = 16;
+constexpr int kCoalesceSum = 0, kCoalesceMax = 1, kCoalesceMin = 2, kCoalesceFirst = 3;      // GCN_COALESCE_*
+constexpr int kDiagKeep = 0, kDiagDrop = 1, kDiagFill = 2, kDiagAdd = 3;                     // GCN_DIAG_*
+constexpr int kNormSym = 0, kNormRow = 1;                                                    // GCN_NORM_*
+hipError_t launch_csr_coalesce_count(const int* rowptr, const int* col, int m, int n, int nnz, int diagonal, int* out_len,
+                                     void* ws, hipStream_t st);
+hipError_t launch_csr_coalesce_fill(const int* rowptr, const int* col, const float* val, int m, int n, int nnz, int reduce,
+                                    int diagonal, float diag_value, const int* out_rowptr, int* out_col, float* out_val,
+                                    int* out_first, int* seg, void* ws, hipStream_t st);
+hipError_t launch_csr_degree(const int* rowptr, const float* val, int m, int nnz, double* deg, hipStream_t st);
+hipError_t launch_csr_normalize(const int* rowptr, const int* col, const float* val, int m, int n, int nnz, const double* deg,
+                                int mode, float* out_val, hipStream_t st);
+
 // slicing.hip — mutable values.  vsrc[s*m + r] = CSR position of the first entry of row r in slice s (from the sliced
 // row pointer; column-sorted rows make every (row, slice) part one contiguous run of the CSR row).
 hipError_t build_value_map(const int* rowptr, const int* vrowptr, int m, int S, int* vsrc, hipStream_t st);

@@ -425,6 +425,89 @@ int gcn_csr_transpose_gather(const int32_t* rowptr_dev, int32_t m, int32_t nnz, 
                              const float* val_dev /* may be NULL */, int32_t* trow_dev, float* tval_dev /* NULL iff val is */,
                              void* stream);
 
+/* Merging the repeated (row, column) entries of a CSR matrix, with the diagonal dropped, filled or added to on the way:
+ * what turns an edge list with repeats and mirrors into the pattern of A + A^T, A + I or their union (gcn_amd/coalesce.py),
+ * as two calls with the caller's prefix sum between them.  Plan-free like the induced subgraph and under the same rules:
+ * the caller's arrays, one memset node and kernels, no allocation, no host read of device data, no global atomics; every
+ * output element has one writer, so a call gives the same bits every time.  Every access is a 4-byte one: no pointer
+ * needs more than 4-byte alignment.  The contract, exact and meant to be re-implemented (tests/coalesce_ref.py is the
+ * numpy twin):
+ *   Input: rowptr_dev [m + 1], col_dev [nnz], val_dev [nnz] or NULL (a pattern), n the number of columns.
+ *   RUNS.  A run is a maximal stretch of consecutive entries of one row with the same column; its first entry is the head.
+ *   With column-sorted rows — the precondition of a full merge; two stable bucketings give that order — a run is exactly
+ *   one distinct (row, column) pair.  On unsorted rows the calls stay memory-safe and are defined by the same sentence:
+ *   only adjacent equal columns merge.
+ *   VALUES.  The value of a run e_0 < ... < e_k is folded in fp32, left to right in entry order, by `reduce`:
+ *     GCN_COALESCE_SUM:    acc = val[e_0]; acc += val[e_j]
+ *     GCN_COALESCE_MAX:    acc = val[e_0]; acc = (v > acc || v != v) ? v : acc   (a NaN propagates, as in np.maximum)
+ *     GCN_COALESCE_MIN:    the same with <
+ *     GCN_COALESCE_FIRST:  val[e_0]
+ *   The head's lane walks its run: a run costs its length in ONE lane.  Real inputs have runs of 1-3 entries; a run of
+ *   thousands is correct and slow.
+ *   DIAGONAL.  `diagonal` applies to the rows r < n, whose diagonal column is r (a row r >= n has none):
+ *     GCN_DIAG_KEEP:  no special handling.
+ *     GCN_DIAG_DROP:  runs with col == r produce no output entry.
+ *     GCN_DIAG_FILL:  if no entry of the row has col == r, one entry (r, r, diag_value) is inserted; an existing diagonal
+ *                     entry stays as merged.
+ *     GCN_DIAG_ADD:   the same insertion, and an existing diagonal run becomes merged + diag_value: one more fp32 add,
+ *                     applied last.
+ *   The output entries of a row are its heads (less the dropped ones) in entry order.  An inserted entry takes output
+ *   position P = the number of heads of the row with col < r, and the heads from that position on move up by one: on a
+ *   column-sorted row it sits after the entries with col < r and before those with col > r.  "No entry has col == r" and
+ *   P are defined, and computed, without sortedness.
+ *   Count:  out_len_dev[r] = the number of output entries of row r.
+ *   The caller turns out_len into out_rowptr_dev [m + 1], its exclusive prefix sum, an INPUT of the fill.
+ *   Fill, for output entry j = out_rowptr[r] + t of row r:
+ *     out_col_dev[j], out_val_dev[j] (when given): the column and the value as above;
+ *     out_first_dev[j] (when given): the head's entry index in the input, or -1 for an inserted diagonal;
+ *     seg_dev[e] (when given) for every input entry e of the row: the output entry j it was merged into, or -1 when it
+ *     was dropped.
+ *   val_dev == NULL means a pattern: out_val_dev must then be NULL too, and the reverse (GCN_ERR_INVALID_ARG otherwise).
+ * These write nothing for their row: a row pointer outside [0, nnz], and in the fill a row whose out_rowptr length differs
+ * from its count (or whose out_rowptr[r] is negative).  Every row length from 0 to nnz works and the host never reads one:
+ * a row of at most GCN_SAMPLE_LONG_ROW entries is taken by one wave, a longer one by a 256-thread workgroup.
+ * ws: GCN_COALESCE_WS_BYTES of device scratch, owned by the call until it has run.  Negative sizes, a null pointer where
+ * data is required (col_dev may be null when nnz == 0; out_first_dev and seg_dev are optional), a short workspace or an
+ * unknown reduce / diagonal code: GCN_ERR_INVALID_ARG.  m == 0: GCN_OK, nothing written.  nnz == 0 is an ordinary call:
+ * with FILL or ADD it still inserts the diagonals.  A caller whose counts sum to 0 has nothing to fill and skips the second
+ * call (every entry was dropped: seg is -1 everywhere). */
+#define GCN_COALESCE_WS_BYTES 16
+#define GCN_COALESCE_SUM   0
+#define GCN_COALESCE_MAX   1
+#define GCN_COALESCE_MIN   2
+#define GCN_COALESCE_FIRST 3
+#define GCN_DIAG_KEEP 0
+#define GCN_DIAG_DROP 1
+#define GCN_DIAG_FILL 2
+#define GCN_DIAG_ADD  3
+int gcn_csr_coalesce_count(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t n, int32_t nnz,
+                           int32_t diagonal, int32_t* out_len_dev, void* ws, size_t ws_bytes, void* stream);
+int gcn_csr_coalesce_fill(const int32_t* rowptr_dev, const int32_t* col_dev, const float* val_dev /* may be NULL */, int32_t m,
+                          int32_t n, int32_t nnz, int32_t reduce, int32_t diagonal, float diag_value,
+                          const int32_t* out_rowptr_dev, int32_t* out_col_dev, float* out_val_dev /* NULL iff val is */,
+                          int32_t* out_first_dev /* may be NULL */, int32_t* seg_dev /* may be NULL */, void* ws,
+                          size_t ws_bytes, void* stream);
+
+/* The two kernels of a normalised adjacency on a CSR matrix: its row sums, and the scaled values.  Plan-free, no workspace,
+ * no atomics, one writer per element; a wave per row and a 256-thread workgroup per row of more than GCN_SAMPLE_LONG_ROW
+ * entries, so no expanded row array and no nnz-sized intermediate exists.  deg_dev is fp64 and needs 8-byte alignment;
+ * every other access is a 4-byte one.
+ *   Degree:  deg_dev[r] = the sum of val_dev over row r, accumulated in fp64 — or the row's length when val_dev is NULL.
+ *   The order of the sum is fixed (the same bits at every call) and otherwise unspecified.
+ *   Normalise, for every entry e of row r with column c and v = val_dev[e] (1 when val_dev is NULL), in fp64:
+ *     GCN_NORM_SYM (m == n required):  out_val_dev[e] = (float)(s_r * v * s_c),  s_i = deg[i] == 0 ? 0 : 1 / sqrt(deg[i])
+ *     GCN_NORM_ROW:                    out_val_dev[e] = (float)(v * t_r),        t_r = deg[r] == 0 ? 0 : 1 / deg[r]
+ *   (the zero for a zero degree is the inf -> 0 rule of the usual host formulation).  A column outside [0, n) is not
+ *   followed (s_c = 0); a row pointer outside [0, nnz] writes nothing for its row.  out_val_dev may be val_dev.
+ * Negative sizes, a null pointer where data is required, an unknown mode or GCN_NORM_SYM with m != n: GCN_ERR_INVALID_ARG;
+ * m == 0 (and for the normalisation nnz == 0): GCN_OK, nothing written. */
+#define GCN_NORM_SYM 0
+#define GCN_NORM_ROW 1
+int gcn_csr_degree_f64(const int32_t* rowptr_dev, const float* val_dev /* may be NULL */, int32_t m, int32_t nnz, double* deg_dev,
+                       void* stream);
+int gcn_csr_normalize_f32(const int32_t* rowptr_dev, const int32_t* col_dev, const float* val_dev /* may be NULL */, int32_t m,
+                          int32_t n, int32_t nnz, const double* deg_dev, int32_t mode, float* out_val_dev, void* stream);
+
 /* LDS-staged row panels (optional): for matrices whose non-zeros sit near the diagonal (community
  * graphs after Rabbit / RCM / Gorder renumbering) a workgroup stages the feature rows of its panel's
  * column window (512 rows x 64 columns = 128 KiB of LDS) once and sums the in-window non-zeros
