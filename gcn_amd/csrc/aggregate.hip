@@ -34,6 +34,7 @@
 #include <climits>
 #include <cmath>
 
+#include "long_chunks.h"
 #include "spmm_kernels.h"
 
 namespace gcn {
@@ -323,35 +324,7 @@ __global__ void __launch_bounds__(256) agg_rows_kernel(Op op, const int* __restr
   }
 }
 
-// ---- long rows ----------------------------------------------------------------------------------------------------------
-// the row holding entry e0 (0 <= e0 < nnz): the largest r < rows with rowptr[r] <= e0 — never an empty row.  64 probes a round.
-__device__ __forceinline__ int find_row(const int* __restrict__ rowptr, int rows, int e0, int lane) {
-  int lo = 0, hi = rows;                               // rowptr[lo] <= e0, and rowptr[hi] > e0 or hi == rows
-  while (hi - lo > 1) {
-    const int step = (hi - lo + 63) >> 6;
-    const long long probe = (long long)lo + (long long)lane * step;
-    const bool le = probe < hi && rowptr[probe] <= e0;
-    const int cnt = __popcll(__ballot(le));            // (rowptr is monotone: the lanes that say yes are a prefix)
-    lo += (cnt > 0 ? cnt - 1 : 0) * step;              // (cnt == 0 only with rowptr[0] > 0: never index backwards)
-    hi = lo + step < hi ? lo + step : hi;
-  }
-  return lo;
-}
-
-// the part [sb, se) of long row r (entries [rb, re)) inside the chunk [e0, e1); slot 0: the row holds the chunk's first
-// entry, slot 1: it starts later in the chunk.  A row longer than a chunk that meets the chunk holds its first or last entry.
-struct Segment { int r, rb, re, sb, se; };
-__device__ __forceinline__ bool long_segment(const int* __restrict__ rowptr, int slot, int rh, int rt, int e0, int e1, Segment& s) {
-  if (slot == 1 && rt == rh) return false;
-  s.r = slot ? rt : rh;
-  s.rb = rowptr[s.r];
-  s.re = rowptr[s.r + 1];
-  if (s.re - s.rb <= kLongRow) return false;
-  s.sb = s.rb > e0 ? s.rb : e0;
-  s.se = s.re < e1 ? s.re : e1;
-  return true;
-}
-
+// ---- long rows (find_row, Segment and long_segment: long_chunks.h) --------------------------------------------------------
 template <class Op>
 __global__ void __launch_bounds__(256) agg_long_partial_kernel(Op op, const int* __restrict__ rowptr, int rows, int nnz, int nchunks,
                                                                const int* __restrict__ long_flag, Partial* __restrict__ part) {
@@ -366,7 +339,7 @@ __global__ void __launch_bounds__(256) agg_long_partial_kernel(Op op, const int*
     const int rh = find_row(rowptr, rows, e0, lane), rt = find_row(rowptr, rows, e1 - 1, lane);
     for (int slot = 0; slot < 2; ++slot) {
       Segment sg;
-      if (!long_segment(rowptr, slot, rh, rt, e0, e1, sg)) continue;             // (wave-uniform)
+      if (!long_segment<kLongRow>(rowptr, slot, rh, rt, e0, e1, sg)) continue;   // (wave-uniform)
       State<Op::VEC> s;
       Op::init(s);
       walk(op, sg.sb, sg.se - sg.sb, lane, j, jok, s);
@@ -394,7 +367,7 @@ __global__ void __launch_bounds__(256) agg_long_finish_kernel(Op op, const int* 
     const int rh = find_row(rowptr, rows, e0, lane), rt = find_row(rowptr, rows, e1 - 1, lane);
     for (int slot = 0; slot < 2; ++slot) {
       Segment sg;
-      if (!long_segment(rowptr, slot, rh, rt, e0, e1, sg)) continue;
+      if (!long_segment<kLongRow>(rowptr, slot, rh, rt, e0, e1, sg)) continue;
       // the row's partials: chunks c_first..c_last, the first in slot 1 unless the row starts on the chunk's first entry.
       // One writer per row: the wave whose chunk holds the row's first entry merges them, in chunk order, a column per lane.
       const int c_first = sg.rb / kChunk, c_last = (sg.re - 1) / kChunk;

@@ -16,7 +16,7 @@
 //
 // The unit is subgraph.hip's: ONE ROW PER WORKGROUP, one wave for a row of at most kSampleLongRow entries and four waves
 // (256 threads) for a longer one.  Inside a wave the running count is a ballot and a popcount; the waves of a workgroup
-// exchange their counts of a pass through a double-buffered LDS slot (one barrier per pass).  The row is read twice: once
+// exchange their counts of a pass through ordered_slots (row_dispatch.h: one barrier per pass).  The row is read twice: once
 // for its three counts (heads, entries on the diagonal, heads left of the diagonal) — which give the length, whether a
 // diagonal is inserted and where — and, in the fill, once more to write (from the caches).
 // seg needs no run walk: an entry that is not dropped belongs to the last head at or before it, i.e. to output entry
@@ -25,12 +25,8 @@
 // lane.  Real inputs (an edge list with its mirror, repeated edges of a multigraph) have runs of 1-3 entries; a run of
 // thousands is correct and slow (its lane reads the run entry by entry while the other lanes of the wave wait).
 //
-// Long rows: as in subgraph.hip the wave kernel leaves a row of more than kSampleLongRow entries alone and raises a flag in
-// the workspace; the long kernel (a fixed grid of 256-thread workgroups that returns at once while the flag is down) screens
-// the rows again — workgroup b examines rows b, b + G, ... 256 at a time, a thread each — and gives each long row a whole
-// workgroup.  The dispatch is written again here rather than shared with subgraph.hip / sample.hip, which stay byte for byte
-// what their measurements were taken on; inside this file one dispatch (rows_kernel / long_rows_kernel over an Op) serves
-// the merge, the degrees and the normalisation.
+// Long rows: the dispatch (the wave kernel, the flag, the long kernel's screening of the rows) is row_dispatch.h's, shared
+// with sample.hip and subgraph.hip; the merge, the degrees and the normalisation are three ops over it.
 //
 // ---- degrees and normalisation -------------------------------------------------------------------------------------------------
 // The same decomposition, a wave per row and a 256-thread workgroup per row of more than kSampleLongRow entries, because
@@ -41,77 +37,19 @@
 // at every call.  Normalise: out[x] = (float)(s_r * v * s_c) or (float)(v * t_r) in fp64, a zero degree scales by zero.
 #include <hip/hip_runtime.h>
 
+#include "row_dispatch.h"
 #include "spmm_kernels.h"
 
 namespace gcn {
 namespace {
 
-constexpr int kLongRow = kSampleLongRow;
-constexpr int kLongBlocks = 1024;                      // workgroups of the long-row kernel (they loop over the rows)
-
-template <int THREADS>
-struct Scratch {
-  int wsum[THREADS / 64][3];                           // the waves' counts of a whole row: heads, diagonal entries, heads left of it
-  int cnt[2][THREADS / 64];                            // per pass parity and wave: heads
-  double dsum[THREADS / 64];                           // the waves' partial row sums
-  int is_long[THREADS];                                // the long kernel's row screening
-};
+struct RowRange { int b, e; };
 
 // the row [b, e) of row i, or false when its row pointer is not usable
-__device__ __forceinline__ bool row_range(const int* rowptr, int nnz, int i, int& b, int& e) {
-  b = rowptr[i];
-  e = rowptr[i + 1];
-  return b >= 0 && e >= b && e <= nnz;
-}
-
-// ---- the row dispatch: Op has rowptr, m, nnz and row<THREADS>(i, b, e, L), called by every thread of the workgroup ----------
-template <class Op>
-__global__ void __launch_bounds__(64) rows_kernel(Op op, int* __restrict__ long_flag) {
-  __shared__ Scratch<64> L;
-  const int i = blockIdx.x;
-  int b, e;
-  if (!row_range(op.rowptr, op.nnz, i, b, e)) return;  // (the workgroup's one wave leaves as a whole)
-  if (e - b > kLongRow) {
-    if (long_flag && threadIdx.x == 0) *long_flag = 1; // (every writer writes the same word)
-    return;
-  }
-  op.template row<64>(i, b, e, L);
-}
-
-template <class Op>
-__global__ void __launch_bounds__(256) long_rows_kernel(Op op, const int* __restrict__ long_flag) {
-  __shared__ Scratch<256> L;
-  if (long_flag && *long_flag == 0) return;
-  const int G = gridDim.x;
-  // this workgroup's rows: blockIdx.x + q * G, q = 0, 1, ...; 256 of them are screened at a time, a thread each
-  const int mine = (op.m - (int)blockIdx.x + G - 1) / G;
-  for (int q0 = 0; q0 < mine; q0 += 256) {
-    const int q = q0 + threadIdx.x;
-    int b, e;
-    L.is_long[threadIdx.x] = q < mine && row_range(op.rowptr, op.nnz, blockIdx.x + q * G, b, e) && e - b > kLongRow;
-    __syncthreads();
-    const int top = mine - q0 < 256 ? mine - q0 : 256;
-    for (int t = 0; t < top; ++t) {
-      if (!L.is_long[t]) continue;                     // (workgroup-uniform)
-      const int i = blockIdx.x + (q0 + t) * G;
-      row_range(op.rowptr, op.nnz, i, b, e);
-      op.template row<256>(i, b, e, L);
-      __syncthreads();                                 // (the next row overwrites the waves' counts)
-    }
-    __syncthreads();                                   // (the next screening overwrites is_long)
-  }
-}
-
-// flag: one int of device scratch (zeroed here) or nullptr, in which case the long kernel screens unconditionally
-template <class Op>
-hipError_t launch_rows(const Op& op, int* flag, hipStream_t st) {
-  if (flag)
-    if (hipError_t err = hipMemsetAsync(flag, 0, sizeof(int), st); err != hipSuccess) return err;
-  rows_kernel<Op><<<(unsigned)op.m, 64, 0, st>>>(op, flag);
-  if (hipError_t err = hipGetLastError(); err != hipSuccess) return err;
-  if (op.nnz <= kLongRow) return hipSuccess;           // (no row can be long)
-  long_rows_kernel<Op><<<(unsigned)(op.m < kLongBlocks ? op.m : kLongBlocks), 256, 0, st>>>(op, flag);
-  return hipGetLastError();
+__device__ __forceinline__ bool row_range(const int* rowptr, int nnz, int i, RowRange& r) {
+  r.b = rowptr[i];
+  r.e = rowptr[i + 1];
+  return r.b >= 0 && r.e >= r.b && r.e <= nnz;
 }
 
 // ---- merge ---------------------------------------------------------------------------------------------------------------------
@@ -125,7 +63,7 @@ struct CoalesceArgs {
   float* out_val;
   int* out_first;
   int* seg;
-  int m, n, nnz, reduce, diagonal;
+  int count, n, nnz, reduce, diagonal;                 // count: rows
   float diag_value;
 };
 
@@ -133,6 +71,14 @@ enum : int { kValid = 1, kKept = 2, kHead = 4, kDiag = 8, kLow = 16 };     // wh
 
 template <bool FILL>
 struct CoalesceOp : CoalesceArgs {
+  using Row = RowRange;
+  template <int THREADS>
+  struct Scratch {
+    int wsum[THREADS / 64][3];                         // the waves' counts of a whole row: heads, diagonal entries, heads left of it
+    int cnt[2][THREADS / 64];                          // per pass parity and wave: heads (ordered_slots)
+  };
+  __device__ bool locate(int i, Row& r) const { return row_range(rowptr, nnz, i, r); }
+
   // the value of the run that starts at entry x (column c), folded left to right in fp32
   __device__ __forceinline__ float fold(long long x, int e, int c) const {
     float acc = val[x];
@@ -149,9 +95,10 @@ struct CoalesceOp : CoalesceArgs {
 
   // one row on a workgroup of THREADS threads (every thread of the workgroup calls it with the same arguments)
   template <int THREADS>
-  __device__ __forceinline__ void row(int r, int b, int e, Scratch<THREADS>& L) const {
+  __device__ __forceinline__ void row(int r, const Row& rr, Scratch<THREADS>& L) const {
     constexpr int WAVES = THREADS / 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = rr.b, e = rr.e;
     const int passes = (int)(((long long)e - b + THREADS - 1) / THREADS);
     const bool has_diag = r < n;                       // (a row r >= n has no diagonal column)
     const bool dropping = diagonal == kDiagDrop && has_diag;
@@ -210,18 +157,7 @@ struct CoalesceOp : CoalesceArgs {
         int c = 0;
         const int f = look(p, c);
         const unsigned long long mask = __ballot(f & kHead);
-        int base = run;
-        if constexpr (WAVES > 1) {
-          if (lane == 0) L.cnt[p & 1][wave] = __popcll(mask);
-          __syncthreads();                             // (the other parity is what a wave one pass ahead writes)
-          for (int w = 0; w < WAVES; ++w) {
-            const int k = L.cnt[p & 1][w];
-            if (w < wave) base += k;
-            run += k;
-          }
-        } else {
-          run += __popcll(mask);
-        }
+        const int base = ordered_slots<WAVES>(mask, p, L.cnt, run);
         if (!(f & kValid)) continue;
         const long long x = (long long)b + (long long)p * THREADS + tid;
         // an entry that is kept belongs to the last head at or before it (a kept entry's head is kept: the same column)
@@ -251,12 +187,20 @@ struct DegreeOp {
   const int* rowptr;
   const float* val;
   double* deg;
-  int m, nnz;
+  int count, nnz;                                      // count: rows
+
+  using Row = RowRange;
+  template <int THREADS>
+  struct Scratch {
+    double dsum[THREADS / 64];                         // the waves' partial row sums
+  };
+  __device__ bool locate(int i, Row& r) const { return row_range(rowptr, nnz, i, r); }
 
   template <int THREADS>
-  __device__ __forceinline__ void row(int r, int b, int e, Scratch<THREADS>& L) const {
+  __device__ __forceinline__ void row(int r, const Row& rr, Scratch<THREADS>& L) const {
     constexpr int WAVES = THREADS / 64;
     const int tid = threadIdx.x;
+    const int b = rr.b, e = rr.e;
     if (!val) {                                        // a pattern: the row's length
       if (tid == 0) deg[r] = (double)(e - b);
       return;
@@ -281,12 +225,18 @@ struct NormalizeOp {
   const float* val;
   const double* deg;
   float* out;
-  int m, n, nnz, mode;
+  int count, n, nnz, mode;                             // count: rows
+
+  using Row = RowRange;
+  template <int THREADS>
+  struct Scratch {};
+  __device__ bool locate(int i, Row& r) const { return row_range(rowptr, nnz, i, r); }
 
   static __device__ __forceinline__ double inv_sqrt(double d) { return d == 0.0 ? 0.0 : 1.0 / sqrt(d); }
 
   template <int THREADS>
-  __device__ __forceinline__ void row(int r, int b, int e, Scratch<THREADS>&) const {
+  __device__ __forceinline__ void row(int r, const Row& rr, Scratch<THREADS>&) const {
+    const int b = rr.b, e = rr.e;
     const double d = deg[r];
     const double sr = mode == kNormSym ? inv_sqrt(d) : (d == 0.0 ? 0.0 : 1.0 / d);
     for (long long x = (long long)b + threadIdx.x; x < e; x += THREADS) {

@@ -30,6 +30,7 @@
 
 #include <cmath>
 
+#include "long_chunks.h"
 #include "spmm_kernels.h"
 
 namespace gcn {
@@ -251,21 +252,7 @@ __global__ void __launch_bounds__(256) edge_rows_kernel(Op op, const int* __rest
   }
 }
 
-// ---- long rows ----------------------------------------------------------------------------------------------------------
-// the row holding entry e0 (0 <= e0 < nnz): the largest r < m with rowptr[r] <= e0 — never an empty row.  64 probes a round.
-__device__ __forceinline__ int find_row(const int* __restrict__ rowptr, int m, int e0, int lane) {
-  int lo = 0, hi = m;                                  // rowptr[lo] <= e0, and rowptr[hi] > e0 or hi == m
-  while (hi - lo > 1) {
-    const int step = (hi - lo + 63) >> 6;
-    const long long probe = (long long)lo + (long long)lane * step;
-    const bool le = probe < hi && rowptr[probe] <= e0;
-    const int cnt = __popcll(__ballot(le));            // (rowptr is monotone: the lanes that say yes are a prefix, lane 0 among them)
-    lo += (cnt > 0 ? cnt - 1 : 0) * step;          // (cnt == 0 only with rowptr[0] > 0: a malformed matrix must not index backwards)
-    hi = lo + step < hi ? lo + step : hi;
-  }
-  return lo;
-}
-
+// ---- long rows (find_row, Segment and long_segment: long_chunks.h) --------------------------------------------------------
 __device__ __forceinline__ float block_max(float v, float* sh) {
   v = gmax<64>(v);
   __syncthreads();                                     // (sh may still be read from the reduction before)
@@ -282,20 +269,6 @@ __device__ __forceinline__ T block_sum(T v, T* sh) {
   return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
-// the part [sb, se) of long row r (entries [rb, re)) inside chunk c; slot 0: the row holds the chunk's first entry,
-// slot 1: it starts later in the chunk.  A row longer than a chunk that meets the chunk holds its first or its last entry.
-struct Segment { int r, rb, re, sb, se; };
-__device__ __forceinline__ bool long_segment(const int* __restrict__ rowptr, int slot, int rh, int rt, int e0, int e1, Segment& s) {
-  if (slot == 1 && rt == rh) return false;
-  s.r = slot ? rt : rh;
-  s.rb = rowptr[s.r];
-  s.re = rowptr[s.r + 1];
-  if (s.re - s.rb <= kLongRow) return false;
-  s.sb = s.rb > e0 ? s.rb : e0;
-  s.se = s.re < e1 ? s.re : e1;
-  return true;
-}
-
 template <class Op>
 __global__ void __launch_bounds__(256) edge_long_partial_kernel(Op op, const int* __restrict__ rowptr, int m, int nnz, int nchunks,
                                                                 const int* __restrict__ long_flag, float2* __restrict__ part) {
@@ -309,7 +282,7 @@ __global__ void __launch_bounds__(256) edge_long_partial_kernel(Op op, const int
     const int rh = find_row(rowptr, m, e0, lane), rt = find_row(rowptr, m, e1 - 1, lane);
     for (int slot = 0; slot < 2; ++slot) {
       Segment s;
-      if (!long_segment(rowptr, slot, rh, rt, e0, e1, s)) continue;            // (block-uniform)
+      if (!long_segment<kLongRow>(rowptr, slot, rh, rt, e0, e1, s)) continue;  // (block-uniform)
       const float cx = op.ctx(s.r);
       if constexpr (Op::SOFTMAX) {
         float mx = -INFINITY;
@@ -343,7 +316,7 @@ __global__ void __launch_bounds__(256) edge_long_finish_kernel(Op op, const int*
     const int rh = find_row(rowptr, m, e0, lane), rt = find_row(rowptr, m, e1 - 1, lane);
     for (int slot = 0; slot < 2; ++slot) {
       Segment s;
-      if (!long_segment(rowptr, slot, rh, rt, e0, e1, s)) continue;
+      if (!long_segment<kLongRow>(rowptr, slot, rh, rt, e0, e1, s)) continue;
       // the row's partials: chunks c_first..c_last, the first in slot 1 unless the row starts on the chunk's first entry.
       // Every block of the row merges the same partials in the same order: thread t takes t, t + 256, ..., then the block tree.
       const int c_first = s.rb / kChunk, c_last = (s.re - 1) / kChunk;

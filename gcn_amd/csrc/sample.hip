@@ -28,12 +28,9 @@
 // f - below entries with key == T (the lower entry index wins a tie); the output position is a prefix popcount of
 // ballots, and the four waves of a long row exchange their per-pass counts through LDS.
 //
-// Long rows: the wave kernel leaves a row of more than kSampleLongRow entries alone (selection or copy: the rule looks at
-// the length only) and raises a flag in the workspace.
-// The long kernel (a fixed grid of 256-thread workgroups; it returns at once while the flag is down) looks for those
-// rows again — workgroup b examines seeds b, b + G, b + 2G, ... 256 at a time — and gives each a whole workgroup: a hub
-// row of tens of thousands of entries is 5 sweeps of a few dozen passes, and neighbouring hubs land on different
-// workgroups.  A single row is not spread over several workgroups.
+// Long rows: the dispatch (the wave kernel, the flag, the long kernel's screening of the seeds) is row_dispatch.h's, shared
+// with subgraph.hip and coalesce.hip; the rule looks at the row's length only, selection or copy.  A hub row of tens of
+// thousands of entries is 5 sweeps of a few dozen passes on its workgroup.
 //
 // A seed outside [0, m), a row pointer outside [0, nnz] or an out_rowptr whose row length is not min(d, f) writes nothing.
 #include <hip/hip_runtime.h>
@@ -41,13 +38,11 @@
 #include <climits>
 
 #include "philox.h"
+#include "row_dispatch.h"
 #include "spmm_kernels.h"
 
 namespace gcn {
 namespace {
-
-constexpr int kLongRow = kSampleLongRow;
-constexpr int kLongBlocks = 1024;                      // workgroups of the long-row kernel (they loop over the seeds)
 
 struct SampleArgs {
   const int* rowptr;
@@ -56,17 +51,16 @@ struct SampleArgs {
   const int* out_rowptr;
   int* out_col;
   int* out_eid;
-  int m, nnz, n_seeds, fanout;                         // fanout: INT_MAX = every entry
+  int m, nnz, count, fanout;                           // count: seeds; fanout: INT_MAX = every entry
   unsigned long long seed, offset;
 };
 
 template <int THREADS>
-struct Scratch {
+struct SampleScratch {
   unsigned hist[256];                                  // the radix histogram of one round
   int wsum[THREADS / 64];                              // inclusive scan totals of the waves
   int res[2];                                          // the chosen bin and the count below it
   int cnt[2][THREADS / 64][2];                         // per pass parity and wave: (keys < T, keys == T)
-  int is_long[THREADS];                                // the long kernel's seed screening
 };
 
 __device__ __forceinline__ uint4 entry_keys(const SampleArgs& a, int g) {
@@ -74,23 +68,26 @@ __device__ __forceinline__ uint4 entry_keys(const SampleArgs& a, int g) {
                        make_uint2((uint32_t)a.seed, (uint32_t)(a.seed >> 32)));
 }
 
-// the row [b, e) of seed i, or false when the seed, the row or the output slot is not usable; o = its output offset
-__device__ __forceinline__ bool seed_row(const SampleArgs& a, int i, int& b, int& e, int& o) {
+struct SeedRow { int b, e, o; };                       // the row's entries [b, e) and its output offset
+
+// the row of seed i, or false when the seed, the row or the output slot is not usable
+__device__ __forceinline__ bool seed_row(const SampleArgs& a, int i, SeedRow& r) {
   const int v = a.seeds[i];
   if (v < 0 || v >= a.m) return false;
-  b = a.rowptr[v];
-  e = a.rowptr[v + 1];
-  if (b < 0 || e < b || e > a.nnz) return false;
-  o = a.out_rowptr[i];
-  const int d = e - b, want = d < a.fanout ? d : a.fanout;
-  return o >= 0 && a.out_rowptr[i + 1] - o == want;
+  r.b = a.rowptr[v];
+  r.e = a.rowptr[v + 1];
+  if (r.b < 0 || r.e < r.b || r.e > a.nnz) return false;
+  r.o = a.out_rowptr[i];
+  const int d = r.e - r.b, want = d < a.fanout ? d : a.fanout;
+  return r.o >= 0 && a.out_rowptr[i + 1] - r.o == want;
 }
 
 // one row on a workgroup of THREADS threads (every thread of the workgroup calls it with the same arguments)
 template <int THREADS>
-__device__ __forceinline__ void sample_row(const SampleArgs& a, int b, int e, int o, Scratch<THREADS>& L) {
+__device__ __forceinline__ void sample_row(const SampleArgs& a, const SeedRow& r, SampleScratch<THREADS>& L) {
   constexpr int WAVES = THREADS / 64, BPT = 256 / THREADS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = r.b, e = r.e, o = r.o;
   const int d = e - b, f = a.fanout;
   if (d <= f) {                                        // the whole row
     for (int t = tid; t < d; t += THREADS) {
@@ -157,6 +154,7 @@ __device__ __forceinline__ void sample_row(const SampleArgs& a, int b, int e, in
   const int need = f - below;                          // entries with key == T to take, the first in entry order (>= 1)
 
   // ---- the selected entries, in entry order ----------------------------------------------------------------------------------
+  // (not row_dispatch.h's ordered_slots: a wave's "taken" depends on the running count of ties over the waves before it)
   const unsigned long long before = (1ull << lane) - 1ull;
   int run_out = 0, run_eq = 0;                         // written so far / entries with key == T met so far
   for (int p = 0; p < passes; ++p) {
@@ -221,53 +219,22 @@ __device__ __forceinline__ void sample_row(const SampleArgs& a, int b, int e, in
   }
 }
 
-__global__ void __launch_bounds__(64) sample_rows_kernel(SampleArgs a, int* __restrict__ long_flag) {
-  __shared__ Scratch<64> L;
-  const int i = blockIdx.x;
-  int b, e, o;
-  if (!seed_row(a, i, b, e, o)) return;                // (the workgroup's one wave leaves as a whole)
-  if (e - b > kLongRow) {
-    if (threadIdx.x == 0) *long_flag = 1;              // (every writer writes the same word)
-    return;
-  }
-  sample_row<64>(a, b, e, o, L);
-}
-
-__global__ void __launch_bounds__(256) sample_long_kernel(SampleArgs a, const int* __restrict__ long_flag) {
-  __shared__ Scratch<256> L;
-  if (*long_flag == 0) return;
-  const int G = gridDim.x;
-  // this workgroup's seeds: blockIdx.x + q * G, q = 0, 1, ...; 256 of them are screened at a time, a thread each
-  const int mine = (a.n_seeds - (int)blockIdx.x + G - 1) / G;
-  for (int q0 = 0; q0 < mine; q0 += 256) {
-    const int q = q0 + threadIdx.x;
-    int b, e, o;
-    L.is_long[threadIdx.x] = q < mine && seed_row(a, blockIdx.x + q * G, b, e, o) && e - b > kLongRow;
-    __syncthreads();
-    const int top = mine - q0 < 256 ? mine - q0 : 256;
-    for (int t = 0; t < top; ++t) {
-      if (!L.is_long[t]) continue;                     // (workgroup-uniform)
-      seed_row(a, blockIdx.x + (q0 + t) * G, b, e, o);
-      sample_row<256>(a, b, e, o, L);
-      __syncthreads();                                 // (the next row zeroes the histogram)
-    }
-    __syncthreads();                                   // (the next screening overwrites is_long)
-  }
-}
+struct SampleOp : SampleArgs {
+  using Row = SeedRow;
+  template <int THREADS>
+  using Scratch = SampleScratch<THREADS>;
+  __device__ bool locate(int i, Row& r) const { return seed_row(*this, i, r); }
+  template <int THREADS>
+  __device__ __forceinline__ void row(int, const Row& r, Scratch<THREADS>& L) const { sample_row<THREADS>(*this, r, L); }
+};
 
 }  // namespace
 
 hipError_t launch_sample_neighbors(const int* rowptr, const int* col, int m, int nnz, const int* seeds, int n_seeds, int fanout,
                                    unsigned long long seed, unsigned long long offset, const int* out_rowptr, int* out_col,
                                    int* out_eid, void* ws, hipStream_t st) {
-  int* flag = static_cast<int*>(ws);
-  const SampleArgs a{rowptr, col, seeds, out_rowptr, out_col, out_eid, m, nnz, n_seeds, fanout < 0 ? INT_MAX : fanout, seed, offset};
-  if (hipError_t err = hipMemsetAsync(flag, 0, sizeof(int), st); err != hipSuccess) return err;
-  sample_rows_kernel<<<(unsigned)n_seeds, 64, 0, st>>>(a, flag);
-  if (hipError_t err = hipGetLastError(); err != hipSuccess) return err;
-  if (nnz <= kLongRow) return hipSuccess;              // (no row can be long)
-  sample_long_kernel<<<(unsigned)(n_seeds < kLongBlocks ? n_seeds : kLongBlocks), 256, 0, st>>>(a, flag);
-  return hipGetLastError();
+  const SampleOp op{{rowptr, col, seeds, out_rowptr, out_col, out_eid, m, nnz, n_seeds, fanout < 0 ? INT_MAX : fanout, seed, offset}};
+  return launch_rows(op, static_cast<int*>(ws), st);
 }
 
 }  // namespace gcn

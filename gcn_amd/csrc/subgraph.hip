@@ -15,18 +15,15 @@
 // average) are a few wave-widths long and a row's output positions are a running count over the row: inside a wave that
 // count is a ballot and a popcount, with no barrier and no atomic.  A pass covers THREADS consecutive entries, lane-major
 // (coalesced reads of col; the gather from vmap is the scattered part), a lane keeps its entry iff vmap[col[e]] >= 0, and
-// the output position is the count of the passes before + the counts of the lower waves of this pass (exchanged through a
-// double-buffered LDS slot: one barrier per pass) + the popcount of the ballot below the lane.
+// the output position is the count of the passes before + the counts of the lower waves of this pass (ordered_slots in
+// row_dispatch.h: one barrier per pass) + the popcount of the ballot below the lane.
 // FILL first counts the row again and compares the count with the length of the caller's slot (a slot of another length
 // writes nothing: the contract), then writes.  The map values of the first kKeep passes stay in registers, so a row of at
 // most kKeep * 64 = 256 entries on a wave reads col and vmap once; a longer row reads them a second time (from the caches).
 //
-// Long rows: as in sample.hip the wave kernel leaves a row of more than kSampleLongRow entries alone and raises a flag in
-// the workspace; the long kernel (a fixed grid of 256-thread workgroups that returns at once while the flag is down)
-// screens the nodes again — workgroup b examines nodes b, b + G, ... 256 at a time, a thread each — and gives each long row
-// a whole workgroup.  A single row is not spread over several workgroups.  (The decomposition is sample.hip's and the few
-// lines of dispatch are written again here rather than shared: the two row functions have nothing else in common — no keys,
-// no histogram, another scratch layout — and sample.hip stays byte for byte what its measurements were taken on.)
+// Long rows: the dispatch (the wave kernel, the flag, the long kernel's screening of the nodes) is row_dispatch.h's, shared
+// with sample.hip and coalesce.hip; the row functions have nothing else in common with sample.hip's — no keys, no histogram,
+// another scratch layout.
 //
 // A node outside [0, m), a row pointer outside [0, nnz] or (FILL) a slot whose length is not the row's count writes nothing.
 //
@@ -48,13 +45,12 @@
 #include <hip/hip_runtime.h>
 
 #include "philox.h"
+#include "row_dispatch.h"
 #include "spmm_kernels.h"
 
 namespace gcn {
 namespace {
 
-constexpr int kLongRow = kSampleLongRow;
-constexpr int kLongBlocks = 1024;                      // workgroups of the long-row kernel (they loop over the nodes)
 constexpr int kKeep = 4;                               // passes whose map values stay in registers between count and fill
 
 struct InduceArgs {
@@ -66,30 +62,32 @@ struct InduceArgs {
   const int* out_rowptr;                               // FILL
   int* out_col;
   int* out_eid;
-  int m, nnz, n_nodes;
+  int m, nnz, count;                                   // count: nodes
 };
 
 template <int THREADS>
-struct Scratch {
+struct InduceScratch {
   int wsum[THREADS / 64];                              // the waves' counts of a whole row
-  int cnt[2][THREADS / 64];                            // per pass parity and wave: kept entries
-  int is_long[THREADS];                                // the long kernel's node screening
+  int cnt[2][THREADS / 64];                            // per pass parity and wave: kept entries (ordered_slots)
 };
 
+struct NodeRow { int b, e; };
+
 // the row [b, e) of node i, or false when the node or the row is not usable
-__device__ __forceinline__ bool node_row(const InduceArgs& a, int i, int& b, int& e) {
+__device__ __forceinline__ bool node_row(const InduceArgs& a, int i, NodeRow& r) {
   const int v = a.nodes[i];
   if (v < 0 || v >= a.m) return false;
-  b = a.rowptr[v];
-  e = a.rowptr[v + 1];
-  return b >= 0 && e >= b && e <= a.nnz;
+  r.b = a.rowptr[v];
+  r.e = a.rowptr[v + 1];
+  return r.b >= 0 && r.e >= r.b && r.e <= a.nnz;
 }
 
 // one row on a workgroup of THREADS threads (every thread of the workgroup calls it with the same arguments)
 template <int THREADS, bool FILL>
-__device__ __forceinline__ void induce_row(const InduceArgs& a, int i, int b, int e, Scratch<THREADS>& L) {
+__device__ __forceinline__ void induce_row(const InduceArgs& a, int i, const NodeRow& r, InduceScratch<THREADS>& L) {
   constexpr int WAVES = THREADS / 64;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = r.b, e = r.e;
   const int passes = (int)(((long long)e - b + THREADS - 1) / THREADS);
   auto local_of = [&](int p) {                         // the map value of this thread's entry of pass p, -1 past the row
     const long long x = (long long)b + (long long)p * THREADS + tid;
@@ -124,19 +122,7 @@ __device__ __forceinline__ void induce_row(const InduceArgs& a, int i, int b, in
     int run = 0;                                       // written by the passes so far
     auto pass = [&](int p, int loc) {
       const unsigned long long mask = __ballot(loc >= 0);
-      int base = run;
-      if constexpr (WAVES > 1) {
-        if (lane == 0) L.cnt[p & 1][wave] = __popcll(mask);
-        __syncthreads();                               // (the other parity is what a wave one pass ahead writes)
-        for (int w = 0; w < WAVES; ++w) {
-          const int c = L.cnt[p & 1][w];
-          if (w < wave) base += c;
-          run += c;
-        }
-      } else {
-        run += __popcll(mask);
-      }
-      const int pos = base + __popcll(mask & before);
+      const int pos = ordered_slots<WAVES>(mask, p, L.cnt, run) + __popcll(mask & before);
       if (loc >= 0 && pos < total) {                   // (pos < total always: exactly total entries are kept)
         a.out_col[o + pos] = loc;
         a.out_eid[o + pos] = b + p * THREADS + tid;
@@ -150,52 +136,14 @@ __device__ __forceinline__ void induce_row(const InduceArgs& a, int i, int b, in
 }
 
 template <bool FILL>
-__global__ void __launch_bounds__(64) induce_rows_kernel(InduceArgs a, int* __restrict__ long_flag) {
-  __shared__ Scratch<64> L;
-  const int i = blockIdx.x;
-  int b, e;
-  if (!node_row(a, i, b, e)) return;                   // (the workgroup's one wave leaves as a whole)
-  if (e - b > kLongRow) {
-    if (threadIdx.x == 0) *long_flag = 1;              // (every writer writes the same word)
-    return;
-  }
-  induce_row<64, FILL>(a, i, b, e, L);
-}
-
-template <bool FILL>
-__global__ void __launch_bounds__(256) induce_long_kernel(InduceArgs a, const int* __restrict__ long_flag) {
-  __shared__ Scratch<256> L;
-  if (*long_flag == 0) return;
-  const int G = gridDim.x;
-  // this workgroup's nodes: blockIdx.x + q * G, q = 0, 1, ...; 256 of them are screened at a time, a thread each
-  const int mine = (a.n_nodes - (int)blockIdx.x + G - 1) / G;
-  for (int q0 = 0; q0 < mine; q0 += 256) {
-    const int q = q0 + threadIdx.x;
-    int b, e;
-    L.is_long[threadIdx.x] = q < mine && node_row(a, blockIdx.x + q * G, b, e) && e - b > kLongRow;
-    __syncthreads();
-    const int top = mine - q0 < 256 ? mine - q0 : 256;
-    for (int t = 0; t < top; ++t) {
-      if (!L.is_long[t]) continue;                     // (workgroup-uniform)
-      const int i = blockIdx.x + (q0 + t) * G;
-      node_row(a, i, b, e);
-      induce_row<256, FILL>(a, i, b, e, L);
-      __syncthreads();                                 // (the next row overwrites the waves' counts)
-    }
-    __syncthreads();                                   // (the next screening overwrites is_long)
-  }
-}
-
-template <bool FILL>
-hipError_t launch_induce(const InduceArgs& a, void* ws, hipStream_t st) {
-  int* flag = static_cast<int*>(ws);
-  if (hipError_t err = hipMemsetAsync(flag, 0, sizeof(int), st); err != hipSuccess) return err;
-  induce_rows_kernel<FILL><<<(unsigned)a.n_nodes, 64, 0, st>>>(a, flag);
-  if (hipError_t err = hipGetLastError(); err != hipSuccess) return err;
-  if (a.nnz <= kLongRow) return hipSuccess;            // (no row can be long)
-  induce_long_kernel<FILL><<<(unsigned)(a.n_nodes < kLongBlocks ? a.n_nodes : kLongBlocks), 256, 0, st>>>(a, flag);
-  return hipGetLastError();
-}
+struct InduceOp : InduceArgs {
+  using Row = NodeRow;
+  template <int THREADS>
+  using Scratch = InduceScratch<THREADS>;
+  __device__ bool locate(int i, Row& r) const { return node_row(*this, i, r); }
+  template <int THREADS>
+  __device__ __forceinline__ void row(int i, const Row& r, Scratch<THREADS>& L) const { induce_row<THREADS, FILL>(*this, i, r, L); }
+};
 
 struct WalkArgs {
   const int* rowptr;
@@ -238,15 +186,15 @@ __global__ void __launch_bounds__(64) random_walk_kernel(WalkArgs a) {
 
 hipError_t launch_induced_subgraph_count(const int* rowptr, const int* col, int m, int nnz, const int* nodes, int n_nodes,
                                          const int* vmap, int* out_len, void* ws, hipStream_t st) {
-  const InduceArgs a{rowptr, col, nodes, vmap, out_len, nullptr, nullptr, nullptr, m, nnz, n_nodes};
-  return launch_induce<false>(a, ws, st);
+  const InduceOp<false> op{{rowptr, col, nodes, vmap, out_len, nullptr, nullptr, nullptr, m, nnz, n_nodes}};
+  return launch_rows(op, static_cast<int*>(ws), st);
 }
 
 hipError_t launch_induced_subgraph_fill(const int* rowptr, const int* col, int m, int nnz, const int* nodes, int n_nodes,
                                         const int* vmap, const int* out_rowptr, int* out_col, int* out_eid, void* ws,
                                         hipStream_t st) {
-  const InduceArgs a{rowptr, col, nodes, vmap, nullptr, out_rowptr, out_col, out_eid, m, nnz, n_nodes};
-  return launch_induce<true>(a, ws, st);
+  const InduceOp<true> op{{rowptr, col, nodes, vmap, nullptr, out_rowptr, out_col, out_eid, m, nnz, n_nodes}};
+  return launch_rows(op, static_cast<int*>(ws), st);
 }
 
 hipError_t launch_random_walk(const int* rowptr, const int* col, int m, int nnz, const int* starts, int n_walks, int length,
