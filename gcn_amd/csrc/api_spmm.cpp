@@ -53,13 +53,8 @@ struct Epilogue {                                      // C = dropout(act(A*B + 
 int run_group_walk(gcn_spmm_plan* p, const SliceSet& ss, bool weighted, const void* table, int elem_bytes, int ld, int k,
                    hipEvent_t ev0, hipEvent_t ev1, hipStream_t st, CutLists* cuts) {
   const GroupStream& G = *ss.g;
-  GroupArgs ga;
-  ga.stream = G.stream; ga.chunk_meta = G.chunk_meta;
-  ga.vals = weighted ? G.vals.get() : nullptr;
-  ga.Bp = table; ga.elem_bytes = elem_bytes; ga.Cv = p->cv; ga.P = p->ws;
-  ga.nchunks = G.nchunks; ga.T = G.T; ga.k = k; ga.ldb = ld;
-  ga.table_rows = ss.table_rows();
-  ga.narrow8 = group8_enabled() ? 1 : 0;
+  GroupArgs ga = group_shape(ss, weighted, elem_bytes, ld, k);
+  ga.Bp = table; ga.Cv = p->cv; ga.P = p->ws;
   if (ev0 && hipEventRecord(ev0, st) != hipSuccess) return GCN_ERR_HIP;
   if (launch_spmm_group(ga, st) != hipSuccess) return GCN_ERR_HIP;
   if (ev1 && hipEventRecord(ev1, st) != hipSuccess) return GCN_ERR_HIP;

@@ -2,9 +2,11 @@
 // stream; spmm_group.hip says why and how), written once for both table formats.  A row format says what the 16 bytes one
 // lane gathers mean — RowF32: 4 fp32 columns of a 64-column tile; RowBf16: 8 bf16 columns of a 128-column tile, widened by
 // shift / mask (a bf16 is the top half of an fp32) — everything else is the same code: the (tile, block) order inside the
-// merged launch, the chunk assignment per XCD, the chunk_meta decode and BIG, the lane-major stream with the value words a
-// run ahead, the DPP broadcast of the row offset, the row-end ballot, the LDS ring with its four drain cases and the
-// piece that sticks out of a chunk.  Every sum is fp32; partial rows go to the fp32 slab Cv / P whatever the table holds.
+// merged launch, the lane-major stream with the value words a run ahead, the DPP broadcast of the row offset, the row-end
+// ballot.  What stands around the chunk loop — the chunk assignment per XCD, the chunk_meta decode and BIG (GroupChunk),
+// the LDS ring with its drains and the piece that sticks out of a chunk (RowSink) — is written for an engine geometry:
+// GroupChunk serves the eight- and five-engine walks of spmm_group.hip as well, RowSink the eight-engine one.  Every sum
+// is fp32; partial rows go to the fp32 slab Cv / P whatever the table holds.
 // Device code only: included by spmm_group.hip (fp32 instantiations) and spmm_group_bf16.hip (bf16 instantiations).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -130,6 +132,143 @@ __device__ __forceinline__ TileBlock group_tile_block(int block, int blocks_per_
 // bits, per lane, and only the offset INSIDE the slice (< 32 768 rows x < 128 KiB) stays in 32 bits — one more vector
 // instruction per gather (add + carry instead of one add).  Without it the 32-bit byte offset (entry + base) * row_bytes
 // would wrap silently.
+
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+// bit u of every group's LANES bits of a ballot, at u = 0
+template <int GROUPS, int LANES>
+constexpr unsigned long long group_bits() {
+  unsigned long long m = 0;
+  for (int g = 0; g < GROUPS; ++g) m |= 1ull << (g * LANES);
+  return m;
+}
+// stream_nt (streams too large to stay cached from one SpMM to the next, group_grid): non-temporal loads
+// keep them from displacing the table — 2.94 -> 2.87 ms per SpMM on the 232 MB stream of the Reddit-shaped
+// graph (profiles/r02zn_*); a stream that fits the caches is better left there (profiles/r02zo_*)
+template <class V>
+__device__ __forceinline__ V stream_load(const V* p, int stream_nt) { return stream_nt ? __builtin_nontemporal_load(p) : *p; }
+// Where this lane's group starts: its chunk, the lane's columns, what the chunk's meta word says.  A wave owns GROUPS
+// consecutive chunks of its XCD's range, a block 4 * GROUPS.  GROUPS * LANES == 64: the range is whole waves (the stream's
+// padding; spmm_group_choice for eight).  Fewer lanes: the groups past the range and the spare lanes walk the wave's
+// first chunk along (loads only) and store nothing — live says which.  Use: construct (arithmetic only), leave if none(),
+// then open() reads the meta word — two steps, because behind a returned flag the compiler closes the divergent region and
+// opens it again, and the stream's first loads wait for the meta word.
+template <class Row, int GROUPS, int LANES, bool BIG>
+struct GroupChunk {
+  static constexpr bool kWholeWaves = GROUPS * LANES == 64;
+  int lane, wib, g, f;            // f: which 16 bytes of the tile's row this lane gathers
+  int per_xcd, c_w, c, fcol;      // chunks of an XCD; the wave's first chunk inside that range; the chunk; the lane's first column
+  bool live, col_ok, head;        // col_ok: the lane's columns exist; head: the chunk's first row began in an earlier chunk
+  unsigned row_bytes, foff;       // foff: byte offset of the lane's columns in a table row
+  int base;                       // first row of the chunk's slice in the table (BIG: 0, it is in Bb)
+  const char* Bb;
+  size_t kk;                      // floats between rows of Cv / P
+  float *ptr, *nptr;              // where the current row goes, and the next one
+
+  // dyn (drop-in flexspmm only; else nullptr): {buffers recognised, chunk count} written by dropin_guard_kernel — the grid
+  // was sized from an upper bound, and buffers this library did not pack are not walked (no chunks: every wave leaves)
+  __device__ __forceinline__ GroupChunk(const void* __restrict__ table, int nchunks, const int* __restrict__ dyn, int bx,
+                                        int col_tile, int k, size_t kk_, int ld) {
+    if (dyn) nchunks = dyn[0] ? dyn[1] : 0;
+    lane = threadIdx.x & 63;
+    wib  = threadIdx.x >> 6;
+    g    = lane / LANES;
+    f    = lane - g * LANES;
+    per_xcd = nchunks >> 3;
+    c_w = ((bx >> 3) * 4 + wib) * GROUPS;
+    live = kWholeWaves || (g < GROUPS && c_w + g < per_xcd);
+    c = (bx & 7) * per_xcd + (live ? c_w + g : c_w);
+    fcol = col_tile * Row::kTileCols + f * Row::kLaneCols;
+    col_ok = fcol < k;
+    row_bytes = (unsigned)ld * (unsigned)Row::kElemBytes;
+    foff = (unsigned)(col_ok ? fcol : col_tile * Row::kTileCols) * (unsigned)Row::kElemBytes;
+    Bb = reinterpret_cast<const char*>(table);
+    kk = kk_;
+  }
+  __device__ __forceinline__ bool none() const { return c_w >= per_xcd; }
+  __device__ __forceinline__ void open(const int2* __restrict__ chunk_meta, float* __restrict__ Cv, float* __restrict__ P) {
+    const int2 meta = chunk_meta[c];                              // one load: nothing else stands before the first gather
+    const int vrow = meta.x >> 1;                                 // virtual row holding the chunk's first entry
+    head = meta.x & 1;
+    base = BIG ? 0 : meta.y;
+    if constexpr (BIG) Bb += (size_t)meta.y * (size_t)row_bytes;  // (per lane: the groups of a wave can sit in different slices)
+    ptr  = head ? P + (size_t)(2 * c) * kk + fcol : Cv + (size_t)vrow * kk + fcol;
+    nptr = Cv + (size_t)(vrow + 1) * kk + fcol;
+  }
+};
+
+// RING: finished rows wait in LDS, GROUPS slots per group, and leave GROUPS at a time — consecutive rows of ONE group,
+// written by the whole wave with one 64-lane pass (a store occupies the addressers like a gather whatever its width).
+// 16 or 32 KiB per block.  Indexed [wave][group][slot][lane] in place: through a reference to the wave's part the
+// address arithmetic of a drain comes out differently.
+template <class Row, int GROUPS, int LANES, bool RING>
+__device__ __forceinline__ auto& block_ring() {
+  __shared__ RowPieces<Row> ring[RING ? 4 : 1][GROUPS][GROUPS][LANES];
+  return ring;
+}
+
+// Where the rows of this lane's group go (GROUPS * LANES == 64; the five-engine walk keeps its own text).
+// A row that ends goes into the ring — unless it is the chunk's head piece or the ring is full, then straight to memory;
+// full rings are drained after every block that ended a row, the rest after the loop.
+template <class Row, int GROUPS, int LANES, bool RING>
+struct RowSink {
+  typedef RowPieces<Row> Ring[RING ? 4 : 1][GROUPS][GROUPS][LANES];
+  Ring& ring;
+  const int wib;
+  float *ptr, *nptr;
+  float* ring_base = nullptr;     // the first row waiting in the ring goes here (the next ones kk further each)
+  const size_t kk;
+  int ring_n = 0;                 // rows of this lane's group waiting in the ring
+  const int g, f;
+  bool first = true;              // no row of this chunk has ended yet
+  const bool head, col_ok;
+
+  template <bool BIG>
+  __device__ __forceinline__ RowSink(const GroupChunk<Row, GROUPS, LANES, BIG>& ch, Ring& r)
+      : ring(r), wib(ch.wib), ptr(ch.ptr), nptr(ch.nptr), kk(ch.kk), g(ch.g), f(ch.f), head(ch.head), col_ok(ch.col_ok) {}
+
+  // the current row of this lane's group has ended with the sum r
+  __device__ __forceinline__ void finish(const RowPieces<Row>& r) {
+    if (RING && !(first && head) && ring_n < GROUPS) {
+      if (col_ok) ring[wib][g][ring_n][f] = r;
+      if (ring_n == 0) ring_base = ptr;
+      ++ring_n;
+    } else if (col_ok) store_row_pieces<Row>(ptr, r);
+    ptr = nptr; nptr += kk; first = false;
+  }
+  // the rows waiting in group G2's ring (ALL: it is full): lane l writes the piece of lane l % LANES of row l / LANES.
+  // The LDS read stands in front of the test: inside it the bf16 kernel ran 2-3 % slower (profiles/r14_drain_read_variants.json)
+  template <bool ALL>
+  __device__ __forceinline__ void drain(int G2) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(uintptr_t)ring_base, LANES * G2);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)((uintptr_t)ring_base >> 32), LANES * G2);
+    float* b0 = reinterpret_cast<float*>(((uintptr_t)hi << 32) | lo);
+    const RowPieces<Row> rv = ring[wib][G2][g][f];
+    if (col_ok && g < (ALL ? GROUPS : __builtin_amdgcn_readlane(ring_n, LANES * G2)))
+      store_row_pieces<Row>(b0 + (size_t)g * kk + f * Row::kLaneCols, rv);
+    if (g == G2) ring_n = 0;
+  }
+  template <bool ALL>
+  __device__ __forceinline__ void drain_flagged(unsigned long long flags) {   // bit LANES * G2: group G2's ring
+#pragma unroll
+    for (int G2 = 0; G2 < GROUPS; ++G2)
+      if (flags & (1ull << (LANES * G2))) drain<ALL>(G2);
+  }
+  __device__ __forceinline__ void drain_full() {
+    if constexpr (RING) { const unsigned long long full = __ballot(ring_n == GROUPS); if (full) drain_flagged<true>(full); }
+  }
+  __device__ __forceinline__ void drain_rest() { if constexpr (RING) drain_flagged<false>(__ballot(ring_n > 0)); }
+  // the row piece that sticks out of the chunk's end (the last entry did not end its row): it is the FIRST piece of its
+  // row — unless the whole chunk lies inside one row, then it is this chunk's head piece — and goes where the row's
+  // partial sum lives, Cv[row]; the pieces of the chunks the row runs on into (their head pieces, P[2c]) are added by
+  // the slice reduction (cut lists) or by group_fixup_kernel
+  __device__ __forceinline__ void tail(bool row_open, const RowPieces<Row>& r) {
+    if (row_open) {
+      if (col_ok) store_row_pieces<Row>(ptr, r);
+    }
+  }
+};
+
 template <class Row, bool VALS, bool RING, bool BIG>
 __device__ __forceinline__ void
 group_walk(const unsigned short* __restrict__ stream, const float* __restrict__ vals, const int2* __restrict__ chunk_meta,
@@ -137,74 +276,34 @@ group_walk(const unsigned short* __restrict__ stream, const float* __restrict__ 
            int nchunks, int T, int k, int seg_blocks, int ld, int stream_nt, int blocks_per_tile, const int* __restrict__ dyn) {
   // T: entries per chunk of ONE group, a multiple of 64 (a chunk is whole runs of four blocks) — a run-time value: the
   // plan picks it so that the blocks fill whole rounds of the chip on small matrices (group_chunk, plan_policy.cpp)
-  // dyn (drop-in flexspmm only, an fp32 matter; else nullptr): {buffers recognised, chunk count} written by
-  // dropin_guard_kernel — the grid was sized from an upper bound of the chunk count, and buffers this library did not
-  // pack are not walked at all
-  if (dyn) { if (dyn[0] == 0) return; nchunks = dyn[1]; }
-  constexpr int LC = Row::kLaneCols, TC = Row::kTileCols;
-  const int lane = threadIdx.x & 63;
-  const int wib  = threadIdx.x >> 6;
-  const int g    = lane >> 4;
-  const int f    = lane & 15;
-  const int per_xcd = nchunks >> 3;
+  constexpr int TC = Row::kTileCols;
   const TileBlock tb = group_tile_block<TC>((int)blockIdx.x, blocks_per_tile, seg_blocks, k);
-  const int col_tile = tb.col_tile, bx = tb.bx;
-  const int c_in = ((bx >> 3) * 4 + wib) * 4;
-  if (c_in >= per_xcd) return;                                  // (whole wave: per_xcd % 4 == 0)
-  const int c = (bx & 7) * per_xcd + c_in + g;                  // this group's chunk
-
-  const int fcol = col_tile * TC + f * LC;
-  const bool fok = fcol < k;
-  const unsigned row_bytes = (unsigned)ld * (unsigned)Row::kElemBytes;
-  const unsigned foff = (unsigned)(fok ? fcol : col_tile * TC) * (unsigned)Row::kElemBytes;
-  const char* Bb = reinterpret_cast<const char*>(table);
-  const size_t kk = (GCN_ABLATE & 8) ? (size_t)TC : (size_t)k;  // (bit 3: partial rows of a tile contiguous — a layout experiment)
-
-  const int2 meta = chunk_meta[c];                              // one load: nothing else stands before the first gather
-  const int vrow = meta.x >> 1;                                 // virtual row holding the chunk's first entry
-  const bool head = meta.x & 1;                                 // ... which began in an earlier chunk
-  const int base = BIG ? 0 : meta.y;                            // first row of this chunk's slice in the table
-  if constexpr (BIG) Bb += (size_t)meta.y * (size_t)row_bytes;  // (per lane: the groups of a wave can sit in different slices)
-  float* ptr  = head ? P + (size_t)(2 * c) * kk + fcol : Cv + (size_t)vrow * kk + fcol;
-  float* nptr = Cv + (size_t)(vrow + 1) * kk + fcol;
-  bool first = true;                                            // no row of this chunk has ended yet
-  // RING: finished rows wait in LDS, four slots per group, and leave four at a time — consecutive rows of ONE group,
-  // written by the whole wave with one 64-lane pass instead of four 16-lane ones (a store occupies the addressers
-  // like a gather whatever its width).  16 KiB per block for fp32 rows, 32 KiB for bf16 ones (32 bytes per lane).
-  __shared__ RowPieces<Row> ring[RING ? 4 : 1][4][4][16];
-  int ring_n = 0;                                               // rows of this lane's group waiting in the ring
-  float* ring_base = nullptr;                                   // ... the first of them goes here (the next ones kk further each)
-#define GCN_G_DRAIN(G2, ROWS)                                                                       \
-  {                                                                                                 \
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(uintptr_t)ring_base, 16 * G2);    \
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)((uintptr_t)ring_base >> 32), 16 * G2); \
-    float* b0 = reinterpret_cast<float*>(((uintptr_t)hi << 32) | lo);                              \
-    const RowPieces<Row> rv = ring[wib][G2][lane >> 4][f];                                          \
-    if (fok && (lane >> 4) < (ROWS)) store_row_pieces<Row>(b0 + (size_t)(lane >> 4) * kk + f * LC, rv); \
-    if (g == G2) ring_n = 0;                                                                        \
-  }
+  // (GCN_ABLATE bit 3: partial rows of a tile contiguous — a layout experiment)
+  GroupChunk<Row, 4, 16, BIG> ch(table, nchunks, dyn, tb.bx, tb.col_tile, k, (GCN_ABLATE & 8) ? (size_t)TC : (size_t)k, ld);
+  if (ch.none()) return;
+  ch.open(chunk_meta, Cv, P);
+  RowSink<Row, 4, 16, RING> sink(ch, block_ring<Row, 4, 16, RING>());
+  const int f = ch.f, base = ch.base;
+  const unsigned row_bytes = ch.row_bytes, foff = ch.foff;
+  const char* Bb = ch.Bb;
 
   // the stream is stored in runs of 64 entries, lane-major (slicing.hip, group_phys): lane f reads its entries of
   // four consecutive blocks with one 8-byte load (16 bytes for the values)
-  typedef unsigned int u32x2_g __attribute__((ext_vector_type(2)));
-  const u32x2_g* __restrict__ sp = reinterpret_cast<const u32x2_g*>(stream + (size_t)c * T) + f;
-  const f32x4* __restrict__ vp = VALS ? reinterpret_cast<const f32x4*>(vals + (size_t)c * T) + f : nullptr;
+  const u32x2* __restrict__ sp = reinterpret_cast<const u32x2*>(stream + (size_t)ch.c * T) + f;
+  // (GCN_ABLATE bit 4: every chunk reads the values of the first one, 1 KiB)
+  const f32x4* __restrict__ vp = VALS ? reinterpret_cast<const f32x4*>(vals + ((GCN_ABLATE & 16) ? 0 : (size_t)ch.c * T)) + f : nullptr;
   typename Row::Unit acc[4] = {};
-  // stream_nt (streams too large to stay cached from one SpMM to the next, group_grid): non-temporal loads
-  // keep them from displacing the table — 2.94 -> 2.87 ms per SpMM on the 232 MB stream of the Reddit-shaped
-  // graph (profiles/r02zn_*); a stream that fits the caches is better left there (profiles/r02zo_*)
-  u32x2_g eq = stream_nt ? __builtin_nontemporal_load(sp) : sp[0], eq_nx = eq;
+  u32x2 eq = stream_load(sp, stream_nt), eq_nx = eq;
   f32x4 vq = {0.f, 0.f, 0.f, 0.f}, vq_nx = vq;
-  if constexpr (VALS) { vq = (GCN_ABLATE & 16) ? (reinterpret_cast<const f32x4*>(vals) + f)[0] : (stream_nt ? __builtin_nontemporal_load(vp) : vp[0]); vq_nx = vq; }
+  if constexpr (VALS) { vq = (GCN_ABLATE & 16) ? vp[0] : stream_load(vp, stream_nt); vq_nx = vq; }
   unsigned fl = 0;
 #pragma unroll 1
   for (int blk = 0; blk < T / 16; ++blk) {
     const int j = blk & 3;
     if (j == 0 && blk + 4 < T / 16 && !(GCN_ABLATE & 4)) {      // the next run, a whole run ahead of its use
       const int nx = (blk / 4 + 1) * 16;
-      eq_nx = stream_nt ? __builtin_nontemporal_load(sp + nx) : sp[nx];
-      if constexpr (VALS) vq_nx = (GCN_ABLATE & 16) ? (reinterpret_cast<const f32x4*>(vals) + f)[nx & 63]   /* every chunk the same 1 KiB */
-                                                    : (stream_nt ? __builtin_nontemporal_load(vp + nx) : vp[nx]);
+      eq_nx = stream_load(sp + nx, stream_nt);
+      if constexpr (VALS) vq_nx = (GCN_ABLATE & 16) ? vp[nx & 63] : stream_load(vp + nx, stream_nt);
     }
     const unsigned e = ((j & 2 ? eq.y : eq.x) >> (16 * (j & 1))) & 0xFFFFu;
     int vbits = 0;                                              // this lane's entry's value; step u takes lane u's
@@ -237,47 +336,21 @@ group_walk(const unsigned short* __restrict__ stream, const float* __restrict__ 
     } else {
 #define GCN_G_STEP(UU)                                                                              \
       GCN_G_ADD(UU)                                                                                 \
-      if (ends & (0x0001000100010001ull << UU)) {                /* some group ends a row here */    \
+      if (ends & (group_bits<4, 16>() << UU)) {                  /* some group ends a row here */    \
         if (row_bcast<UU>((int)fl)) {                                                               \
-          if (RING && !(first && head) && ring_n < 4) {                                             \
-            if (fok) ring[wib][g][ring_n][f] = row_pieces<Row>(acc);             \
-            if (ring_n == 0) ring_base = ptr;                                                       \
-            ++ring_n;                                                                               \
-          } else if (fok) store_row_pieces<Row>(ptr, row_pieces<Row>(acc));      \
+          sink.finish(row_pieces<Row>(acc));                                                        \
           _Pragma("unroll") for (int i = 0; i < 4; ++i) acc[i] = typename Row::Unit{};              \
-          ptr = nptr; nptr += kk; first = false;                                                    \
         }                                                                                           \
       }
       GCN_G_ALL(GCN_G_STEP)
 #undef GCN_G_STEP
-      if constexpr (RING) {
-        const unsigned long long full = __ballot(ring_n == 4);
-        if (full) {
-          if (full & 0x0000000000000001ull) GCN_G_DRAIN(0, 4)
-          if (full & 0x0000000000010000ull) GCN_G_DRAIN(1, 4)
-          if (full & 0x0000000100000000ull) GCN_G_DRAIN(2, 4)
-          if (full & 0x0001000000000000ull) GCN_G_DRAIN(3, 4)
-        }
-      }
+      sink.drain_full();
     }
 #undef GCN_G_ADD
 #undef GCN_G_ALL
   }
-  if constexpr (RING) {                                         // what is left in the rings
-    const unsigned long long some = __ballot(ring_n > 0);
-    if (some & 0x0000000000000001ull) GCN_G_DRAIN(0, __builtin_amdgcn_readlane(ring_n, 0))
-    if (some & 0x0000000000010000ull) GCN_G_DRAIN(1, __builtin_amdgcn_readlane(ring_n, 16))
-    if (some & 0x0000000100000000ull) GCN_G_DRAIN(2, __builtin_amdgcn_readlane(ring_n, 32))
-    if (some & 0x0001000000000000ull) GCN_G_DRAIN(3, __builtin_amdgcn_readlane(ring_n, 48))
-  }
-#undef GCN_G_DRAIN
-  // the row piece that sticks out of the chunk's end (the last entry did not end its row): it is the FIRST piece of its
-  // row — unless the whole chunk lies inside one row, then it is this chunk's head piece — and goes where the row's
-  // partial sum lives, Cv[row]; the pieces of the chunks the row runs on into (their head pieces, P[2c]) are added by
-  // the slice reduction (cut lists) or by group_fixup_kernel
-  if (!row_bcast<15>((int)fl)) {
-    if (fok) store_row_pieces<Row>(ptr, row_pieces<Row>(acc));
-  }
+  sink.drain_rest();
+  sink.tail(!row_bcast<15>((int)fl), row_pieces<Row>(acc));
 }
 
 }  // namespace gcn

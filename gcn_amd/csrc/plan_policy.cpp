@@ -58,7 +58,6 @@ namespace {
 bool env_on(const char* name) { const char* e = std::getenv(name); return !e || e[0] != '0'; }
 }  // namespace
 
-bool group8_enabled() { static const bool v = env_on("GCN_AMD_GROUP8"); return v; }
 bool group_fused_fixup() { static const bool v = env_on("GCN_AMD_GROUP_FUSED_FIXUP"); return v; }
 
 // Entries per chunk of one 16-lane group.  A block walks 16 chunks and 4 blocks are resident per CU (114 VGPRs), so the
@@ -265,6 +264,19 @@ bool odd_width_detour(const gcn_spmm_plan* p, int k) {
 
 int alt_class(int k) { return k <= 32 ? 0 : -1; }
 
+// the shape of one call's group launch on ss: what the launch (run_group_walk adds the buffers) and the report decide from
+GroupArgs group_shape(const SliceSet& ss, bool weighted, int elem_bytes, int ld, int k) {
+  const GroupStream& G = *ss.g;
+  GroupArgs ga{};
+  ga.stream = G.stream; ga.chunk_meta = G.chunk_meta;
+  ga.vals = weighted ? G.vals.get() : nullptr;
+  ga.elem_bytes = elem_bytes;
+  ga.nchunks = G.nchunks; ga.T = G.T; ga.k = k; ga.ldb = ld;
+  ga.table_rows = ss.table_rows();
+  ga.narrow8 = group8_enabled() ? 1 : 0;
+  return ga;
+}
+
 // Widths 33..48 on the five-engine kernel stay on the plan's own slices; where the row stride would have been padded to
 // 64 floats (k = 44 and the odd widths' k' detour) they gather from rows of 48 instead (192 bytes: always two lines, a
 // quarter less table and copy): *ldb = 48, *relay = the call lays that copy out itself (k = 41 / 47: 1.39 / 1.36 ->
@@ -276,9 +288,7 @@ SliceSet pick_slice_set(gcn_spmm_plan* p, int k, int* ldb, bool* relay, bool bui
   const SliceSet own = own_slice_set(p);
   if (p->nnz <= 0 || k % 4 != 0) return own;
   if (k > 32 && k <= 48 && *ldb > 48 && valless_pays(p, k, 48) && group_launch(p, true, false)) {
-    GroupArgs probe{};
-    probe.k = k; probe.ldb = 48; probe.table_rows = group_table_rows(p);
-    if (spmm_group12_applies(probe)) { *ldb = 48; *relay = true; }
+    if (spmm_group_choice(group_shape(own, false, 4, 48, k)).engine == GroupEngine::five12) { *ldb = 48; *relay = true; }
     return own;
   }
   const int cls = alt_class(k);
@@ -362,24 +372,11 @@ int gcn_spmm_plan_main_kernel(const gcn_spmm_plan_t* p, int32_t k, int32_t epilo
     // everything reported — stride, table size, addressing mode, chunk count — from THAT set
     bool relay = false;
     const SliceSet ss = pick_slice_set(const_cast<gcn_spmm_plan*>(p), a.k, &ld_eff, &relay, /*build=*/false, nullptr, nullptr, nullptr, nullptr);
-    const bool big = spmm_group_needs_big(ss.table_rows(), ld_eff * 4LL);
-    const char* bigs = big ? "true" : "false";
-    GroupArgs probe{};
-    probe.k = a.k; probe.ldb = ld_eff; probe.table_rows = ss.table_rows();
-    if (group8_enabled() && a.k <= 32 && ss.g->nchunks % 64 == 0)
-      snprintf(buf, (size_t)buflen, "gcn::spmm_group8_kernel<true, %s>", bigs);
-    else if (spmm_group12_applies(probe))
-      snprintf(buf, (size_t)buflen, "gcn::spmm_group12_kernel");
-    else
-      snprintf(buf, (size_t)buflen, "gcn::spmm_group_ring_kernel<%s>", bigs);
+    spmm_group_kernel_name(spmm_group_choice(group_shape(ss, false, 4, ld_eff, a.k)), buf, (size_t)buflen);
     return GCN_OK;
   }
   if (!a.valless && weighted_pass(p, a.k, ld_eff)) {
-    const char* bigs = spmm_group_needs_big(group_table_rows(p), ld_eff * 4LL) ? "true" : "false";
-    if (group8_enabled() && a.k <= 32 && p->group.nchunks % 64 == 0)
-      snprintf(buf, (size_t)buflen, "gcn::spmm_group8_weighted_kernel<%s>", bigs);
-    else
-      snprintf(buf, (size_t)buflen, "gcn::spmm_group_weighted_kernel<%s>", bigs);
+    spmm_group_kernel_name(spmm_group_choice(group_shape(own_slice_set(p), true, 4, ld_eff, a.k)), buf, (size_t)buflen);
     return GCN_OK;
   }
   describe_main_kernel(a, buf, (size_t)buflen);
@@ -391,8 +388,7 @@ int gcn_spmm_plan_main_kernel_bf16(const gcn_spmm_plan_t* p, int32_t k, int32_t 
   // (the slice set only as it exists: nothing is built here)
   const Bf16Route r = bf16_route(const_cast<gcn_spmm_plan*>(p), k, /*build=*/false, nullptr, nullptr, nullptr, nullptr);
   if (!r.group) return gcn_spmm_plan_main_kernel(p, k, epilogue, buf, buflen);    // the fallback runs the fp32 entry
-  const char* bigs = spmm_group_needs_big(r.ss.table_rows(), r.ldh * 2LL) ? "true" : "false";
-  snprintf(buf, (size_t)buflen, r.weighted ? "gcn::spmm_group_bf16_weighted_kernel<%s>" : "gcn::spmm_group_bf16_kernel<%s>", bigs);
+  spmm_group_kernel_name(spmm_group_choice(group_shape(r.ss, r.weighted, 2, r.ldh, k)), buf, (size_t)buflen);
   return GCN_OK;
 }
 

@@ -25,9 +25,10 @@ struct SliceSet {
 };
 SliceSet own_slice_set(const gcn_spmm_plan* p);
 int alt_class(int k);                   // width class of the narrow slice sets (0: k <= 32), -1: none
+// the shape of one call's group launch on ss (no table, no result buffers): what the launch and the report both decide from
+GroupArgs group_shape(const SliceSet& ss, bool weighted, int elem_bytes, int ld, int k);
 
 // development switches that select an alternate code path a TEST needs (read once per process)
-bool group8_enabled();                  // GCN_AMD_GROUP8=0: k <= 32 on the 64-column group pass
 bool group_fused_fixup();               // GCN_AMD_GROUP_FUSED_FIXUP=0: cut rows' pieces added by a pass of their own
 
 int group_chunk(long long entries, int cu);

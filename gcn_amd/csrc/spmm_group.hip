@@ -35,9 +35,12 @@
 //
 // The walk itself is group_walk.h: one template for this file's fp32 tables (RowF32, 64-column tiles) and the bf16 tables
 // of spmm_group_bf16.hip (RowBf16, 128-column tiles).  This file holds the fp32 instantiations, the eight- and five-engine
-// walks for narrow widths (walks of their own), and the one launch rule of them all (group_grid, launch_spmm_group).
+// walks for narrow widths — chunk loops of their own around group_walk.h's chunk start (and, eight engines, row sink) —, the one choice of
+// kernel (spmm_group_choice: the launch and the reported name ask it) and the one launch rule (group_grid,
+// launch_spmm_group).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include "spmm_kernels.h"
 #include "group_walk.h"
@@ -69,7 +72,7 @@ spmm_group_weighted_kernel(const unsigned short* __restrict__ stream, const floa
 
 // (the eight- and five-engine walks below hold their partial rows as float4)
 __device__ __forceinline__ void store_row_piece(float* dst, const float4& v) { store_row_piece(dst, f32x4{v.x, v.y, v.z, v.w}); }
-
+__device__ __forceinline__ RowPieces<RowF32> row_pieces(const float4& v) { return RowPieces<RowF32>{{f32x4{v.x, v.y, v.z, v.w}}}; }
 
 // ------------------------------------------------------------------------------------------------------------
 // k <= 32: EIGHT independent 8-lane row engines per wave (lane = g*8 + f, f = which float4 of the 32-column tile).
@@ -79,7 +82,8 @@ __device__ __forceinline__ void store_row_piece(float* dst, const float4& v) { s
 // 8-byte words: u16 4f.. and 32+4f..), same chunk_meta / partial slab / fix list; a wave owns eight consecutive
 // chunks.  The DPP broadcasts still work on rows of 16 lanes = two groups: the upper group of a row takes its
 // entry from a copy rotated by eight lanes.  Two 8-entry blocks are in flight together (sixteen gathers).
-// Non-temporal stores; value-free (with the LDS ring) or weighted.
+// Non-temporal stores; value-free (with the LDS ring: rows of 128 bytes, eight of one group leave together) or weighted.
+__device__ __forceinline__ int row_ror8(int v) { return __builtin_amdgcn_mov_dpp(v, 0x128, 0xf, 0xf, true); }   // lane l <- lane (l + 8) % 16 of its row
 template <int UU>
 __device__ __forceinline__ int row_ror8_bcast(int v, int vrot, bool upper) {   // entry UU of THIS lane's 8-lane group
   const int lo = row_bcast<UU>(v), hi = row_bcast<UU>(vrot);
@@ -91,75 +95,37 @@ __device__ __forceinline__ void
 group8_walk(const unsigned short* __restrict__ stream, const float* __restrict__ vals, const int2* __restrict__ chunk_meta,
             const float* __restrict__ Bp, float* __restrict__ Cv, float* __restrict__ P,
             int nchunks, int T, int k, int ldb, int stream_nt, const int* __restrict__ dyn) {
-  if (dyn) { if (dyn[0] == 0) return; nchunks = dyn[1]; }      // (as group_walk)
-  const int lane = threadIdx.x & 63;
-  const int wib  = threadIdx.x >> 6;
-  const int g    = lane >> 3;
-  const int f    = lane & 7;
-  const bool upper = (lane & 8) != 0;                           // the upper group of its 16-lane DPP row
-  const int per_xcd = nchunks >> 3;
-  const int c_in = ((int)(blockIdx.x >> 3) * 4 + wib) * 8;
-  if (c_in >= per_xcd) return;                                  // (whole wave: per_xcd % 8 == 0)
-  const int c = (int)(blockIdx.x & 7) * per_xcd + c_in + g;     // this group's chunk
+  GroupChunk<RowF32, 8, 8, BIG> ch(Bp, nchunks, dyn, (int)blockIdx.x, 0, k, (size_t)k, ldb);
+  if (ch.none()) return;
+  ch.open(chunk_meta, Cv, P);
+  RowSink<RowF32, 8, 8, RING> sink(ch, block_ring<RowF32, 8, 8, RING>());
+  const int f = ch.f, base = ch.base;
+  const bool upper = (ch.lane & 8) != 0;                        // the upper group of its 16-lane DPP row
+  const unsigned row_bytes = ch.row_bytes, foff = ch.foff;
+  const char* Bb = ch.Bb;
 
-  const int fcol = f * 4;
-  const bool fok = fcol < k;
-  const unsigned row_bytes = (unsigned)ldb * 4u;
-  const unsigned foff = (unsigned)(fok ? fcol : 0) * 4u;
-  const char* Bb = reinterpret_cast<const char*>(Bp);
-  const size_t kk = (size_t)k;
-
-  const int2 meta = chunk_meta[c];
-  const int vrow = meta.x >> 1;
-  const bool head = meta.x & 1;
-  const int base = BIG ? 0 : meta.y;
-  if constexpr (BIG) Bb += (size_t)meta.y * (size_t)row_bytes;  // (as group_walk)
-  float* ptr  = head ? P + (size_t)(2 * c) * kk + fcol : Cv + (size_t)vrow * kk + fcol;
-  float* nptr = Cv + (size_t)(vrow + 1) * kk + fcol;
-  bool first = true;
-  // RING: finished rows wait in LDS, eight slots per group, and leave eight at a time — consecutive rows of ONE group,
-  // written by the whole wave with one 64-lane store (as spmm_group_ring_kernel; here a row is 128 bytes)
-  __shared__ f32x4 ring[RING ? 4 : 1][8][8][8];
-  int ring_n = 0;
-  float* ring_base = nullptr;
-#define GCN_G8_DRAIN(G2, ROWS)                                                                      \
-  {                                                                                                 \
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(uintptr_t)ring_base, 8 * G2);     \
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)((uintptr_t)ring_base >> 32), 8 * G2); \
-    float* b0 = reinterpret_cast<float*>(((uintptr_t)hi << 32) | lo);                              \
-    const f32x4 rv = ring[wib][G2][lane >> 3][f];                                                   \
-    if (fok && (lane >> 3) < (ROWS))                                                                \
-      store_row_piece(b0 + (size_t)(lane >> 3) * kk + f * 4, make_float4(rv.x, rv.y, rv.z, rv.w));  \
-    if (g == G2) ring_n = 0;                                                                        \
-  }
-
-  typedef unsigned int u32x2_g8 __attribute__((ext_vector_type(2)));
-  const u32x2_g8* __restrict__ sp = reinterpret_cast<const u32x2_g8*>(stream + (size_t)c * T);
+  const u32x2* __restrict__ sp = reinterpret_cast<const u32x2*>(stream + (size_t)ch.c * T);
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   // words of the current run: w0 = entries of the even 8-entry blocks (0, 2, 4, 6), w1 = of the odd ones
-  u32x2_g8 w0 = stream_nt ? __builtin_nontemporal_load(sp + f) : sp[f];
-  u32x2_g8 w1 = stream_nt ? __builtin_nontemporal_load(sp + 8 + f) : sp[8 + f];
-  u32x2_g8 w0_nx = w0, w1_nx = w1;
+  u32x2 w0 = stream_load(sp + f, stream_nt), w1 = stream_load(sp + 8 + f, stream_nt);
+  u32x2 w0_nx = w0, w1_nx = w1;
   // VALS: the values of the same entries (slicing.hip lays them out like the stream): two 16-byte words per run
-  const f32x4* __restrict__ vp = VALS ? reinterpret_cast<const f32x4*>(vals + (size_t)c * T) : nullptr;
+  const f32x4* __restrict__ vp = VALS ? reinterpret_cast<const f32x4*>(vals + (size_t)ch.c * T) : nullptr;
   f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
-  if constexpr (VALS) {
-    v0 = stream_nt ? __builtin_nontemporal_load(vp + f) : vp[f];
-    v1 = stream_nt ? __builtin_nontemporal_load(vp + 8 + f) : vp[8 + f];
-  }
+  if constexpr (VALS) { v0 = stream_load(vp + f, stream_nt); v1 = stream_load(vp + 8 + f, stream_nt); }
   f32x4 v0_nx = v0, v1_nx = v1;
   unsigned fl1 = 0;
 #pragma unroll 1
   for (int d = 0; d < T / 16; ++d) {                            // two 8-entry blocks (2d, 2d+1 of the chunk) per turn
     const int j = d & 3;                                        // ... the j-th pair of the current run
     if (j == 0 && d + 4 < T / 16) {                             // the next run, a whole run ahead of its use
-      const u32x2_g8* nx = sp + (d / 4 + 1) * 16;
-      w0_nx = stream_nt ? __builtin_nontemporal_load(nx + f) : nx[f];
-      w1_nx = stream_nt ? __builtin_nontemporal_load(nx + 8 + f) : nx[8 + f];
+      const u32x2* nx = sp + (d / 4 + 1) * 16;
+      w0_nx = stream_load(nx + f, stream_nt);
+      w1_nx = stream_load(nx + 8 + f, stream_nt);
       if constexpr (VALS) {
         const f32x4* vnx = vp + (d / 4 + 1) * 16;
-        v0_nx = stream_nt ? __builtin_nontemporal_load(vnx + f) : vnx[f];
-        v1_nx = stream_nt ? __builtin_nontemporal_load(vnx + 8 + f) : vnx[8 + f];
+        v0_nx = stream_load(vnx + f, stream_nt);
+        v1_nx = stream_load(vnx + 8 + f, stream_nt);
       }
     }
     const unsigned e0 = ((j & 2 ? w0.y : w0.x) >> (16 * (j & 1))) & 0xFFFFu;
@@ -168,18 +134,15 @@ group8_walk(const unsigned short* __restrict__ stream, const float* __restrict__
     if constexpr (VALS) {
       vb0 = __builtin_bit_cast(int, j == 0 ? v0.x : j == 1 ? v0.y : j == 2 ? v0.z : v0.w);
       vb1 = __builtin_bit_cast(int, j == 0 ? v1.x : j == 1 ? v1.y : j == 2 ? v1.z : v1.w);
-      vb0r = __builtin_amdgcn_mov_dpp(vb0, 0x128, 0xf, 0xf, true);
-      vb1r = __builtin_amdgcn_mov_dpp(vb1, 0x128, 0xf, 0xf, true);
+      vb0r = row_ror8(vb0); vb1r = row_ror8(vb1);
     }
     if (j == 3) { w0 = w0_nx; w1 = w1_nx; v0 = v0_nx; v1 = v1_nx; }
     const int ro0 = (int)(__umul24((e0 & 0x7FFFu) + (unsigned)base, row_bytes));
     const int ro1 = (int)(__umul24((e1 & 0x7FFFu) + (unsigned)base, row_bytes));
-    const int ro0r = __builtin_amdgcn_mov_dpp(ro0, 0x128, 0xf, 0xf, true);   // row_ror:8 — lane l <- lane (l + 8) % 16 of its row
-    const int ro1r = __builtin_amdgcn_mov_dpp(ro1, 0x128, 0xf, 0xf, true);
+    const int ro0r = row_ror8(ro0), ro1r = row_ror8(ro1);
     const unsigned fl0 = e0 >> 15;
     fl1 = e1 >> 15;
-    const int fl0r = __builtin_amdgcn_mov_dpp((int)fl0, 0x128, 0xf, 0xf, true);
-    const int fl1r = __builtin_amdgcn_mov_dpp((int)fl1, 0x128, 0xf, 0xf, true);
+    const int fl0r = row_ror8((int)fl0), fl1r = row_ror8((int)fl1);
     float4 b[16];
 #define GCN_G8_ALL(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7)
 #define GCN_G8_GATHER0(UU) \
@@ -206,16 +169,8 @@ group8_walk(const unsigned short* __restrict__ stream, const float* __restrict__
     } else {
 #define GCN_G8_STEP(UU, I, ENDS, FL, FLR, VB, VBR)                                                  \
       GCN_G8_ADDV(UU, I, VB, VBR)                                                                   \
-      if (ENDS & (0x0101010101010101ull << UU)) {                /* some group ends a row here */    \
-        if (row_ror8_bcast<UU>((int)FL, FLR, upper)) {                                              \
-          if (RING && !(first && head) && ring_n < 8) {                                             \
-            if (fok) ring[wib][g][ring_n][f] = f32x4{acc.x, acc.y, acc.z, acc.w};                   \
-            if (ring_n == 0) ring_base = ptr;                                                       \
-            ++ring_n;                                                                               \
-          } else if (fok) store_row_piece(ptr, acc);                                                \
-          acc = make_float4(0.f, 0.f, 0.f, 0.f);                                                    \
-          ptr = nptr; nptr += kk; first = false;                                                    \
-        }                                                                                           \
+      if (ENDS & (group_bits<8, 8>() << UU)) {                   /* some group ends a row here */    \
+        if (row_ror8_bcast<UU>((int)FL, FLR, upper)) { sink.finish(row_pieces(acc)); acc = make_float4(0.f, 0.f, 0.f, 0.f); } \
       }
 #define GCN_G8_STEP0(UU) GCN_G8_STEP(UU, UU, ends0, fl0, fl0r, vb0, vb0r)
 #define GCN_G8_STEP1(UU) GCN_G8_STEP(UU, 8 + UU, ends1, fl1, fl1r, vb1, vb1r)
@@ -224,41 +179,16 @@ group8_walk(const unsigned short* __restrict__ stream, const float* __restrict__
 #undef GCN_G8_STEP0
 #undef GCN_G8_STEP1
 #undef GCN_G8_STEP
-      if constexpr (RING) {
-        const unsigned long long full = __ballot(ring_n == 8);
-        if (full) {
-          if (full & (1ull << 0))  GCN_G8_DRAIN(0, 8)
-          if (full & (1ull << 8))  GCN_G8_DRAIN(1, 8)
-          if (full & (1ull << 16)) GCN_G8_DRAIN(2, 8)
-          if (full & (1ull << 24)) GCN_G8_DRAIN(3, 8)
-          if (full & (1ull << 32)) GCN_G8_DRAIN(4, 8)
-          if (full & (1ull << 40)) GCN_G8_DRAIN(5, 8)
-          if (full & (1ull << 48)) GCN_G8_DRAIN(6, 8)
-          if (full & (1ull << 56)) GCN_G8_DRAIN(7, 8)
-        }
-      }
+      sink.drain_full();
     }
 #undef GCN_G8_ADD1
 #undef GCN_G8_ADD0
 #undef GCN_G8_ADDV
 #undef GCN_G8_ALL
   }
-  if constexpr (RING) {                                         // what is left in the rings
-    const unsigned long long some = __ballot(ring_n > 0);
-    if (some & (1ull << 0))  GCN_G8_DRAIN(0, __builtin_amdgcn_readlane(ring_n, 0))
-    if (some & (1ull << 8))  GCN_G8_DRAIN(1, __builtin_amdgcn_readlane(ring_n, 8))
-    if (some & (1ull << 16)) GCN_G8_DRAIN(2, __builtin_amdgcn_readlane(ring_n, 16))
-    if (some & (1ull << 24)) GCN_G8_DRAIN(3, __builtin_amdgcn_readlane(ring_n, 24))
-    if (some & (1ull << 32)) GCN_G8_DRAIN(4, __builtin_amdgcn_readlane(ring_n, 32))
-    if (some & (1ull << 40)) GCN_G8_DRAIN(5, __builtin_amdgcn_readlane(ring_n, 40))
-    if (some & (1ull << 48)) GCN_G8_DRAIN(6, __builtin_amdgcn_readlane(ring_n, 48))
-    if (some & (1ull << 56)) GCN_G8_DRAIN(7, __builtin_amdgcn_readlane(ring_n, 56))
-  }
-#undef GCN_G8_DRAIN
-  // the row piece that sticks out of the chunk's end (the chunk's last entry — entry 7 of its last block — did not end its row)
-  if (!row_ror8_bcast<7>((int)fl1, __builtin_amdgcn_mov_dpp((int)fl1, 0x128, 0xf, 0xf, true), upper)) {
-    if (fok) store_row_piece(ptr, acc);                        // (to Cv[row], or the chunk's head piece: as in group_walk)
-  }
+  sink.drain_rest();
+  // (the chunk's last entry is entry 7 of its last block)
+  sink.tail(!row_ror8_bcast<7>((int)fl1, row_ror8((int)fl1), upper), row_pieces(acc));
 }
 
 template <bool RING, bool BIG>
@@ -289,40 +219,27 @@ spmm_group8_weighted_kernel(const unsigned short* __restrict__ stream, const flo
 // its group's block, lanes f < 4 hold entries 12..15 as well (a second 8-byte word per run); an entry reaches the
 // group's lanes through ds_bpermute (a DPP row is 16 lanes wide and would straddle the groups).  Row ends: two ballots
 // (entries 0..11 and 12..15).  Same chunk_meta, partial slab, cut lists and pieces; a wave owns five consecutive
-// chunks, a block twenty.  Value-free pass, 32-bit slice bases, LDS ring of five rows per group (one 60-lane store).
+// chunks, a block twenty (GroupChunk: the groups that are not live).  Value-free pass, 32-bit slice bases, LDS ring of
+// five rows per group (one 60-lane store).
 __device__ __forceinline__ int lane_bcast(int src_lane_bytes, int v) { return __builtin_amdgcn_ds_bpermute(src_lane_bytes, v); }
 
 __device__ __forceinline__ void
 group12_walk(const unsigned short* __restrict__ stream, const int2* __restrict__ chunk_meta,
              const float* __restrict__ Bp, float* __restrict__ Cv, float* __restrict__ P,
              int nchunks, int T, int k, int ldb, int stream_nt, const int* __restrict__ dyn) {
-  if (dyn) { if (dyn[0] == 0) return; nchunks = dyn[1]; }
-  const int lane = threadIdx.x & 63;
-  const int wib  = threadIdx.x >> 6;
-  const int g    = lane / 12;                                   // 0..4; 5: the four spare lanes
-  const int f    = lane - g * 12;
-  const int per_xcd = nchunks >> 3;
-  const int bx = (int)blockIdx.x;
-  const int c_w = ((bx >> 3) * 4 + wib) * 5;                    // first chunk of this wave inside its XCD's range
-  if (c_w >= per_xcd) return;                                   // (whole wave)
-  // groups past the XCD's range and the spare lanes walk the wave's first chunk along (loads only, nothing stored)
-  const bool live = g < 5 && c_w + g < per_xcd;
-  const int c = (bx & 7) * per_xcd + (live ? c_w + g : c_w);
-
-  const int fcol = f * 4;
-  const bool fok = live && fcol < k;
-  const unsigned row_bytes = (unsigned)ldb * 4u;
-  const unsigned foff = (unsigned)(fcol < k ? fcol : 0) * 4u;
-  const char* Bb = reinterpret_cast<const char*>(Bp);
-  const size_t kk = (size_t)k;
-
-  const int2 meta = chunk_meta[c];
-  const int vrow = meta.x >> 1;
-  const bool head = meta.x & 1;
-  const int base = meta.y;
-  float* ptr  = head ? P + (size_t)(2 * c) * kk + fcol : Cv + (size_t)vrow * kk + fcol;
-  float* nptr = Cv + (size_t)(vrow + 1) * kk + fcol;
+  GroupChunk<RowF32, 5, 12, false> ch(Bp, nchunks, dyn, (int)blockIdx.x, 0, k, (size_t)k, ldb);
+  if (ch.none()) return;
+  ch.open(chunk_meta, Cv, P);
+  const int lane = ch.lane, wib = ch.wib, g = ch.g, f = ch.f, fcol = ch.fcol, base = ch.base, c = ch.c;
+  const bool live = ch.live, fok = live && ch.col_ok, head = ch.head;
+  const unsigned row_bytes = ch.row_bytes, foff = ch.foff;
+  const char* Bb = ch.Bb;
+  const size_t kk = ch.kk;
+  float *ptr = ch.ptr, *nptr = ch.nptr;
   bool first = true;
+  // The ring, its drains and the row ends stay this walk's own text, and the stream words are loaded and decoded in place:
+  // on RowSink, or with stream_load, the compiler allocates this kernel differently (126 to 137 VGPRs
+  // against 135, three or four waves) and its chunk loop is no longer the one that was measured — DESIGN §4.17.
   __shared__ f32x4 ring[4][5][5][12];                           // [wave][group][slot][float4 of the row]
   int ring_n = 0;
   float* ring_base = nullptr;
@@ -339,12 +256,11 @@ group12_walk(const unsigned short* __restrict__ stream, const int2* __restrict__
     if (g == G2) ring_n = 0;                                                                        \
   }
 
-  typedef unsigned int u32x2_g __attribute__((ext_vector_type(2)));
-  const u32x2_g* __restrict__ sp = reinterpret_cast<const u32x2_g*>(stream + (size_t)c * T);
+  const u32x2* __restrict__ sp = reinterpret_cast<const u32x2*>(stream + (size_t)c * T);
   const int f2 = f < 4 ? 12 + f : f;                            // the second word of lanes 0..3: entries 12..15 (others: a copy)
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  u32x2_g eq = stream_nt ? __builtin_nontemporal_load(sp + f) : sp[f], eq_nx = eq;
-  u32x2_g eq2 = stream_nt ? __builtin_nontemporal_load(sp + f2) : sp[f2], eq2_nx = eq2;
+  u32x2 eq = stream_nt ? __builtin_nontemporal_load(sp + f) : sp[f], eq_nx = eq;
+  u32x2 eq2 = stream_nt ? __builtin_nontemporal_load(sp + f2) : sp[f2], eq2_nx = eq2;
   const int srcA = g * 48;                                      // byte index of the group's lane 0 (ds_bpermute counts bytes)
   unsigned long long endsA = 0ull, endsB = 0ull;
 #pragma unroll 1
@@ -376,7 +292,7 @@ group12_walk(const unsigned short* __restrict__ stream, const int2* __restrict__
       const unsigned long long mineB = endsB >> (g < 5 ? g * 12 : 60);    // ... entries 12..15 at 0..3
 #define GCN_G12_STEP(UU)                                                                            \
       GCN_G12_ADD(UU)                                                                               \
-      if ((UU < 12 ? endsA : endsB) & (0x0001001001001001ull << (UU < 12 ? UU : UU - 12))) {        \
+      if ((UU < 12 ? endsA : endsB) & (group_bits<5, 12>() << (UU < 12 ? UU : UU - 12))) {        \
         if (((UU < 12 ? mineA : mineB) >> (UU < 12 ? UU : UU - 12)) & 1ull) {                       \
           if (!(first && head) && ring_n < 5) {                                                     \
             if (fok) ring[wib][g < 5 ? g : 0][ring_n][f] = f32x4{acc.x, acc.y, acc.z, acc.w};       \
@@ -440,26 +356,44 @@ bool spmm_group_eligible(int k, int ldb, long long table_rows, const void* B, co
   return !spmm_group_needs_big(table_rows, ldb * 4LL) || ldb * 4 < (1 << 17);
 }
 
-// 33 <= k <= 48, fp32, value-free, 32-bit slice bases: the five-engine kernel (GCN_AMD_GROUP12=0: the 64-column pass)
-bool spmm_group12_applies(const GroupArgs& a) {
-  static const bool on = [] { const char* e = getenv("GCN_AMD_GROUP12"); return !e || e[0] != '0'; }();
-  const int ldb = a.ldb > 0 ? a.ldb : a.k;
-  return on && a.narrow12 && a.elem_bytes == 4 && !a.vals && a.k > 32 && a.k <= 48 && a.k % 4 == 0 &&
-         !spmm_group_needs_big(a.table_rows, ldb * 4LL);
+// development switches, each read once per process: GCN_AMD_GROUP8=0 keeps k <= 32, GCN_AMD_GROUP12=0 keeps 33..48 on the
+// 64-column pass.  The first reaches the choice as GroupArgs::narrow8 (the drop-in flexspmm leaves the default).
+static bool knob_on(const char* name) { const char* e = getenv(name); return !e || e[0] != '0'; }
+static bool group12_enabled() { static const bool on = knob_on("GCN_AMD_GROUP12"); return on; }
+bool group8_enabled() { static const bool on = knob_on("GCN_AMD_GROUP8"); return on; }
+
+// THE rule for which kernel a launch runs (the launch switches on it, the plan API reports from it): eight engines for
+// fp32, k <= 32 and whole waves of eight chunks per XCD; five for fp32, 33 <= k <= 48, value-free, 32-bit slice bases
+GroupChoice spmm_group_choice(const GroupArgs& a) {
+  const int ld = a.ldb > 0 ? a.ldb : a.k;
+  GroupChoice c;
+  c.bf16 = a.elem_bytes == 2;
+  c.weighted = a.vals != nullptr;
+  c.big = spmm_group_needs_big(a.table_rows, (long long)ld * a.elem_bytes);
+  c.engine = GroupEngine::four16;
+  if (!c.bf16 && a.k % 4 == 0) {
+    if (a.narrow8 && a.k <= 32 && a.nchunks % 64 == 0) c.engine = GroupEngine::eight8;
+    else if (group12_enabled() && a.narrow12 && !c.weighted && a.k > 32 && a.k <= 48 && !c.big) c.engine = GroupEngine::five12;
+  }
+  return c;
 }
 
-// k <= 32, fp32, whole waves of eight chunks per XCD: the eight-engine kernels take the launch
-bool spmm_group8_applies(const GroupArgs& a) {
-  return a.narrow8 && a.elem_bytes == 4 && a.k <= 32 && a.k % 4 == 0 && a.nchunks % 64 == 0;
+// the kernel's name as a profile shows it
+void spmm_group_kernel_name(const GroupChoice& c, char* buf, size_t len) {
+  const char* big = c.big ? "true" : "false";
+  if (!c.bf16 && c.engine == GroupEngine::five12) { snprintf(buf, len, "gcn::spmm_group12_kernel"); return; }
+  if (c.bf16) snprintf(buf, len, c.weighted ? "gcn::spmm_group_bf16_weighted_kernel<%s>" : "gcn::spmm_group_bf16_kernel<%s>", big);
+  else if (c.engine == GroupEngine::eight8) snprintf(buf, len, c.weighted ? "gcn::spmm_group8_weighted_kernel<%s>" : "gcn::spmm_group8_kernel<true, %s>", big);
+  else snprintf(buf, len, c.weighted ? "gcn::spmm_group_weighted_kernel<%s>" : "gcn::spmm_group_ring_kernel<%s>", big);
 }
 
 namespace {
 
-// The launch rule of every group kernel, for column tiles of tile_cols (the eight- and five-engine kernels, one tile
-// and a grid of their own, take stream_nt from it).
-hipError_t group_grid(const GroupArgs& a, int tile_cols, GroupGrid* g) {
-  const int per_xcd = a.nchunks / 8;
-  g->blocks_per_tile = 8 * ((per_xcd + 15) / 16);
+// The launch rule of every group kernel: GROUPS engines per wave (a block walks 4 * GROUPS chunks) on column tiles of
+// tile_cols (the eight- and five-engine kernels have one tile, and no order to pick).
+hipError_t group_grid(const GroupArgs& a, int tile_cols, int groups, GroupGrid* g) {
+  const int per_xcd = a.nchunks / 8, per_block = 4 * groups;
+  g->blocks_per_tile = 8 * ((per_xcd + per_block - 1) / per_block);
   const int tiles = (a.k + tile_cols - 1) / tile_cols;
   // all tiles in ONE launch: tile t+1 starts on the CUs that tile t's last blocks leave idle (k = 128 / 256: 2.89 / 5.70 ->
   // 2.87 / 5.66 ms, profiles/r02zzb_merged_tile_launch.log)
@@ -487,23 +421,20 @@ hipError_t group_grid(const GroupArgs& a, int tile_cols, GroupGrid* g) {
 }
 
 template <bool BIG>
-hipError_t launch_group8_t(const GroupArgs& a, int ldb, int stream_nt, hipStream_t s) {
-  const int nb8 = 8 * ((a.nchunks / 8 + 31) / 32);
+hipError_t launch_group_f32(const GroupArgs& a, const GroupChoice& c, int ldb, const GroupGrid& g, hipStream_t s) {
   const int2* meta = reinterpret_cast<const int2*>(a.chunk_meta);
   const float* Bp = static_cast<const float*>(a.Bp);
-  if (a.vals) spmm_group8_weighted_kernel<BIG><<<dim3(nb8), dim3(256), 0, s>>>(a.stream, a.vals, meta, Bp, a.Cv, a.P, a.nchunks, a.T, a.k, ldb, stream_nt, a.dyn);
-  else        spmm_group8_kernel<true, BIG><<<dim3(nb8), dim3(256), 0, s>>>(a.stream, meta, Bp, a.Cv, a.P, a.nchunks, a.T, a.k, ldb, stream_nt, a.dyn);
-  return hipGetLastError();
-}
-
-template <bool BIG>
-hipError_t launch_group_t(const GroupArgs& a, int ldb, const GroupGrid& g, hipStream_t s) {
-  const int2* meta = reinterpret_cast<const int2*>(a.chunk_meta);
-  const float* Bp = static_cast<const float*>(a.Bp);
-  if (a.vals)
-    spmm_group_weighted_kernel<BIG><<<dim3(g.nblocks), dim3(256), 0, s>>>(a.stream, a.vals, meta, Bp, a.Cv, a.P, a.nchunks, a.T, a.k, g.seg_blocks, ldb, g.stream_nt, g.blocks_per_tile, a.dyn);
-  else
-    spmm_group_ring_kernel<BIG><<<dim3(g.nblocks), dim3(256), 0, s>>>(a.stream, meta, Bp, a.Cv, a.P, a.nchunks, a.T, a.k, g.seg_blocks, ldb, g.stream_nt, g.blocks_per_tile, a.dyn);
+  const dim3 grid(g.nblocks), block(256);
+  if (c.engine == GroupEngine::five12) {
+    if constexpr (BIG) return hipErrorInvalidValue;             // (spmm_group_choice: 32-bit slice bases only)
+    else spmm_group12_kernel<<<grid, block, 0, s>>>(a.stream, meta, Bp, a.Cv, a.P, a.nchunks, a.T, a.k, ldb, g.stream_nt, a.dyn);
+  } else if (c.engine == GroupEngine::eight8) {
+    if (c.weighted) spmm_group8_weighted_kernel<BIG><<<grid, block, 0, s>>>(a.stream, a.vals, meta, Bp, a.Cv, a.P, a.nchunks, a.T, a.k, ldb, g.stream_nt, a.dyn);
+    else            spmm_group8_kernel<true, BIG><<<grid, block, 0, s>>>(a.stream, meta, Bp, a.Cv, a.P, a.nchunks, a.T, a.k, ldb, g.stream_nt, a.dyn);
+  } else {
+    if (c.weighted) spmm_group_weighted_kernel<BIG><<<grid, block, 0, s>>>(a.stream, a.vals, meta, Bp, a.Cv, a.P, a.nchunks, a.T, a.k, g.seg_blocks, ldb, g.stream_nt, g.blocks_per_tile, a.dyn);
+    else            spmm_group_ring_kernel<BIG><<<grid, block, 0, s>>>(a.stream, meta, Bp, a.Cv, a.P, a.nchunks, a.T, a.k, g.seg_blocks, ldb, g.stream_nt, g.blocks_per_tile, a.dyn);
+  }
   return hipGetLastError();
 }
 
@@ -512,26 +443,19 @@ hipError_t launch_group_t(const GroupArgs& a, int ldb, const GroupGrid& g, hipSt
 hipError_t launch_spmm_group(const GroupArgs& a, hipStream_t s) {
   if (a.nchunks <= 0 || a.k <= 0) return hipSuccess;
   if (a.elem_bytes != 4 && a.elem_bytes != 2) return hipErrorInvalidValue;
-  const bool bf16 = a.elem_bytes == 2;
   const int lane_cols = 16 / a.elem_bytes;                            // columns in the 16 bytes a lane gathers
   if (a.nchunks % 32 != 0 || a.k % lane_cols != 0 || a.T < 64 || a.T % 64 != 0) return hipErrorInvalidValue;
   const int ld = a.ldb > 0 ? a.ldb : a.k;
   if (ld % lane_cols != 0 || ld < a.k || ((uintptr_t)a.Bp & 15) != 0) return hipErrorInvalidValue;
   if (a.table_rows <= 0) return hipErrorInvalidValue;                 // (the addressing mode depends on it)
-  const long long row_bytes = (long long)ld * a.elem_bytes;
-  const bool big = spmm_group_needs_big(a.table_rows, row_bytes);
-  if (big && row_bytes >= (1 << 17)) return hipErrorInvalidValue;     // (the offset inside a slice must still fit 32 bits)
+  const GroupChoice c = spmm_group_choice(a);
+  if (c.big && (long long)ld * a.elem_bytes >= (1 << 17)) return hipErrorInvalidValue;   // (the offset inside a slice must still fit 32 bits)
+  const int groups    = c.engine == GroupEngine::eight8 ? 8 : c.engine == GroupEngine::five12 ? 5 : 4;
+  const int tile_cols = c.engine == GroupEngine::eight8 ? 32 : c.engine == GroupEngine::five12 ? 48 : c.bf16 ? 128 : 64;
   GroupGrid g;
-  if (const hipError_t e = group_grid(a, bf16 ? 128 : 64, &g); e != hipSuccess) return e;
-  if (bf16) return a.dyn ? hipErrorInvalidValue : launch_group_walk_bf16(a, ld, g, big, s);   // (no bf16 drop-in path)
-  if (spmm_group8_applies(a)) return big ? launch_group8_t<true>(a, ld, g.stream_nt, s) : launch_group8_t<false>(a, ld, g.stream_nt, s);
-  if (spmm_group12_applies(a)) {
-    const int nb12 = 8 * ((a.nchunks / 8 + 19) / 20);
-    spmm_group12_kernel<<<dim3(nb12), dim3(256), 0, s>>>(a.stream, reinterpret_cast<const int2*>(a.chunk_meta), static_cast<const float*>(a.Bp),
-                                                         a.Cv, a.P, a.nchunks, a.T, a.k, ld, g.stream_nt, a.dyn);
-    return hipGetLastError();
-  }
-  return big ? launch_group_t<true>(a, ld, g, s) : launch_group_t<false>(a, ld, g, s);
+  if (const hipError_t e = group_grid(a, tile_cols, groups, &g); e != hipSuccess) return e;
+  if (c.bf16) return a.dyn ? hipErrorInvalidValue : launch_group_walk_bf16(a, ld, g, c.big, s);   // (no bf16 drop-in path)
+  return c.big ? launch_group_f32<true>(a, c, ld, g, s) : launch_group_f32<false>(a, c, ld, g, s);
 }
 
 }  // namespace gcn

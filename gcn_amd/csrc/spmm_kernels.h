@@ -122,8 +122,12 @@ hipError_t launch_spmm_group(const GroupArgs& a, hipStream_t s);      // the sin
 struct GroupGrid { int blocks_per_tile, nblocks, stream_nt, seg_blocks; };
 // spmm_group_bf16.hip holds the bf16 instantiations of the walk; launch_spmm_group has checked the arguments
 hipError_t launch_group_walk_bf16(const GroupArgs& a, int ld, const GroupGrid& g, bool big, hipStream_t s);
-bool spmm_group8_applies(const GroupArgs& a);
-bool spmm_group12_applies(const GroupArgs& a);
+// which kernel a launch with this shape runs (the one rule: the launch and the plan API's report ask it), and its name
+enum class GroupEngine { four16, eight8, five12 };                   // engines x lanes of a wave
+struct GroupChoice { GroupEngine engine; bool weighted, big, bf16; };
+GroupChoice spmm_group_choice(const GroupArgs& a);
+void spmm_group_kernel_name(const GroupChoice& c, char* buf, size_t len);
+bool group8_enabled();                  // GCN_AMD_GROUP8=0: k <= 32 on the 64-column group pass (what GroupArgs::narrow8 is set from)
 // the slice-major 15-bit stream the group kernel walks (S slices of width w = ceil(n/S) <= 32767): every virtual
 // row gets >= 1 entry, every slice is padded to whole chunks and the total to a multiple of 32 chunks with
 // entries that gather the slice's zero row.  Outputs: vrowptr_g [S*m+1] (caller-allocated; the fix-up pass needs

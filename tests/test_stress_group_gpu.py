@@ -173,9 +173,9 @@ def _big_child():
             h.update(C32.cpu().numpy().tobytes())
         n_bf16 += 1
     want = {"gcn::spmm_group_ring_kernel", "gcn::spmm_group_weighted_kernel", "gcn::spmm_group8_kernel",
-            "gcn::spmm_group_bf16_kernel", "gcn::spmm_group_bf16_weighted_kernel"}
-    if os.environ.get("GCN_AMD_GROUP8", "1") == "0":
-        want.discard("gcn::spmm_group8_kernel")                 # (the switch that keeps narrow widths off the eight-engine kernel)
+            "gcn::spmm_group8_weighted_kernel", "gcn::spmm_group_bf16_kernel", "gcn::spmm_group_bf16_weighted_kernel"}
+    if os.environ.get("GCN_AMD_GROUP8", "1") == "0":            # (the switch that keeps narrow widths off the eight-engine kernels)
+        want -= {"gcn::spmm_group8_kernel", "gcn::spmm_group8_weighted_kernel"}
     assert not big or want <= seen, seen
     print("big ok", sorted(seen))
     print("big digest", h.hexdigest())
