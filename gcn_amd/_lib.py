@@ -29,6 +29,9 @@ COALESCE_WS_BYTES = 16       # GCN_COALESCE_WS_BYTES (gcn_csr_coalesce_count / _
 COALESCE_SUM, COALESCE_MAX, COALESCE_MIN, COALESCE_FIRST = 0, 1, 2, 3   # GCN_COALESCE_*: the value of a merged run
 DIAG_KEEP, DIAG_DROP, DIAG_FILL, DIAG_ADD = 0, 1, 2, 3                   # GCN_DIAG_*: what the merge does to the diagonal
 NORM_SYM, NORM_ROW = 0, 1    # GCN_NORM_SYM / GCN_NORM_ROW (gcn_csr_normalize_f32)
+SPGEMM_WAVE_MAX = 512        # GCN_SPGEMM_WAVE_MAX: rows of at most this many possible columns are taken by a wave (gcn_spgemm_*_csr)
+SPGEMM_BLOCK_MAX = 8192      # GCN_SPGEMM_BLOCK_MAX: ... by a workgroup with a table in LDS; above, a dense accumulator
+SPGEMM_DENSE_BLOCKS = 16     # GCN_SPGEMM_DENSE_BLOCKS: the workgroups (and accumulators in the workspace) of the dense rows
 
 
 def bucket_ws_bytes(count, nbuckets):
@@ -37,6 +40,20 @@ def bucket_ws_bytes(count, nbuckets):
     count, nbuckets = int(count), int(nbuckets)
     ints = 4 + nbuckets + sum(min(nbuckets, count // (above + 1)) for above in (1, BUCKET_WAVE_MAX, BUCKET_BLOCK_MAX))
     return (ints * 4 + 15) // 16 * 16
+
+
+def spgemm_ws_bytes(m, n):
+    """bytes of device scratch gcn_spgemm_count_csr / _fill_csr need (gcn_spgemm_ws_bytes, written out in
+    include/gcn_spmm.h): two flags, a product count per row, and per dense-row workgroup n stamps and n floats"""
+    return 16 + (4 * int(m) + 15) // 16 * 16 + 8 * int(n) * SPGEMM_DENSE_BLOCKS
+
+
+def spgemm_slots(k):
+    """slots of the hash table of a row with K = k possible columns: the power of two >= 2 k, at least 64"""
+    s = 64
+    while s < 2 * int(k):
+        s *= 2
+    return s
 
 
 _c_i32 = ctypes.c_int32
@@ -111,6 +128,11 @@ SIGNATURES = {
                                              _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_csr_degree_f64": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p]),
     "gcn_csr_normalize_f32": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_p]),
+    "gcn_spgemm_ws_bytes": (ctypes.c_int, [_c_i32, _c_i32, ctypes.POINTER(ctypes.c_size_t)]),
+    "gcn_spgemm_count_csr": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p,
+                                            ctypes.c_size_t, _c_p]),
+    "gcn_spgemm_fill_csr": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p,
+                                           _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_spmm_plan_sddmm_kernel":(ctypes.c_int, [_c_p, _c_i32, ctypes.c_char_p, _c_i32]),
     "gcn_spmm_plan_enable_panels": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_p]),
     "gcn_spmm_plan_panel_rows": (_c_i32, [_c_p]),

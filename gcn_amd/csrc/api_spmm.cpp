@@ -437,6 +437,42 @@ int gcn_csr_normalize_f32(const int32_t* rowptr, const int32_t* col, const float
                                                                                                                   : GCN_ERR_HIP;
 }
 
+static_assert(kSpgemmWaveMax == GCN_SPGEMM_WAVE_MAX && kSpgemmBlockMax == GCN_SPGEMM_BLOCK_MAX &&
+              kSpgemmDenseBlocks == GCN_SPGEMM_DENSE_BLOCKS, "include/gcn_spmm.h");
+
+int gcn_spgemm_ws_bytes(int32_t m, int32_t n, size_t* bytes) {
+  if (m < 0 || n < 0 || !bytes) return GCN_ERR_INVALID_ARG;
+  *bytes = spgemm_workspace_bytes(m, n);
+  return GCN_OK;
+}
+
+int gcn_spgemm_count_csr(const int32_t* a_rowptr, const int32_t* a_col, int32_t m, int32_t p, int32_t nnz_a,
+                         const int32_t* b_rowptr, const int32_t* b_col, int32_t n, int32_t nnz_b, int32_t* out_len, void* ws,
+                         size_t ws_bytes, void* stream) {
+  if (m < 0 || p < 0 || n < 0 || nnz_a < 0 || nnz_b < 0) return GCN_ERR_INVALID_ARG;
+  if (m == 0) return GCN_OK;
+  if (!out_len) return GCN_ERR_INVALID_ARG;
+  if (nnz_a == 0 || nnz_b == 0 || p == 0 || n == 0)     // (no product exists: every row is empty)
+    return hipMemsetAsync(out_len, 0, (size_t)m * 4, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+  if (!a_rowptr || !a_col || !b_rowptr || !b_col || !ws || ws_bytes < spgemm_workspace_bytes(m, n)) return GCN_ERR_INVALID_ARG;
+  return launch_spgemm_count(a_rowptr, a_col, m, p, nnz_a, b_rowptr, b_col, n, nnz_b, out_len, ws, (hipStream_t)stream) == hipSuccess
+             ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_spgemm_fill_csr(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val, int32_t m, int32_t p, int32_t nnz_a,
+                        const int32_t* b_rowptr, const int32_t* b_col, const float* b_val, int32_t n, int32_t nnz_b,
+                        const int32_t* out_rowptr, int32_t* out_col, float* out_val, void* ws, size_t ws_bytes, void* stream) {
+  if (m < 0 || p < 0 || n < 0 || nnz_a < 0 || nnz_b < 0 || (out_val == nullptr) != (a_val == nullptr && b_val == nullptr))
+    return GCN_ERR_INVALID_ARG;
+  if (m == 0) return GCN_OK;
+  if (!out_rowptr) return GCN_ERR_INVALID_ARG;
+  if (nnz_a == 0 || nnz_b == 0 || p == 0 || n == 0) return GCN_OK;       // (nothing to write)
+  if (!a_rowptr || !a_col || !b_rowptr || !b_col || !out_col || !ws || ws_bytes < spgemm_workspace_bytes(m, n))
+    return GCN_ERR_INVALID_ARG;
+  return launch_spgemm_fill(a_rowptr, a_col, a_val, m, p, nnz_a, b_rowptr, b_col, b_val, n, nnz_b, out_rowptr, out_col, out_val,
+                            ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
 int gcn_spmm_plan_sddmm_kernel(const gcn_spmm_plan_t* p, int32_t k, char* buf, int32_t buflen) {
   if (!p || k <= 0 || !buf || buflen <= 0) return GCN_ERR_INVALID_ARG;
   snprintf(buf, (size_t)buflen, "gcn::sddmm_kernel<%s, %s>", sddmm_sliced(p, k) ? "true" : "false",

@@ -244,6 +244,21 @@ hipError_t launch_csr_degree(const int* rowptr, const float* val, int m, int nnz
 hipError_t launch_csr_normalize(const int* rowptr, const int* col, const float* val, int m, int n, int nnz, const double* deg,
                                 int mode, float* out_val, hipStream_t st);
 
+// spgemm.hip — C = A * B of two CSR matrices (count, the caller's scan, fill): row-wise Gustavson with the products of an
+// entry added in A's entry order (plan-free, no floating-point atomics: see the file's header and include/gcn_spmm.h).
+// A [m x p], B [p x n]; a row of at most kSpgemmWaveMax possible columns is taken by a wave with a table in LDS, one of at
+// most kSpgemmBlockMax by a 256-thread workgroup with a table in LDS, a longer one by one of kSpgemmDenseBlocks workgroups
+// with a dense accumulator in the workspace.  out_rowptr [m + 1] is an INPUT of the fill; ws: spgemm_workspace_bytes(m, n).
+constexpr int kSpgemmWaveMax = 512;
+constexpr int kSpgemmBlockMax = 8192;
+constexpr int kSpgemmDenseBlocks = 16;
+size_t spgemm_workspace_bytes(int m, int n);
+hipError_t launch_spgemm_count(const int* a_rowptr, const int* a_col, int m, int p, int nnz_a, const int* b_rowptr,
+                               const int* b_col, int n, int nnz_b, int* out_len, void* ws, hipStream_t st);
+hipError_t launch_spgemm_fill(const int* a_rowptr, const int* a_col, const float* a_val, int m, int p, int nnz_a,
+                              const int* b_rowptr, const int* b_col, const float* b_val, int n, int nnz_b,
+                              const int* out_rowptr, int* out_col, float* out_val, void* ws, hipStream_t st);
+
 // slicing.hip — mutable values.  vsrc[s*m + r] = CSR position of the first entry of row r in slice s (from the sliced
 // row pointer; column-sorted rows make every (row, slice) part one contiguous run of the CSR row).
 hipError_t build_value_map(const int* rowptr, const int* vrowptr, int m, int S, int* vsrc, hipStream_t st);

@@ -508,6 +508,53 @@ int gcn_csr_degree_f64(const int32_t* rowptr_dev, const float* val_dev /* may be
 int gcn_csr_normalize_f32(const int32_t* rowptr_dev, const int32_t* col_dev, const float* val_dev /* may be NULL */, int32_t m,
                           int32_t n, int32_t nnz, const double* deg_dev, int32_t mode, float* out_val_dev, void* stream);
 
+/* C = A * B for two CSR matrices (SpGEMM), A [m x p] and B [p x n]: int32 row pointers and columns, fp32 values, a NULL
+ * value pointer meaning a pattern (every value 1).  Two calls with the caller's prefix sum between them, plan-free and under
+ * the rules of the merge above: the caller's arrays and workspace, one memset node and kernels, no allocation, no host read of
+ * device data, no floating-point atomic; the same bits at every call.  Every access is a 4-byte one.  The contract, exact and
+ * meant to be re-implemented (tests/spgemm_ref.py is the numpy twin):
+ *   PATTERN.  Row i of C has one entry for every column c for which an entry (i, j) of A and an entry (j, c) of B exist.
+ *   The pattern is structural: explicit zeros and sums that cancel keep their entry.  The entries of a row ascend by column.
+ *   VALUE.  The products of an output entry (i, c) are listed with A's entries of row i, in entry order, as the outer loop and
+ *   B's entries of row j, in entry order, as the inner loop.  Each product is fl32(a * b), one rounding, never contracted into
+ *   an FMA; the value is the first product, then acc = fl32(acc + product) left to right ("the first product", not 0 +
+ *   product: a lone -0.0 stays -0.0).  NaN and infinities propagate as the arithmetic gives them.  A pattern operand counts as
+ *   ones; with both operands patterns there are no values: out_val_dev must be NULL exactly then (GCN_ERR_INVALID_ARG
+ *   otherwise).
+ *   PRECONDITIONS.  A may repeat (row, column) pairs freely: they are more products, in entry order.  B must hold each column
+ *   at most once per row (what gcn_csr_coalesce_* returns); its rows need not be sorted.  Where B repeats a column inside a
+ *   row, the pattern is still right and the values of the entries that column feeds are unspecified; nothing is written out
+ *   of bounds.
+ *   An A column outside [0, p) and a B column outside [0, n) contribute nothing.  A row pointer of A outside [0, nnz_a] (or a
+ *   descending pair) makes that row of C empty; one of B makes the entries of A that point at that row contribute nothing.
+ *   Count:  out_len_dev[i] = the number of entries of row i of C.  The caller turns out_len into out_rowptr_dev [m + 1], its
+ *   exclusive prefix sum, an INPUT of the fill.
+ *   Fill:  out_col_dev and out_val_dev of every row.  A row whose out_rowptr length differs from its count (or whose
+ *   out_rowptr[i] is negative) gets nothing written.
+ * HOW A ROW IS TAKEN depends on K_i = min(U_i, n) alone, U_i the number of products of the row (the lengths of the B rows its
+ * entries point at, added up), so both calls agree: K_i <= GCN_SPGEMM_WAVE_MAX: a wave with a hash table in LDS;
+ * K_i <= GCN_SPGEMM_BLOCK_MAX: a 256-thread workgroup with a hash table in LDS; above: one of GCN_SPGEMM_DENSE_BLOCKS
+ * workgroups with n stamps and n floats of the workspace.  A table has the power of two >= 2 K_i slots (at least 64) and is
+ * probed linearly from column & (slots - 1).  Every row length from 0 to n works and the host never reads one.
+ * ws: device scratch owned by the call until it has run, gcn_spgemm_ws_bytes(m, n) =
+ *   16 + 4 * m rounded up to a multiple of 16 + 8 * n * GCN_SPGEMM_DENSE_BLOCKS  bytes; 4-byte alignment is enough.
+ * Negative sizes, a null pointer where data is required or a short workspace: GCN_ERR_INVALID_ARG, before any GPU work.
+ * m == 0: GCN_OK, nothing written.  nnz_a == 0, nnz_b == 0, p == 0 or n == 0: no product exists; the count zeroes out_len_dev
+ * (its only required pointer), the fill writes nothing and needs out_rowptr_dev only.  A caller whose counts sum to 0 has
+ * nothing to fill and skips the second call. */
+#define GCN_SPGEMM_WAVE_MAX     512
+#define GCN_SPGEMM_BLOCK_MAX    8192
+#define GCN_SPGEMM_DENSE_BLOCKS 16
+int gcn_spgemm_ws_bytes(int32_t m, int32_t n, size_t* bytes);
+int gcn_spgemm_count_csr(const int32_t* a_rowptr_dev, const int32_t* a_col_dev, int32_t m, int32_t p, int32_t nnz_a,
+                         const int32_t* b_rowptr_dev, const int32_t* b_col_dev, int32_t n, int32_t nnz_b, int32_t* out_len_dev,
+                         void* ws, size_t ws_bytes, void* stream);
+int gcn_spgemm_fill_csr(const int32_t* a_rowptr_dev, const int32_t* a_col_dev, const float* a_val_dev /* may be NULL */, int32_t m,
+                        int32_t p, int32_t nnz_a, const int32_t* b_rowptr_dev, const int32_t* b_col_dev,
+                        const float* b_val_dev /* may be NULL */, int32_t n, int32_t nnz_b, const int32_t* out_rowptr_dev,
+                        int32_t* out_col_dev, float* out_val_dev /* NULL iff both values are */, void* ws, size_t ws_bytes,
+                        void* stream);
+
 /* LDS-staged row panels (optional): for matrices whose non-zeros sit near the diagonal (community
  * graphs after Rabbit / RCM / Gorder renumbering) a workgroup stages the feature rows of its panel's
  * column window (512 rows x 64 columns = 128 KiB of LDS) once and sums the in-window non-zeros
