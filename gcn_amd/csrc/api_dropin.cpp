@@ -5,7 +5,7 @@
 // starts with "libgcnspmm:" and RETURNS with the caller's output buffers untouched (C stays the zero matrix gcn6
 // hands over, gcn6.py:37; vomp / the CSR stay as they were), so it is never silent and the Python process lives
 // on in a state that can be diagnosed.  Contract: include/gcn_spmm.h (2).
-#include "plan.h"
+#include "plan_policy.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -416,8 +416,9 @@ static void flexspmm_group(const int* seg_rowPtr, const float* segNzCV, const in
       seen->insert(key);
     }
   }
-  const int kc = (k + 3) / 4 * 4;                                 // the group kernels compute at a multiple of 4
-  const int ldb = kc != k ? (kc + 31) / 32 * 32 : padded_ldb(n, k);
+  const gcn::OddShape o = gcn::odd_width_shape(n, k);
+  const int kc = o.k4;                                            // the group kernels compute at a multiple of 4
+  const int ldb = kc != k ? o.ld : padded_ldb(n, k);
   const long long table_rows = (long long)g.S * ((long long)g.w + 1);
   if (!gcn::spmm_group_eligible(kc, ldb, table_rows, nullptr, nullptr, nullptr)) {
     std::fprintf(stderr, "libgcnspmm: flexspmm: feature width %d is beyond what the packed format serves for n=%d; "
@@ -470,10 +471,10 @@ void flexspmm(int* seg_rowPtr, float* segNzCV, int* segVoMap, int* grouped_tailS
   const long long nnz_ub = 9LL * n_segs + 17;        // (n_segs is nnz/9 or one less)
   const int nchunks_ub = (int)((nnz_ub + T - 1) / T);
   // odd widths: computed at k' = k rounded up to 4 on row-padded copies, as in gcn_spmm_csr_f32_bias_relu
-  const bool odd = k > 16 && k % 4 != 0 &&
-                   (long long)sizeof(float) * n * (((k + 3) / 4 * 4 + 31) / 32 * 32) <= (768LL << 20);
-  const int kc = odd ? (k + 3) / 4 * 4 : k;                      // width the kernels compute at
-  const int ldb = odd ? (kc + 31) / 32 * 32 : padded_ldb(n, k);  // row stride B is gathered with
+  const gcn::OddShape o = gcn::odd_width_shape(n, k);
+  const bool odd = k > 16 && k % 4 != 0 && o.fits;
+  const int kc = odd ? o.k4 : k;                                 // width the kernels compute at
+  const int ldb = odd ? o.ld : padded_ldb(n, k);                 // row stride B is gathered with
   std::lock_guard<std::mutex> lk(gcn::g_plan_mu);
   // scratch of the legacy default stream on this device (the reference launches there, flexspmm.cu:512)
   gcn_spmm_plan* sp = gcn::scratch_plan(nullptr);

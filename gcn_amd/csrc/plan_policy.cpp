@@ -192,23 +192,7 @@ size_t ws_elems(const gcn_spmm_plan* p, int k) {
   return 2 * (size_t)(chunks > 0 ? chunks : 1) * (size_t)k;
 }
 
-// Is a k-wide SpMM of this plan launched on the sliced copy?  The four-per-gather kernel pays from k = 33 (narrower
-// rows gather 128 B or less per non-zero: the partial rows cost more than the L2 hits buy, 2.12 vs 2.02 ms at
-// k = 32).  The group kernels pay from k = 12: their 64-column pass costs the same whatever k is, and beats the
-// unsliced kernels there (Reddit-shaped, whole SpMM, profiles/r02zzg_narrow_widths_sliced.log: k = 12 / 16 / 20 /
-// 32: 1.49 / 1.36 / 1.60 / 1.58 -> 1.23 / 1.02 / 1.23 / 1.10 ms; k = 8 a tie, k = 4 loses) — provided the width
-// reaches them: a multiple of 4, or wide enough for the k' = ceil(k/4)*4 detour.
-bool sliced_for(const gcn_spmm_plan* p, int k) {
-  if (p->slicing.S <= 0 || p->nnz <= 0) return false;
-  if (k >= kSliceMinK) return true;
-  if (!p->group.ready() || p->panels.R != 0 || k < kGroupMinK) return false;
-  if (k % 4 == 0) return true;
-  const int kp = (k + 3) / 4 * 4, ldb = (kp + 31) / 32 * 32;         // (the conditions of odd_width_detour)
-  return k > 16 && p->gather_width != 1 && (long long)sizeof(float) * p->n * ldb <= (768LL << 20);
-}
-
-// rows of the slice-by-slice copy of B the group kernels gather from on the plan's OWN slice set (decides their addressing mode)
-long long group_table_rows(const gcn_spmm_plan* p) { return (long long)p->slicing.S * ((long long)p->group.w + 1); }
+namespace {
 
 SliceSet own_slice_set(const gcn_spmm_plan* p) {
   SliceSet s;
@@ -216,20 +200,76 @@ SliceSet own_slice_set(const gcn_spmm_plan* p) {
   return s;
 }
 
-// would the sliced launch of a k-wide SpMM run a value-free kernel (and is the scaled copy of B worth it)?
-bool valless_pays(const gcn_spmm_plan* p, int k, int ldb) {
-  // (the scaled copy of B costs 2*n*k*4 bytes of traffic whatever the matrix; the value stream it saves is
-  //  4 bytes per non-zero plus instructions.  With the group kernel the rank-0 share of an 8-way partition of
-  //  the Reddit-shaped graph, 61 non-zeros per column of the block, still gains: 0.460 against 0.511 ms,
-  //  profiles/r02z7_rank_share_value_free.log; below 48 per column nothing has been measured, so it stays off)
-  if (!sliced_for(p, k) || !p->factors.ready() || p->panels.R != 0 || p->nnz / p->n < kVallessMinPerCol) return false;
-  if (p->group.vals) return false;                     // (the plan was built for the weighted pass: value-free did not pay)
-  if (p->group.ready() && spmm_group_eligible(k, ldb, group_table_rows(p), nullptr, nullptr, nullptr)) return true;   // spmm_group.hip
-  SpmmArgs t{};                                        // the launch as the sliced branch will issue it
-  t.k = k; t.nnz = p->nnz; t.n = p->n; t.nchunks_grid = p->nchunks; t.T = p->T;
-  t.m = p->slicing.S * p->m; t.ldb = ldb; t.tile_cols = p->tile_cols ? p->tile_cols : 64;
-  t.gather_width = p->gather_width;
-  return spmm_will_use_quad(t) && spmm_quad_lanes(k) == 16;
+// Widths that are not a multiple of 4 can take a detour over k4 = k rounded up to 4 (OddShape) to reach the
+// 16-byte-per-lane kernels: never from a panel plan or one kept on one non-zero per gather, and only while the padded
+// table fits its cap
+bool detour_possible(const gcn_spmm_plan* p, int k, const OddShape& o) {
+  return k > 16 && k % 4 != 0 && p->nnz > 0 && p->panels.R == 0 && p->gather_width != 1 && o.fits;
+}
+
+// Is a k-wide SpMM of this plan launched on the sliced copy?  The four-per-gather kernel pays from k = 33 (narrower
+// rows gather 128 B or less per non-zero: the partial rows cost more than the L2 hits buy, 2.12 vs 2.02 ms at
+// k = 32).  The group kernels pay from k = 12: their 64-column pass costs the same whatever k is, and beats the
+// unsliced kernels there (Reddit-shaped, whole SpMM, profiles/r02zzg_narrow_widths_sliced.log: k = 12 / 16 / 20 /
+// 32: 1.49 / 1.36 / 1.60 / 1.58 -> 1.23 / 1.02 / 1.23 / 1.10 ms; k = 8 a tie, k = 4 loses) — provided the width
+// reaches them (lanes16): a multiple of 4, or one the detour is possible for.
+bool sliced_for(const gcn_spmm_plan* p, int k, bool lanes16) {
+  if (p->slicing.S <= 0 || p->nnz <= 0) return false;
+  if (k >= kSliceMinK) return true;
+  return p->group.ready() && p->panels.R == 0 && k >= kGroupMinK && lanes16;
+}
+
+// ... and is the detour taken?  It follows the rule of the kernels it reaches: the four-per-gather kernel only pays from
+// ~48 non-zeros per (virtual) row up, the group kernels do not mind short rows
+bool odd_width_detour(const gcn_spmm_plan* p, bool sliced) {
+  if (p->gather_width == 4) return true;
+  if (sliced && p->group.ready() && (p->group.vals || value_free_plan(p))) return true;
+  const long long rows = sliced ? (long long)p->slicing.S * p->m : (long long)p->m;
+  return rows > 0 && p->nnz / rows >= 48;
+}
+
+// What the sliced launch of a k-wide pass (B gathered with stride ld) runs.  valless: a value-free kernel, on a copy of
+// B scaled by u_col.  (That copy costs 2*n*k*4 bytes of traffic whatever the matrix; the value stream it saves is
+// 4 bytes per non-zero plus instructions.  With the group kernel the rank-0 share of an 8-way partition of the
+// Reddit-shaped graph, 61 non-zeros per column of the block, still gains: 0.460 against 0.511 ms,
+// profiles/r02z7_rank_share_value_free.log; below 48 per column nothing has been measured, so it stays off — and a plan
+// whose group stream carries values was built for the weighted pass: value-free did not pay.)  weighted: the group
+// kernel with the values beside its stream.  group: either way B is gathered from the slice-by-slice copy.
+struct PassKind { bool valless = false, weighted = false, group = false; };
+PassKind pass_kind(const gcn_spmm_plan* p, int k, int ld, bool sliced, int tile_cols) {
+  PassKind pk;
+  if (!sliced || p->panels.R != 0) return pk;
+  const bool walks = p->group.ready() && spmm_group_eligible(k, ld, own_slice_set(p).table_rows(), nullptr, nullptr, nullptr);
+  if (p->group.vals) { pk.weighted = pk.group = walks; return pk; }
+  if (!value_free_plan(p)) return pk;
+  if (walks) { pk.valless = pk.group = true; return pk; }
+  SpmmRoute r;                                         // without the group stream: the four-per-gather kernel, all 16 lanes
+  r.family = SpmmFamily::sliced_quad; r.k_run = k; r.ldb = ld; r.copy = BCopy::row_padded; r.tile_cols = tile_cols;
+  pk.valless = spmm_will_use_quad(spmm_args(p, r, false)) && spmm_quad_lanes(k) == 16;
+  pk.group = pk.valless && p->group.ready();        // (a stream that exists is walked: the width it cannot serve is refused there)
+  return pk;
+}
+
+// The narrow slice set (k <= 32: plan_build.cpp, maybe_build_alt) when the plan has or can have one, else its own
+SliceSet narrow_slice_set(gcn_spmm_plan* p, int k, bool build, const int32_t* rowptr, const int32_t* col, const float* val,
+                          hipStream_t st) {
+  const int cls = alt_class(k);
+  if (cls < 0) return own_slice_set(p);
+  if (build) maybe_build_alt(p, cls, rowptr, col, val, st);
+  if (!p->group_alt[cls].ready()) return own_slice_set(p);
+  SliceSet s;
+  s.g = &p->group_alt[cls]; s.S = p->alt_S[cls]; s.alt = cls;
+  return s;
+}
+
+}  // namespace
+
+OddShape odd_width_shape(long long n, int k) {
+  OddShape o;
+  o.k4 = (k + 3) / 4 * 4;
+  o.ld = (o.k4 + 31) / 32 * 32;
+  o.fits = (long long)sizeof(float) * n * o.ld <= (768LL << 20);
+  return o;
 }
 
 // will a sliced plan of this matrix run the group kernel value-free (known before the slicing exists)
@@ -238,29 +278,6 @@ bool value_free_plan(const gcn_spmm_plan* p) {
 }
 // ... or the group kernel at all (value-free or weighted): it decides the automatic slice count
 bool group_plan(const gcn_spmm_plan* p) { return p->panels.R == 0; }
-// the sliced launch of a k-wide SpMM runs the WEIGHTED group kernel (values beside the stream)
-bool weighted_pass(const gcn_spmm_plan* p, int k, int ldb) {
-  return sliced_for(p, k) && p->panels.R == 0 && p->group.ready() && p->group.vals &&
-         spmm_group_eligible(k, ldb, group_table_rows(p), nullptr, nullptr, nullptr);
-}
-// a launch decided as (valless, weighted) runs one of the group kernels: B is gathered from the slice-by-slice copy
-bool group_launch(const gcn_spmm_plan* p, bool valless, bool weighted) {
-  return weighted || (valless && p->group.ready() && !p->group.vals);
-}
-
-// Widths that are not a multiple of 4 take a detour over k' = k rounded up to 4 (gcn_spmm_csr_f32_epilogue); it
-// exists to reach the 16-byte-per-lane kernels, so it follows their rule: the four-per-gather kernel only pays
-// from ~48 non-zeros per (virtual) row up, the group kernel of the value-free pass does not mind short rows
-bool odd_width_detour(const gcn_spmm_plan* p, int k) {
-  if (!(k > 16 && k % 4 != 0 && p->nnz > 0 && p->panels.R == 0 && p->gather_width != 1)) return false;
-  const int kp = (k + 3) / 4 * 4, ldb = (kp + 31) / 32 * 32;
-  if ((long long)sizeof(float) * p->n * ldb > (768LL << 20)) return false;
-  if (p->gather_width == 4) return true;
-  const bool sliced = sliced_for(p, k);
-  if (sliced && p->group.ready() && (p->group.vals || value_free_plan(p))) return true;
-  const long long rows = sliced ? (long long)p->slicing.S * p->m : (long long)p->m;
-  return rows > 0 && p->nnz / rows >= 48;
-}
 
 int alt_class(int k) { return k <= 32 ? 0 : -1; }
 
@@ -277,53 +294,117 @@ GroupArgs group_shape(const SliceSet& ss, bool weighted, int elem_bytes, int ld,
   return ga;
 }
 
-// Widths 33..48 on the five-engine kernel stay on the plan's own slices; where the row stride would have been padded to
-// 64 floats (k = 44 and the odd widths' k' detour) they gather from rows of 48 instead (192 bytes: always two lines, a
-// quarter less table and copy): *ldb = 48, *relay = the call lays that copy out itself (k = 41 / 47: 1.39 / 1.36 ->
-// 1.34 / 1.30 ms; 36 / 40 keep their dense rows).  (A slice set of their own — 11..13 slices instead of 15 — was built
-// and measured: +-1 %, profiles/r03ba_*; not kept.)  k <= 32: the narrow set (plan_build.cpp, maybe_build_alt).
-SliceSet pick_slice_set(gcn_spmm_plan* p, int k, int* ldb, bool* relay, bool build, const int32_t* rowptr, const int32_t* col,
-                        const float* val, hipStream_t st) {
-  *relay = false;
-  const SliceSet own = own_slice_set(p);
-  if (p->nnz <= 0 || k % 4 != 0) return own;
-  if (k > 32 && k <= 48 && *ldb > 48 && valless_pays(p, k, 48) && group_launch(p, true, false)) {
-    if (spmm_group_choice(group_shape(own, false, 4, 48, k)).engine == GroupEngine::five12) { *ldb = 48; *relay = true; }
-    return own;
+// The route of a k-wide fp32 call.
+// Feature rows that are not a whole number of 128-byte cache lines straddle lines: where that matters (padded_ldb) B is
+// first re-laid with its rows padded to the next multiple of 32 floats (one streaming copy, ~45 us for 233 k x 100) and
+// gathered from there.  The same copy carries the row scaling of the value-free pass (values u[r]*u[c]: B' = diag(u) B)
+// and, for the group kernels, the slice-by-slice layout.  Widths that are not a multiple of 4 (class counts: 41, 47, ...)
+// cannot use the 16-byte-per-lane kernels on the caller's layout: where the detour pays they are computed at k4 on such
+// copies, B re-laid with zero columns and the product compacted into C afterwards (Reddit-shaped k = 41: 2.13 -> 1.87 ms).
+// The slice set of a value-free group launch: k <= 32 the narrow set; widths 33..48 stay on the plan's own slices, and
+// where the stride would have been padded to 64 floats (k = 44 and the detour's k4) the five-engine kernel gathers from
+// rows of 48 instead (192 bytes: always two lines, a quarter less table and copy; k = 41 / 47: 1.39 / 1.36 -> 1.34 /
+// 1.30 ms; 36 / 40 keep their dense rows).  (A slice set of their own — 11..13 slices instead of 15 — was built and
+// measured: +-1 %, profiles/r03ba_*; not kept.)
+SpmmRoute spmm_route(gcn_spmm_plan* p, int k, bool build, const int32_t* rowptr, const int32_t* col, const float* val,
+                     hipStream_t st, bool prelaid) {
+  SpmmRoute r;
+  r.ss = own_slice_set(p);
+  const OddShape o = odd_width_shape(p->n, k);
+  const bool may_detour = !prelaid && detour_possible(p, k, o);
+  const bool sliced = sliced_for(p, k, k % 4 == 0 || may_detour);
+  r.odd = may_detour && odd_width_detour(p, sliced);
+  r.k_run = r.odd ? o.k4 : k;
+  r.ldb = r.odd ? o.ld : padded_ldb(p->n, k);
+  if (p->panels.R > 0 && p->nnz > 0 && k > 32) {
+    r.family = SpmmFamily::panels;
+    r.tile_cols = p->tile_cols ? p->tile_cols : auto_tile_cols(p->n, k);
+  } else {
+    r.tile_cols = p->tile_cols ? p->tile_cols : (sliced ? 64 : auto_tile_cols(p->n, k));
+    const PassKind pk = pass_kind(p, r.k_run, r.ldb, sliced, r.tile_cols);
+    r.valless = pk.valless; r.weighted = pk.weighted;
+    r.family = pk.group ? SpmmFamily::group : sliced ? SpmmFamily::sliced_quad : SpmmFamily::unsliced;
+    r.col16 = r.family == SpmmFamily::sliced_quad && r.valless && p->col16.ready();
+    if (pk.group && r.valless && !prelaid) {
+      if (r.k_run <= 32) r.ss = narrow_slice_set(p, r.k_run, build, rowptr, col, val, st);
+      else if (r.k_run <= 48 && r.ldb > 48 &&
+               spmm_group_choice(group_shape(r.ss, false, 4, 48, r.k_run)).engine == GroupEngine::five12) r.ldb = 48;
+    }
+    r.S_run = pk.group ? r.ss.S : sliced ? p->slicing.S : 0;
+    r.reduce_epilogue = sliced && !r.odd;
   }
-  const int cls = alt_class(k);
-  if (cls < 0 || !valless_pays(p, k, *ldb) || !group_launch(p, true, false)) return own;
-  if (build) maybe_build_alt(p, cls, rowptr, col, val, st);
-  if (!p->group_alt[cls].ready()) return own;
-  SliceSet s;
-  s.g = &p->group_alt[cls]; s.S = p->alt_S[cls]; s.alt = cls;
-  return s;
+  if (prelaid) return r;                               // (B comes in the group layout, rows r.ldb apart)
+  if (p->nnz > 0 && r.family == SpmmFamily::group) r.copy = BCopy::group_layout;
+  else if (p->nnz > 0 && (r.odd || r.ldb != k || r.valless)) r.copy = BCopy::row_padded;
+  else r.ldb = k;                                      // the caller's own rows
+  return r;
+}
+
+// The launch of a non-group route as launch_spmm takes it, without the operand pointers (panels: of the pass over the
+// entries outside the windows)
+SpmmArgs spmm_args(const gcn_spmm_plan* p, const SpmmRoute& r, bool epilogue) {
+  SpmmArgs a{};
+  a.relu = epilogue && !r.reduce_epilogue && !r.odd ? 1 : 0;
+  a.nchunks = a.nchunks_grid = p->nchunks; a.T = p->T; a.m = p->m; a.nnz = p->nnz; a.k = r.k_run; a.n = p->n;
+  a.ldb = r.ldb != r.k_run ? r.ldb : 0;
+  a.empty_rows = p->empty_rows;
+  a.tile_cols = r.tile_cols;
+  a.blocks_per_cu = p->blocks_per_cu;
+  a.gather_width = p->gather_width;
+  if (r.family == SpmmFamily::panels) {
+    const Panels& pn = p->panels;
+    a.nchunks = a.nchunks_grid = pn.out_nchunks; a.T = pn.out_T; a.nnz = pn.out_nnz;
+    a.empty_rows = -1;                                 // (rows whose entries all sit inside their window: not counted)
+    a.accumulate = 1;
+  } else if (r.family == SpmmFamily::sliced_quad) {
+    const Slicing& sl = p->slicing;
+    a.m = sl.S * p->m;
+    a.empty_rows = sl.empty_vrows;
+    a.stream_rows = 1;                                 // partial rows leave with non-temporal stores (3.667 -> 3.646 ms, profiles/r02zi_*)
+    a.valless = r.valless ? 1 : 0;
+    if (r.col16) {                                     // 16-bit column stream, slice-aligned chunks
+      const Col16Stream& c16 = p->col16;
+      a.nnz = c16.nnz16; a.nchunks = a.nchunks_grid = c16.nchunks16;
+      a.col16 = 1; a.col16_S = sl.S; a.col16_w = (p->n + sl.S - 1) / sl.S;
+      a.empty_rows = -1;                               // (its own row pointer: not counted)
+      for (int i = 0; i < 9; ++i) a.col16_start[i] = c16.start16[i];
+    }
+  }
+  return a;
 }
 
 // bf16 operands (spmm_group_bf16.hip): widths k >= 64 with k % 8 == 0 on a plan that runs a group kernel.  The slice set
 // follows the table's row BYTES, not k: a bf16 call at k takes the set of an fp32 call at k / 2 (k = 64: the narrow set
-// of 128-byte rows, built here at first use like the fp32 k <= 32 one).  Rows of the bf16 table are padded to whole
-// 128-byte lines.  Anything else — unsliced plans, panels, narrow / odd widths — takes the fallback.
+// of 128-byte rows, built here at first use like the fp32 k <= 32 one; the five-engine kernel's 48-float rows are an fp32
+// matter only).  Rows of the bf16 table are padded to whole 128-byte lines.  Anything else — unsliced plans, panels,
+// narrow / odd widths — takes the fallback.
 Bf16Route bf16_route(gcn_spmm_plan* p, int k, bool build, const int32_t* rowptr, const int32_t* col, const float* val,
                      hipStream_t st) {
   Bf16Route r;
   if (k < 64 || k % 8 != 0 || p->nnz <= 0 || p->panels.R != 0 || !p->group.ready()) return r;
   const int ldh = (k + 63) / 64 * 64;
   const int kw = k / 2, ldw = ldh / 2;                 // the fp32 width and stride with the same row bytes
-  const bool valless = valless_pays(p, kw, ldw);
-  const bool weighted = !valless && weighted_pass(p, kw, ldw);
-  if (!group_launch(p, valless, weighted)) return r;
-  SliceSet ss = own_slice_set(p);
-  if (valless) {
-    int ld = ldw;
-    bool relay = false;                                // (the five-engine kernel's 48-float rows: an fp32 matter only)
-    ss = pick_slice_set(p, kw, &ld, &relay, build, rowptr, col, val, st);
-  }
+  const PassKind pk = pass_kind(p, kw, ldw, sliced_for(p, kw, true), p->tile_cols ? p->tile_cols : 64);
+  if (!pk.group) return r;
+  const SliceSet ss = pk.valless ? narrow_slice_set(p, kw, build, rowptr, col, val, st) : own_slice_set(p);
   const GroupStream* g = ss.g;
   if (!g || !g->ready() || g->nchunks % 32 != 0 || g->T < 64 || g->T % 64 != 0) return r;
   if (spmm_group_needs_big(ss.table_rows(), ldh * 2LL) && ldh * 2 >= (1 << 17)) return r;
-  r.group = true; r.weighted = weighted; r.ss = ss; r.ldh = ldh;
+  r.group = true; r.weighted = pk.weighted; r.ss = ss; r.ldh = ldh;
   return r;
+}
+
+// the route as it stands: the reports build nothing
+static SpmmRoute report_route(const gcn_spmm_plan* p, int k, bool prelaid = false) {
+  return spmm_route(const_cast<gcn_spmm_plan*>(p), k, /*build=*/false, nullptr, nullptr, nullptr, nullptr, prelaid);
+}
+
+// only the value-free group pass gathers from a scaled, slice-by-slice copy of B; the layout is that of the plan's OWN
+// slice set whatever the width
+int spmm_route_prelaid(const gcn_spmm_plan* p, int k, SpmmRoute* r) {
+  if (k <= 0 || k % 4 != 0) return GCN_ERR_INVALID_ARG;
+  *r = report_route(p, k, /*prelaid=*/true);
+  return r->family == SpmmFamily::group && r->valless ? GCN_OK : GCN_ERR_INVALID_ARG;
 }
 
 }  // namespace gcn
@@ -334,52 +415,20 @@ extern "C" {
 
 int32_t gcn_spmm_plan_num_passes(const gcn_spmm_plan_t* p, int32_t k) {
   if (!p || k <= 0) return -1;
-  if (p->panels.R > 0 && k > 32) return (k + 63) / 64;
-  {                                                    // the group kernels take every tile in one launch
-    int kk = k, ldb = padded_ldb(p->n, k);
-    if (odd_width_detour(p, k)) { kk = (k + 3) / 4 * 4; ldb = (kk + 31) / 32 * 32; }
-    const bool vl = valless_pays(p, kk, ldb);
-    if (group_launch(p, vl, !vl && weighted_pass(p, kk, ldb))) return 1;
-  }
-  const int tile = p->tile_cols ? p->tile_cols : (p->slicing.S > 0 && k > 32 ? 64 : auto_tile_cols(p->n, k));
-  const int vec = pick_vec(k, tile, nullptr, nullptr, nullptr);   // 16-B aligned operands
-  return (k + 64 * vec - 1) / (64 * vec);
+  const SpmmRoute r = report_route(p, k);
+  if (r.family == SpmmFamily::panels) return (k + 63) / 64;
+  if (r.family == SpmmFamily::group) return 1;         // the group kernels take every tile in one launch
+  const int vec = pick_vec(r.k_run, r.tile_cols, nullptr, nullptr, nullptr);   // 16-B aligned operands
+  return (r.k_run + 64 * vec - 1) / (64 * vec);
 }
 
 int gcn_spmm_plan_main_kernel(const gcn_spmm_plan_t* p, int32_t k, int32_t epilogue, char* buf, int32_t buflen) {
   if (!p || k <= 0 || !buf || buflen <= 0) return GCN_ERR_INVALID_ARG;
-  if (p->panels.R > 0 && k > 32) { snprintf(buf, (size_t)buflen, "gcn::spmm_panel_in_kernel"); return GCN_OK; }
-  SpmmArgs a{};
-  const bool sliced = sliced_for(p, k);
-  a.k = k; a.n = p->n; a.m = sliced ? p->slicing.S * p->m : p->m; a.nnz = p->nnz;
-  a.nchunks_grid = p->nchunks;
-  a.relu = epilogue && !sliced ? 1 : 0;               // sliced: the epilogue runs in the slice reduction
-  a.tile_cols = p->tile_cols ? p->tile_cols : (sliced ? 64 : auto_tile_cols(p->n, k));
-  a.gather_width = p->gather_width;
-  if (odd_width_detour(p, k)) {
-    a.k = (k + 3) / 4 * 4;                             // odd widths run at k rounded up to 4 (see gcn_spmm_csr_f32_epilogue)
-    a.ldb = (a.k + 31) / 32 * 32;
-    a.relu = 0;
-    a.valless = valless_pays(p, a.k, a.ldb);
-  } else {
-    if (const int ldb = padded_ldb(p->n, k); ldb != k) a.ldb = ldb;
-    a.valless = valless_pays(p, k, a.ldb > 0 ? a.ldb : k);   // as spmm_impl decides
-  }
-  a.col16 = a.valless && p->col16.ready();
-  int ld_eff = a.ldb > 0 ? a.ldb : a.k;
-  if (a.valless && p->group.ready()) {
-    // the slice set the call would run on (the narrow one only if it exists already: nothing is built here), and
-    // everything reported — stride, table size, addressing mode, chunk count — from THAT set
-    bool relay = false;
-    const SliceSet ss = pick_slice_set(const_cast<gcn_spmm_plan*>(p), a.k, &ld_eff, &relay, /*build=*/false, nullptr, nullptr, nullptr, nullptr);
-    spmm_group_kernel_name(spmm_group_choice(group_shape(ss, false, 4, ld_eff, a.k)), buf, (size_t)buflen);
-    return GCN_OK;
-  }
-  if (!a.valless && weighted_pass(p, a.k, ld_eff)) {
-    spmm_group_kernel_name(spmm_group_choice(group_shape(own_slice_set(p), true, 4, ld_eff, a.k)), buf, (size_t)buflen);
-    return GCN_OK;
-  }
-  describe_main_kernel(a, buf, (size_t)buflen);
+  const SpmmRoute r = report_route(p, k);
+  if (r.family == SpmmFamily::panels) snprintf(buf, (size_t)buflen, "gcn::spmm_panel_in_kernel");
+  else if (r.family == SpmmFamily::group)
+    spmm_group_kernel_name(spmm_group_choice(group_shape(r.ss, r.weighted, 4, r.ldb, r.k_run)), buf, (size_t)buflen);
+  else describe_main_kernel(spmm_args(p, r, epilogue != 0), buf, (size_t)buflen);
   return GCN_OK;
 }
 
@@ -394,15 +443,13 @@ int gcn_spmm_plan_main_kernel_bf16(const gcn_spmm_plan_t* p, int32_t k, int32_t 
 
 int gcn_spmm_plan_prelaid_layout(const gcn_spmm_plan_t* p, int32_t k, int32_t* slices, int32_t* slice_cols,
                                  int64_t* table_rows, int32_t* ld) {
-  if (!p || k <= 0 || k % 4 != 0) return GCN_ERR_INVALID_ARG;
-  const int ldb = padded_ldb(p->n, k);
-  // only the value-free group pass gathers from a scaled, slice-by-slice copy of B; the layout is that of the plan's
-  // OWN slice set whatever the width (gcn_spmm_csr_f32_prelaid runs on it)
-  if (!valless_pays(p, k, ldb) || !group_launch(p, true, false)) return GCN_ERR_INVALID_ARG;
-  if (slices) *slices = p->slicing.S;
-  if (slice_cols) *slice_cols = p->group.w;
-  if (table_rows) *table_rows = group_table_rows(p);
-  if (ld) *ld = ldb;
+  SpmmRoute r;
+  if (!p) return GCN_ERR_INVALID_ARG;
+  if (const int rc = spmm_route_prelaid(p, k, &r); rc != GCN_OK) return rc;
+  if (slices) *slices = r.ss.S;
+  if (slice_cols) *slice_cols = r.ss.g->w;
+  if (table_rows) *table_rows = r.ss.table_rows();
+  if (ld) *ld = r.ldb;
   return GCN_OK;
 }
 

@@ -23,7 +23,6 @@ struct SliceSet {
   int alt = -1;                         // width class of group_alt, -1: the plan's own set
   long long table_rows() const { return (long long)S * ((long long)(g ? g->w : 0) + 1); }
 };
-SliceSet own_slice_set(const gcn_spmm_plan* p);
 int alt_class(int k);                   // width class of the narrow slice sets (0: k <= 32), -1: none
 // the shape of one call's group launch on ss (no table, no result buffers): what the launch and the report both decide from
 GroupArgs group_shape(const SliceSet& ss, bool weighted, int elem_bytes, int ld, int k);
@@ -33,21 +32,39 @@ bool group_fused_fixup();               // GCN_AMD_GROUP_FUSED_FIXUP=0: cut rows
 
 int group_chunk(long long entries, int cu);
 size_t ws_elems(const gcn_spmm_plan* p, int k);
-long long group_table_rows(const gcn_spmm_plan* p);
 
-bool sliced_for(const gcn_spmm_plan* p, int k);
-bool valless_pays(const gcn_spmm_plan* p, int k, int ldb);
 bool value_free_plan(const gcn_spmm_plan* p);
 bool group_plan(const gcn_spmm_plan* p);
-bool weighted_pass(const gcn_spmm_plan* p, int k, int ldb);
-bool group_launch(const gcn_spmm_plan* p, bool valless, bool weighted);
-bool odd_width_detour(const gcn_spmm_plan* p, int k);
 
-// Which slice set does a k-wide call run on (k already rounded up to a multiple of 4; *ldb the row stride it would gather
-// with, lowered to 48 for the widths the five-engine kernel serves from 192-byte rows: *relay = the call lays that copy
-// out itself)?  `build`: build the narrow set at first use (needs the CSR); without it only what exists is chosen.
-SliceSet pick_slice_set(gcn_spmm_plan* p, int k, int* ldb, bool* relay, bool build, const int32_t* rowptr, const int32_t* col,
-                        const float* val, hipStream_t st);
+// Widths that are not a multiple of 4 are computed at k4 = ceil(k / 4) * 4 on copies whose rows are ld floats apart (whole
+// 128-byte lines); fits: that copy of an n-row table stays within the 768 MiB the re-laid tables are capped at.
+struct OddShape { int k4, ld; bool fits; };
+OddShape odd_width_shape(long long n, int k);
+
+// How ONE k-wide fp32 call runs: decided once (spmm_route), consumed by the launch (api_spmm.cpp) and printed by the
+// reports (gcn_spmm_plan_num_passes / _main_kernel / _prelaid_layout).  DESIGN.md §4.19 lists who reads what.
+enum class SpmmFamily { panels, unsliced, sliced_quad, group };
+enum class BCopy { none, row_padded, group_layout };   // the copy of B the call lays out first
+struct SpmmRoute {
+  SpmmFamily family = SpmmFamily::unsliced;
+  bool odd = false;                     // computed at k_run = ceil(k / 4) * 4 into a padded result, compacted afterwards
+  int k_run = 0;
+  int ldb = 0;                          // row stride B is gathered with (k_run: the caller's own rows)
+  BCopy copy = BCopy::none;             // (a value-free route's copy has its rows multiplied by u_col)
+  bool valless = false, weighted = false, col16 = false;
+  SliceSet ss;                          // the slice set a group launch walks
+  int S_run = 0;                        // slices the partial rows are sized with (0: not sliced)
+  int tile_cols = 0;
+  bool reduce_epilogue = false;         // the slice reduction carries bias, ReLU and dropout (else the main kernel / a pass after it)
+};
+// `build`: build the narrow slice set (k <= 32) at first use, which needs the CSR; without it only what exists is chosen.
+// `prelaid`: the caller hands B over in the plan's pre-laid layout (own slice set, rows already scaled, no detour).
+SpmmRoute spmm_route(gcn_spmm_plan* p, int k, bool build, const int32_t* rowptr, const int32_t* col, const float* val,
+                     hipStream_t st, bool prelaid = false);
+// the launch of a non-group route without its pointers: what launch_spmm is handed and describe_main_kernel names
+SpmmArgs spmm_args(const gcn_spmm_plan* p, const SpmmRoute& r, bool epilogue);
+// the route of a call that hands B over pre-laid (k % 4 == 0), or GCN_ERR_INVALID_ARG: the plan has no such layout for k
+int spmm_route_prelaid(const gcn_spmm_plan* p, int k, SpmmRoute* r);
 
 // How a bf16 call at width k runs (api_spmm.cpp, gcn_spmm_csr_bf16_epilogue): on the bf16 group walk (group = true) —
 // value-free or weighted, on the slice set an fp32 call with the same table row BYTES would take (k / 2 columns), from a

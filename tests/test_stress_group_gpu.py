@@ -83,7 +83,7 @@ def test_group8_kernel_random(seed):
     assert adj.num_slices == S and adj.has_value_factors
     name = adj.main_kernel(k)
     knobs_off = os.environ.get("GCN_AMD_GROUP8", "1") == "0"
-    if len(col) // n >= 48 and not knobs_off:                    # (below: the weighted pass, see valless_pays)
+    if len(col) // n >= 48 and not knobs_off:                    # (below: the weighted pass, see pass_kind in plan_policy.cpp)
         assert name.startswith("gcn::spmm_group8_kernel<"), (name, k)
     assert not adj.main_kernel(8).startswith("gcn::spmm_group")
     B = rng.standard_normal((n, k)).astype(np.float32)
@@ -111,7 +111,7 @@ def test_group12_kernel_random(seed):
     assert adj.num_slices == S and adj.has_value_factors
     name = adj.main_kernel(k)
     knobs_off = os.environ.get("GCN_AMD_GROUP12", "1") == "0" or os.environ.get("GCN_AMD_GROUP_BIG", "0") == "1"   # (64-bit slice bases: the 64-column pass)
-    if len(col) // n >= 48 and not knobs_off:                    # (below: the weighted pass, see valless_pays)
+    if len(col) // n >= 48 and not knobs_off:                    # (below: the weighted pass, see pass_kind in plan_policy.cpp)
         assert name == "gcn::spmm_group12_kernel", (name, k)
     assert name.startswith("gcn::spmm_group"), (name, k)
     B = rng.standard_normal((n, k)).astype(np.float32)
