@@ -32,6 +32,9 @@ NORM_SYM, NORM_ROW = 0, 1    # GCN_NORM_SYM / GCN_NORM_ROW (gcn_csr_normalize_f3
 SPGEMM_WAVE_MAX = 512        # GCN_SPGEMM_WAVE_MAX: rows of at most this many possible columns are taken by a wave (gcn_spgemm_*_csr)
 SPGEMM_BLOCK_MAX = 8192      # GCN_SPGEMM_BLOCK_MAX: ... by a workgroup with a table in LDS; above, a dense accumulator
 SPGEMM_DENSE_BLOCKS = 16     # GCN_SPGEMM_DENSE_BLOCKS: the workgroups (and accumulators in the workspace) of the dense rows
+KNN_K_MAX = 64               # GCN_KNN_K_MAX: the most neighbours gcn_knn_f32 returns per query
+KNN_TILE_Q = 64              # GCN_KNN_TILE_Q: queries of a workgroup
+KNN_TILE_C = 64              # GCN_KNN_TILE_C: candidates of a tile; the candidate range is split in whole tiles
 
 
 def bucket_ws_bytes(count, nbuckets):
@@ -46,6 +49,22 @@ def spgemm_ws_bytes(m, n):
     """bytes of device scratch gcn_spgemm_count_csr / _fill_csr need (gcn_spgemm_ws_bytes, written out in
     include/gcn_spmm.h): two flags, a product count per row, and per dense-row workgroup n stamps and n floats"""
     return 16 + (4 * int(m) + 15) // 16 * 16 + 8 * int(n) * SPGEMM_DENSE_BLOCKS
+
+
+def knn_splits(q, n, splits, cus=256):
+    """parts of the candidate range gcn_knn_f32 works with (gcn_knn_splits, the rule written out in include/gcn_spmm.h):
+    splits >= 1 as given, 0 = two workgroups per CU but at least 8 tiles per part (not measured); then within [1, tiles]"""
+    q, n, splits, cus = int(q), int(n), int(splits), int(cus)
+    blocks, tiles = -(-q // KNN_TILE_Q), -(-n // KNN_TILE_C)
+    if splits <= 0:
+        splits = min(-(-2 * (cus if cus > 0 else 256) // blocks), tiles // 8) if blocks > 0 else 1
+    return max(1, min(splits, tiles))
+
+
+def knn_ws_bytes(q, n, k, splits, cus=256):
+    """bytes of device scratch gcn_knn_f32 needs (gcn_knn_ws_bytes, written out in include/gcn_spmm.h): k keys of 8 bytes
+    and one fp64 partial sum for every (query, part)"""
+    return 16 + (8 * int(q) * knn_splits(q, n, splits, cus) * (int(k) + 1) + 15) // 16 * 16
 
 
 def spgemm_slots(k):
@@ -133,6 +152,10 @@ SIGNATURES = {
                                             ctypes.c_size_t, _c_p]),
     "gcn_spgemm_fill_csr": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p,
                                            _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_knn_splits": (ctypes.c_int, [_c_i32, _c_i32, _c_i32]),
+    "gcn_knn_ws_bytes": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i32, ctypes.POINTER(ctypes.c_size_t)]),
+    "gcn_knn_f32": (ctypes.c_int, [_c_p, ctypes.c_int64, _c_p, ctypes.c_int64, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32,
+                                   _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_spmm_plan_sddmm_kernel":(ctypes.c_int, [_c_p, _c_i32, ctypes.c_char_p, _c_i32]),
     "gcn_spmm_plan_enable_panels": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_p]),
     "gcn_spmm_plan_panel_rows": (_c_i32, [_c_p]),

@@ -421,6 +421,45 @@ int gcn_spgemm_fill_csr(const int32_t* a_rowptr, const int32_t* a_col, const flo
                             ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
 }
 
+static_assert(kKnnKMax == GCN_KNN_K_MAX && kKnnTileQ == GCN_KNN_TILE_Q && kKnnTileC == GCN_KNN_TILE_C, "include/gcn_spmm.h");
+
+namespace {
+// the sizes every knn entry point refuses: negative, k outside [1, GCN_KNN_K_MAX], or more workgroups / part keys than fit
+bool knn_sizes_ok(int32_t q, int32_t n, int32_t k, int32_t splits) {
+  return q >= 0 && n >= 0 && k >= 1 && k <= GCN_KNN_K_MAX && splits >= 0;
+}
+bool knn_grid_ok(int32_t q, int eff) {
+  return (((long long)q + kKnnTileQ - 1) / kKnnTileQ) * (long long)eff < (1LL << 31);
+}
+}  // namespace
+
+int gcn_knn_splits(int32_t q, int32_t n, int32_t splits) {
+  if (q < 0 || n < 0 || splits < 0) return -1;
+  return knn_effective_splits(q, n, splits, cu_count_cached());
+}
+
+int gcn_knn_ws_bytes(int32_t q, int32_t n, int32_t k, int32_t splits, size_t* bytes) {
+  if (!knn_sizes_ok(q, n, k, splits) || !bytes) return GCN_ERR_INVALID_ARG;
+  const int eff = knn_effective_splits(q, n, splits, cu_count_cached());
+  if (!knn_grid_ok(q, eff)) return GCN_ERR_INVALID_ARG;
+  *bytes = knn_workspace_bytes(q, k, eff);
+  return GCN_OK;
+}
+
+int gcn_knn_f32(const float* x, int64_t ldx, const float* y, int64_t ldy, int32_t q, int32_t n, int32_t d, int32_t k,
+                int32_t self_offset, int32_t splits, int32_t* out_idx, float* out_dist2, double* out_sum, void* ws,
+                size_t ws_bytes, void* stream) {
+  if (!knn_sizes_ok(q, n, k, splits) || d < 1 || ldx < d || ldy < d || self_offset < -1) return GCN_ERR_INVALID_ARG;
+  if (q == 0) return GCN_OK;
+  const int eff = knn_effective_splits(q, n, splits, cu_count_cached());
+  if (!knn_grid_ok(q, eff)) return GCN_ERR_INVALID_ARG;
+  if (!x || (n > 0 && !y) || !out_idx || !ws || (reinterpret_cast<uintptr_t>(ws) & 7) != 0 ||
+      ws_bytes < knn_workspace_bytes(q, k, eff))
+    return GCN_ERR_INVALID_ARG;
+  return launch_knn(x, ldx, y, ldy, q, n, d, k, self_offset, eff, out_idx, out_dist2, out_sum, ws, (hipStream_t)stream) == hipSuccess
+             ? GCN_OK : GCN_ERR_HIP;
+}
+
 int gcn_spmm_plan_sddmm_kernel(const gcn_spmm_plan_t* p, int32_t k, char* buf, int32_t buflen) {
   if (!p || k <= 0 || !buf || buflen <= 0) return GCN_ERR_INVALID_ARG;
   snprintf(buf, (size_t)buflen, "gcn::sddmm_kernel<%s, %s>", sddmm_sliced(p, k) ? "true" : "false",

@@ -54,6 +54,19 @@ int auto_tile_cols(long long n, int k) {
   return 0;                                      // widest tile k allows (<= 256 columns)
 }
 
+// Parts of the candidate range per query block of gcn_knn_f32 when the caller passes splits = 0.  NOT MEASURED: the aim is two
+// workgroups per CU (a workgroup at k = 64 takes 99 KiB of LDS, so one is resident per CU and the second fills the tail),
+// with at least 8 candidate tiles per part so that a part's k keys and its merge stay small beside its distances.
+int knn_auto_splits(int q, int n, int cus) {
+  if (cus <= 0) cus = 256;
+  const long long blocks = ((long long)q + kKnnTileQ - 1) / kKnnTileQ;
+  const long long tiles = ((long long)n + kKnnTileC - 1) / kKnnTileC;
+  if (blocks <= 0) return 1;
+  long long s = (2LL * cus + blocks - 1) / blocks;
+  if (s > tiles / 8) s = tiles / 8;
+  return s < 1 ? 1 : (int)s;
+}
+
 namespace {
 bool env_on(const char* name) { const char* e = std::getenv(name); return !e || e[0] != '0'; }
 }  // namespace

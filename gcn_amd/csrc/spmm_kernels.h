@@ -259,6 +259,19 @@ hipError_t launch_spgemm_fill(const int* a_rowptr, const int* a_col, const float
                               const int* b_rowptr, const int* b_col, const float* b_val, int n, int nnz_b,
                               const int* out_rowptr, int* out_col, float* out_val, void* ws, hipStream_t st);
 
+// knn.hip — brute-force k nearest neighbours of fp32 rows by squared Euclidean distance (plan-free, no floating-point
+// atomics: see the file's header and include/gcn_spmm.h).  A 256-thread workgroup owns kKnnTileQ queries and streams its part
+// of the candidates through in tiles of kKnnTileC; `eff_splits` = knn_effective_splits(...) parts per query block, merged by
+// a second kernel.  ws: knn_workspace_bytes(q, k, eff_splits), 8-byte aligned.
+constexpr int kKnnKMax = 64;
+constexpr int kKnnTileQ = 64;
+constexpr int kKnnTileC = 64;
+int knn_auto_splits(int q, int n, int cus);            // plan_policy.cpp
+int knn_effective_splits(int q, int n, int splits, int cus);
+size_t knn_workspace_bytes(int q, int k, int eff_splits);
+hipError_t launch_knn(const float* x, long long ldx, const float* y, long long ldy, int q, int n, int d, int k, int self_offset,
+                      int eff_splits, int* out_idx, float* out_dist2, double* out_sum, void* ws, hipStream_t st);
+
 // slicing.hip — mutable values.  vsrc[s*m + r] = CSR position of the first entry of row r in slice s (from the sliced
 // row pointer; column-sorted rows make every (row, slice) part one contiguous run of the CSR row).
 hipError_t build_value_map(const int* rowptr, const int* vrowptr, int m, int S, int* vsrc, hipStream_t st);

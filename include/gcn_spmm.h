@@ -555,6 +555,50 @@ int gcn_spgemm_fill_csr(const int32_t* a_rowptr_dev, const int32_t* a_col_dev, c
                         int32_t* out_col_dev, float* out_val_dev /* NULL iff both values are */, void* ws, size_t ws_bytes,
                         void* stream);
 
+/* Brute-force k nearest neighbours: for every query row x_i (fp32 [q x d], row stride ldx >= d floats) the k candidate rows
+ * y_j (fp32 [n x d], row stride ldy >= d) of smallest squared Euclidean distance.  The q x n distance matrix is never written
+ * to memory.  Plan-free: the caller's arrays and workspace, two kernels enqueued on the stream, no allocation, no host read
+ * of device data, no synchronisation (one linear chain under graph capture), no floating-point atomic; the same bits at every
+ * call.  x and y may be the same array or overlap.  Operands need 4-byte alignment only.  The contract, exact and meant to be
+ * re-implemented (tests/knn_ref.py is the numpy twin):
+ *   DISTANCE.  d2(i, j) is a pure function of the two rows: one fp32 accumulator starting at 0, the columns c = 0 .. d - 1 in
+ *   ascending order, diff = fl32(x_ic - y_jc), acc = fmaf(diff, diff, acc) (one rounding).  It is computed from differences,
+ *   never as |x|^2 + |y|^2 - 2 x.y.  So a row is at distance exactly 0 from itself and from a duplicate, d2(a, b) and
+ *   d2(b, a) are the same bits, the result does not depend on tile, split or launch shape, and it is within
+ *   (d + 4) * 2^-24 relative of the exact value (each term: one rounding of the difference, squared, and one of the fma, on a
+ *   sum of non-negative terms).
+ *   ORDER.  The key of a candidate is the pair (fp32 bits of d2, index j) compared as unsigned integers: non-negative floats
+ *   order as their bits; a NaN distance, of either sign bit, ranks behind every number, +inf included, all NaNs tie, and it
+ *   is returned as NaN.  Keys are unique, so the k smallest keys are a unique set.  Output row i lists them ascending by key:
+ *   on equal distances the smaller index comes first.  With fewer than k admissible candidates the tail is index -1 and
+ *   distance +inf.
+ *   SELF EXCLUSION.  self_offset >= 0 makes candidate self_offset + i inadmissible for query i ("x is y, without the point
+ *   itself" is 0; "the queries are rows [o, o + q) of y" is o); -1 turns it off.
+ *   ROW SUMS.  out_sum_dev (fp64 [q], NULL skips it): sum over ALL n candidates j of sqrt((double) d2(i, j)), the excluded one
+ *   too, with its true distance (0 for a self).  The order of the additions depends on nothing but the effective split
+ *   count: the same bits at every call; two split counts differ by at most n * 2^-53 relative.
+ * HOW THE WORK IS SPREAD.  A 256-thread workgroup owns GCN_KNN_TILE_Q queries and streams candidates through in tiles of
+ * GCN_KNN_TILE_C.  The ceil(n / GCN_KNN_TILE_C) tiles are cut into S contiguous parts (part p: tiles [p T / S, (p + 1) T / S));
+ * every (query block, part) writes its k smallest keys and its part of the row sum to the workspace and a second kernel, a
+ * wave per query, selects among the S * k keys and adds the partial sums in part order.  Apart from the last bits of the row
+ * sum the result is identical for every S.  splits >= 1 is taken as given; splits == 0 lets the library choose
+ * (NOT MEASURED: a guess that awaits a sweep):  S = ceil(2 * CUs / ceil(q / GCN_KNN_TILE_Q)), at most T / 8.  Either is then
+ * clamped to [1, T]: S = gcn_knn_splits(q, n, splits).
+ * ws: device scratch owned by the call until it has run, 8-byte aligned, gcn_knn_ws_bytes(q, n, k, splits) =
+ *   16 + 8 * q * S * (k + 1) rounded up to a multiple of 16  bytes.
+ * GCN_ERR_INVALID_ARG, before any GPU work: negative q, n or splits, k < 1, k > GCN_KNN_K_MAX, d < 1, a stride below d,
+ * self_offset < -1, ceil(q / GCN_KNN_TILE_Q) * S >= 2^31, and (with q > 0) a null x, out_idx or ws, a null y with n > 0, a
+ * workspace that is short or not 8-byte aligned.  q == 0: GCN_OK, nothing launched.  n == 0: every output row is -1 / +inf and
+ * the sums are 0.  out_idx_dev: int32 [q * k]; out_dist2_dev: fp32 [q * k], NULL skips it. */
+#define GCN_KNN_K_MAX  64
+#define GCN_KNN_TILE_Q 64
+#define GCN_KNN_TILE_C 64
+int gcn_knn_splits(int32_t q, int32_t n, int32_t splits);                  /* the effective S; -1 for a negative argument */
+int gcn_knn_ws_bytes(int32_t q, int32_t n, int32_t k, int32_t splits, size_t* bytes);
+int gcn_knn_f32(const float* x_dev, int64_t ldx, const float* y_dev, int64_t ldy, int32_t q, int32_t n, int32_t d, int32_t k,
+                int32_t self_offset, int32_t splits, int32_t* out_idx_dev, float* out_dist2_dev /* may be NULL */,
+                double* out_sum_dev /* may be NULL */, void* ws, size_t ws_bytes, void* stream);
+
 /* LDS-staged row panels (optional): for matrices whose non-zeros sit near the diagonal (community
  * graphs after Rabbit / RCM / Gorder renumbering) a workgroup stages the feature rows of its panel's
  * column window (512 rows x 64 columns = 128 KiB of LDS) once and sums the in-window non-zeros
