@@ -20,8 +20,9 @@ more term of the row ([A 1].[B; bias]) and its addition rounds relative to a sum
 correct kernel could meet the bound where |bias| exceeds |A|.|B|.  The bf16 cases keep util.bf16_assert_bound.
 
 Every case holds empty rows and a hub row (util.exact_pattern; the two cases whose value factors the plan or csr2tile
-must find by itself need a stored diagonal in every row and have single-entry rows in place of the empty ones), and
-asserts the kernel name it claims to run.  The recipes that force a family are those of tests/test_contract_gpu.py."""
+must find by itself need a stored diagonal in every row and have single-entry rows in place of the empty ones; lds_all, whose
+entries all lie inside their panels' windows, has empty rows and no hub row), and asserts the kernel name it claims to run.
+test_exact_epilogue runs leg 1 with the fused epilogue on every route and every piece of code that carries it.  The recipes that force a family are those of tests/test_contract_gpu.py."""
 import ctypes
 import os
 
@@ -32,8 +33,9 @@ import torch
 
 import gcn_amd
 from gcn_amd import _lib, dropin
-from util import (HUB_MIN, assert_elementwise, assert_exact, assert_exact_inputs, bf16_assert_bound, bf16_reference,
-                  dropout_keep, exact_operands, int_features, oracle_spmm, spmm_references, wide_features)
+from util import (EPILOGUE_DROPOUT, EPILOGUE_NINE_SLICES, EPILOGUES, EXACT_EPILOGUE_CASES, HUB_MIN, assert_elementwise, assert_exact,
+                  assert_exact_inputs, bf16_assert_bound, bf16_reference, epilogue_inputs, epilogue_reference, exact_operands,
+                  guards_intact, int_features, offset_view, oracle_spmm, spmm_references, wide_features)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -52,9 +54,9 @@ def _t(a, dtype=None):
     return t if dtype is None else t.to(dtype)
 
 
-def _adj(ops, **kw):
+def _adj(ops, hub=True, **kw):
     lens = np.diff(ops["rp"])
-    assert lens.max() >= HUB_MIN and (lens <= 1).sum() >= 2          # a hub row and empty (or diagonal-only) rows
+    assert (lens.max() >= HUB_MIN or not hub) and (lens <= 1).sum() >= 2   # a hub row and empty (or diagonal-only) rows
     return gcn_amd.CsrAdjacency(_t(ops["rp"]), _t(ops["ci"]), _t(ops["va"]), (ops["m"], ops["n"]), **kw)
 
 
@@ -76,16 +78,48 @@ def _unsliced_adj(family, gather, kind):
     return _PLANS[key]
 
 
-def _group_adj(pattern, kind, hand_over=True):
-    """the slices=3 plan of a 6000-vertex graph: the 15-bit slice-major stream and its kernels"""
-    key = ("group", pattern, kind, hand_over)
+def _group_adj(pattern, kind, hand_over=True, slices=3):
+    """the slices=3 plan of a 6000-vertex graph: the 15-bit slice-major stream and its kernels (slices=9: the same graph in
+    slices of 667 columns, one unrolled group of eight and a tail of one in the wide slice reduction)"""
+    key = ("group", pattern, kind, hand_over, slices)
     if key not in _PLANS:
         ops = exact_operands(pattern, kind)
-        adj = _adj(ops, slices=3)
+        adj = _adj(ops, slices=slices)
         if ops["u_row"] is not None and hand_over:
             adj.set_value_factors(_t(ops["u_row"]), _t(ops["u_col"]))
-        assert adj.num_slices == 3
+        assert adj.num_slices == slices
         assert adj.has_value_factors == (ops["u_row"] is not None), (pattern, kind)
+        _PLANS[key] = (adj, ops)
+    return _PLANS[key]
+
+
+def _special_adj(pattern):
+    """the cached plans of the sliced four-per-gather routes and of the panels, as their plain exact tests force them"""
+    key = ("special", pattern)
+    if key not in _PLANS:
+        if pattern == "vcsr":                                        # slices of 35 000 columns cannot use the 15-bit stream
+            ops = exact_operands("vcsr", "int")
+            adj = _adj(ops, slices=4)
+            adj.set_gather_width(4)
+            assert adj.num_slices == 4 and not adj.has_value_factors
+        elif pattern == "col16":                                     # value-free on the 16-bit column stream, two slices
+            ops = exact_operands("col16", "pow2")
+            adj = _adj(ops, slices=2)
+            adj.set_value_factors(_t(ops["u_row"]), _t(ops["u_col"]))
+            adj.set_gather_width(4)
+            assert adj.num_slices == 2 and adj.has_value_factors
+        elif pattern == "lds":
+            ops = exact_operands("lds", "int")
+            adj = _adj(ops, panels=1)
+            assert adj.panel_rows > 0 and adj.dense_panels == 0 and adj.panel_coverage < 1.0
+        elif pattern == "lds_all":                                   # nothing outside the windows: launch_panel_epilogue
+            ops = exact_operands("lds_all", "int")
+            adj = _adj(ops, hub=False, panels=1)
+            assert adj.panel_rows > 0 and adj.dense_panels == 0 and adj.panel_coverage == 1.0
+        else:
+            ops = exact_operands("mfma", "int")
+            adj = _adj(ops, panels=1)
+            assert adj.dense_panels >= 10
         _PLANS[key] = (adj, ops)
     return _PLANS[key]
 
@@ -170,9 +204,7 @@ def test_exact_value_factors_found_by_the_plan(pattern, kind):
 
 def test_exact_sliced_virtual_csr_with_values():
     """slices of 35 000 columns cannot use the 15-bit stream: the four-per-gather kernel on the slice-major virtual CSR"""
-    ops = exact_operands("vcsr", "int")
-    adj = _adj(ops, slices=4)
-    adj.set_gather_width(4)
+    adj, ops = _special_adj("vcsr")
     name = adj.main_kernel(64)
     assert adj.num_slices == 4 and not adj.has_value_factors
     assert name.startswith("gcn::spmm_quad_kernel<16,"), name
@@ -181,10 +213,7 @@ def test_exact_sliced_virtual_csr_with_values():
 
 def test_exact_sliced_virtual_csr_value_free_on_the_16_bit_column_stream():
     """... and value-free (build_col16_stream): 20 000 x 70 000, two slices, 49 entries per column so the scaled copy pays"""
-    ops = exact_operands("col16", "pow2")
-    adj = _adj(ops, slices=2)
-    adj.set_value_factors(_t(ops["u_row"]), _t(ops["u_col"]))
-    adj.set_gather_width(4)
+    adj, ops = _special_adj("col16")
     assert adj.num_slices == 2 and adj.has_value_factors
     assert adj.main_kernel(64) == "gcn::spmm_quad_kernel<16, false, true, true>", adj.main_kernel(64)
     _exact(adj, ops, 64, "col16")
@@ -192,8 +221,7 @@ def test_exact_sliced_virtual_csr_value_free_on_the_16_bit_column_stream():
 
 def test_exact_lds_panels():
     """spmm_panel_in_quad_kernel (window entries staged in LDS) and the accumulate pass over the rest"""
-    ops = exact_operands("lds", "int")
-    adj = _adj(ops, panels=1)
+    adj, ops = _special_adj("lds")
     assert adj.panel_rows > 0 and adj.dense_panels == 0
     for k in (64, 100):
         assert adj.main_kernel(k) == "gcn::spmm_panel_in_kernel"
@@ -203,52 +231,154 @@ def test_exact_lds_panels():
 @pytest.mark.parametrize("k", [36, 64, 128])
 def test_exact_dense_mfma_panels(k):
     """spmm_panel_dense_mfma_kernel: duplicates ADD in the tile, the tile's zeros add exactly"""
-    key = ("mfma", "int")
-    if key not in _PLANS:
-        ops = exact_operands("mfma", "int")
-        _PLANS[key] = (_adj(ops, panels=1), ops)
-    adj, ops = _PLANS[key]
+    adj, ops = _special_adj("mfma")
     assert adj.dense_panels >= 10 and adj.main_kernel(k) == "gcn::spmm_panel_in_kernel"
     _exact(adj, ops, k, ("mfma", k))
 
 
-EPILOGUES = [dict(bias=True), dict(relu=True), dict(bias=True, relu=True), dict(bias=True, relu=True, dropout=True), dict(dropout=True)]
+# ---------------------------------------------------------------------------------------------------------------
+# leg 1, the fused epilogue: every route x every piece of code that carries it (DESIGN.md §4.19)
+UNSLICED_EPI = {"narrow4": "spmm_narrow_kernel<4, 4, true,", "narrow8": "spmm_narrow_kernel<8, 8, true,",
+                "narrow16_dpp": "spmm_narrow16_dpp_kernel<true>", "quad4": "spmm_quad_kernel<4, true,", "quad16": "spmm_quad_kernel<16, true,",
+                "chunk1": "spmm_chunk_kernel<1, 32, true,", "chunk2": "spmm_chunk_kernel<2, 8, true,", "chunk4": "spmm_chunk_kernel<4, 4, true,"}
+_VF = {"pow2": "value_free", "int": "weighted"}
 
 
-@pytest.mark.parametrize("plan,k", [("unsliced", 100), ("unsliced", 36), ("group_value_free", 41), ("group_weighted", 64)])
-def test_exact_epilogue(plan, k):
-    """integer bias, ReLU, dropout p = 0.5 (scale 1 / (1 - p) = 2 exactly) with the mask of util.dropout_keep: the unsliced
-    kernels' in-place pass and the slice reduction; empty rows hold dropout(act(bias))"""
-    if plan == "unsliced":
-        adj, ops = _unsliced_adj("chunk1" if k == 100 else "quad16", 1 if k == 100 else 4, "int")
-        assert UNSLICED_NAMES["chunk1" if k == 100 else "quad16"] in adj.main_kernel(k, True), adj.main_kernel(k, True)
+def _epi_cases():
+    """(id, carrier, pattern, kind, k, options).  Which slice reduction launch_slice_reduce's rule selects stands beside
+    every case that has one: slice_reduce_wide_kernel for k % 4 == 0, k <= 256 and 16-byte aligned Cv, C, bias and cut slab
+    (DROP = the mask is on; rows per wave and step 256 / k), slice_reduce_kernel<4> for k % 4 == 0 beyond 256 columns,
+    slice_reduce_kernel<1> for everything else."""
+    c = []
+    # the main kernel carries bias / ReLU (EPI), the empty-row pass writes act(bias), the mask is launch_dropout over m * k
+    for family, k, gather in [("narrow4", 4, 0), ("narrow8", 8, 0), ("narrow16_dpp", 15, 0), ("narrow16_dpp", 16, 0), ("quad4", 16, 4),
+                              ("quad16", 36, 4), ("quad16", 128, 4), ("chunk1", 100, 1),
+                              ("chunk1", 41, 1),            # gather width 1: no detour, VEC = 1, a mask count that is no multiple of 4
+                              ("chunk2", 128, 1), ("chunk4", 256, 1)]:
+        c.append((f"main-{family}-k{k}", "main", "unsliced", "int", k, dict(family=family, gather=gather)))
+    # the detour at k' = ceil(k / 4) * 4: launch_unpad_rows carries bias / ReLU, the mask is launch_dropout over m * k with
+    # the CALLER's k.  The group plans reduce at k' (44: wide kernel, DROP = false, five rows per step; 24: ten) with no epilogue
+    c.append(("detour-unsliced-k41", "detour", "unsliced", "int", 41, dict(family="quad16", gather=4)))
+    c.append(("detour-group_value_free-k41", "detour", "group_dup", "pow2", 41, {}))
+    c.append(("detour-group_value_free-k21", "detour", "group_dup", "pow2", 21, {}))
+    c.append(("detour-group_weighted-k41", "detour", "group_dup", "int", 41, {}))
+    # the slice reduction carries everything, the row factor (value-free) and the cut-row pieces included
+    for kind in ("pow2", "int"):
+        for k in (16, 32,                                   # wide kernel, DROP, 16 and 8 rows per wave and step
+                  40,                                       # wide kernel, six rows per step, four lanes idle
+                  64, 128,                                  # wide kernel, four and two rows per step
+                  260):                                     # k > 256: slice_reduce_kernel<4>
+            c.append((f"reduce-{_VF[kind]}-k{k}", "reduce", "group_dup", kind, k, {}))
+        for k in EPILOGUE_NINE_SLICES["group_dup"]:         # wide kernel: one unrolled group of eight slices and a tail of one
+            c.append((f"reduce9-{_VF[kind]}-k{k}", "reduce", "group_dup", kind, k, dict(slices=9)))
+        # the bias one float off the 16-byte grid: slice_reduce_kernel<1>, its scalar mask path
+        c.append((f"reduce-{_VF[kind]}-k64-bias_off_grid", "reduce", "group_dup", kind, 64, dict(bias_off=1)))
+    # sliced, four per gather: the wide kernel at k = 64 without cut lists; col16 with the row factor
+    c.append(("reduce-vcsr-k64", "sliced_quad", "vcsr", "int", 64, {}))
+    c.append(("reduce-col16-k64", "sliced_quad", "col16", "pow2", 64, {}))
+    # panels: the accumulating chunk kernel over the entries outside the windows carries bias / ReLU; lds_all has none
+    # outside, there launch_panel_epilogue does; the mask is launch_dropout
+    for pattern, widths in (("lds", (64, 100)), ("mfma", (36, 64, 128)), ("lds_all", (64, 100))):
+        for k in widths:
+            c.append((f"panels-{pattern}-k{k}", "panels", pattern, "int", k, {}))
+    # bf16 operands: an fp32 result through launch_slice_reduce (wide kernel), a bf16 one through launch_slice_reduce_bf16
+    # (one rounding after the epilogue); an unsliced plan widens, runs the fp32 entry (EPI in the main kernel) and narrows
+    for kind in ("pow2", "int"):
+        for k in (64, 128, 136):
+            c.append((f"bf16-{_VF[kind]}-k{k}", "bf16", "group_dup", kind, k, {}))
+    c.append(("bf16-fallback-quad16-k64", "bf16_fallback", "unsliced", "int", 64, dict(family="quad16", gather=4)))
+    return c
+
+
+EPI_CASES = _epi_cases()
+assert all(any((p, kd) == (tp, tk) and k in tw for tp, tk, tw in EXACT_EPILOGUE_CASES) for _i, _c, p, kd, k, _o in EPI_CASES)
+_EPI_INPUTS = {}
+
+
+def _epilogue_inputs(ops, pattern, kind, k):
+    """(B, bias, keep, C* as fp32) of one (matrix, width), computed once: the 3- and 9-slice plans and the bf16 cases share it"""
+    key = (pattern, kind, k)
+    if key not in _EPI_INPUTS:
+        B, bias, keep = epilogue_inputs(ops["m"], ops["n"], k)
+        assert_exact_inputs(ops["rp"], ops["ci"], ops["va"], B, extra=bias, scale=2.0)
+        _EPI_INPUTS[key] = (B, bias, keep, oracle_spmm(ops["rp"], ops["ci"], ops["va"], B))
+    return _EPI_INPUTS[key]
+
+
+def _epilogue_plan(carrier, pattern, kind, k, opt):
+    """the plan of a case, with the assertion that it runs the kernel and takes the route the case is about"""
+    bf16 = carrier.startswith("bf16")
+    if pattern == "unsliced":
+        adj, ops = _unsliced_adj(opt["family"], opt["gather"], kind)
+        name, plain = adj.main_kernel(k, True), adj.main_kernel(k, False)
+        if carrier == "detour":                              # the main kernel runs without its epilogue
+            assert name == plain and "spmm_quad_kernel<16, false," in name, (name, plain)
+        else:
+            assert UNSLICED_EPI[opt["family"]] in name and UNSLICED_NAMES[opt["family"]] in plain and name != plain, (name, plain)
+        if bf16:
+            assert adj.main_kernel(k, True, dtype=torch.bfloat16) == name
+    elif pattern == "group_dup":
+        adj, ops = _group_adj(pattern, kind, slices=opt.get("slices", 3))
+        assert adj.num_slices == opt.get("slices", 3)
+        if not bf16:                                         # (the bf16 name after the call: k = 64 may build a slice set)
+            name = _assert_group_kernel(adj, k, kind == "int")
+            assert adj.main_kernel(k, True) == name          # the walk carries no epilogue: the reduction or the compaction does
     else:
-        adj, ops = _group_adj("group_dup", "int" if plan == "group_weighted" else "pow2")
-        _assert_group_kernel(adj, k, plan == "group_weighted")
+        adj, ops = _special_adj(pattern)
+        name = adj.main_kernel(k, True)
+        if pattern == "vcsr":
+            assert name.startswith("gcn::spmm_quad_kernel<16, false, false,") and name == adj.main_kernel(k), name
+        elif pattern == "col16":
+            assert name == "gcn::spmm_quad_kernel<16, false, true, true>", name
+        else:
+            assert name == "gcn::spmm_panel_in_kernel", name
+    return adj, ops
+
+
+@pytest.mark.parametrize("case", EPI_CASES, ids=[c[0] for c in EPI_CASES])
+def test_exact_epilogue(case):
+    """C = dropout(act(A.B + bias)) EQUALS util.epilogue_reference on every element, empty rows (dropout(act(bias))) included,
+    for all five EPILOGUES on every route and every piece of code that carries the epilogue: integer bias in [-8, 8], p = 0.5
+    (scale 2 exactly), offset 11, the mask of util.dropout_keep; C starts as NaN.  tests/test_exact_cpu.py proves on these very
+    inputs that a result with one step missing or out of order is refused.  A bf16 result equals the reference converted once.
+    An explicit slice count builds no narrow slice set, so the k <= 32 cases run on the plan's own slices (asserted).
+    Out of scope: OFF32 = false in the wide reduction (a plane of partial rows of 4 GiB), the pre-laid entry (it has no bias,
+    ReLU or mask argument) and GCN_AMD_GROUP_FUSED_FIXUP=0 (read once per process)."""
+    cid, carrier, pattern, kind, k, opt = case
+    adj, ops = _epilogue_plan(carrier, pattern, kind, k, opt)
     m = ops["m"]
-    rng = np.random.default_rng(k)
-    B = int_features(ops["n"], k, seed=3000 + k)
-    bias = rng.integers(-8, 9, k).astype(np.float32)
-    assert_exact_inputs(ops["rp"], ops["ci"], ops["va"], B, extra=bias, scale=2.0)
-    Cref = oracle_spmm(ops["rp"], ops["ci"], ops["va"], B).astype(np.float64)
-    p, seed, offset = 0.5, 0x1234567, 11
-    keep = dropout_keep(m * k, p, seed, offset).reshape(m, k)
-    assert 0.45 < keep.mean() < 0.55
+    B, bias, keep, Cref = _epilogue_inputs(ops, pattern, kind, k)
+    bf16 = carrier.startswith("bf16")
+    Bd = _t(B, torch.bfloat16 if bf16 else None)
+    if bf16:
+        assert torch.equal(Bd.float(), _t(B))
+    bias_d, flat = offset_view(bias, opt["bias_off"], torch.float32, DEV) if opt.get("bias_off") else (_t(bias), None)
+    assert bias_d.data_ptr() % 16 == 4 * opt.get("bias_off", 0)
+    p, seed, offset = EPILOGUE_DROPOUT
     empty = np.diff(ops["rp"]) == 0
+    assert empty.sum() >= 2
     for e in EPILOGUES:
-        Z = Cref + (bias.astype(np.float64)[None, :] if e.get("bias") else 0.0)
-        if e.get("relu"):
-            Z = np.maximum(Z, 0.0)
-        if e.get("dropout"):
-            Z = np.where(keep, 2.0 * Z, 0.0)
-        C = adj.matmul_raw(_t(B), out=torch.full((m, k), float("nan"), device=DEV), bias=_t(bias) if e.get("bias") else None,
-                           relu=bool(e.get("relu")), dropout=(p, seed, offset) if e.get("dropout") else None).cpu().numpy()
-        assert_exact(C, Z.astype(np.float32), (plan, k, e))
-        act_bias = np.maximum(bias, 0) if e.get("relu") else bias
-        want = np.broadcast_to(act_bias if e.get("bias") else np.zeros(k, np.float32), (m, k))
-        if e.get("dropout"):
-            want = np.where(keep, 2 * want, 0)
-        assert np.array_equal(C[empty], want[empty]), (plan, k, e)
+        ref64 = epilogue_reference(Cref, bias if e.get("bias") else None, bool(e.get("relu")), keep if e.get("dropout") else None, 2.0)
+        ref = ref64.astype(np.float32)
+        assert np.array_equal(ref.astype(np.float64), ref64)      # an fp32 number: a bf16 result is rounded once, from it
+        kw = dict(bias=bias_d if e.get("bias") else None, relu=bool(e.get("relu")), dropout=(p, seed, offset) if e.get("dropout") else None)
+        C = adj.matmul_raw(Bd, out=torch.full((m, k), float("nan"), device=DEV), **kw).cpu().numpy()
+        assert_exact(C, ref, (cid, e))
+        want = np.broadcast_to(epilogue_reference(np.zeros((1, k)), bias if e.get("bias") else None, bool(e.get("relu")), None, 2.0), (m, k))
+        want = np.where(keep, 2.0 * want, 0.0) if e.get("dropout") else want
+        assert np.array_equal(C[empty], want[empty].astype(np.float32)), (cid, e)
+        if bf16:
+            C16 = adj.matmul_raw(Bd, out=torch.full((m, k), float("nan"), device=DEV, dtype=torch.bfloat16), **kw)
+            assert C16.dtype == torch.bfloat16
+            assert_exact(C16.float().cpu().numpy(), torch.from_numpy(ref).to(torch.bfloat16).float().numpy(), (cid, e, "bf16 result"))
+    if flat is not None:
+        assert guards_intact(flat, bias_d), cid
+    if carrier == "bf16":
+        want = "gcn::spmm_group_bf16_weighted_kernel<" if kind == "int" else "gcn::spmm_group_bf16_kernel<"
+        name = adj.main_kernel(k, True, dtype=torch.bfloat16)
+        assert name.startswith(want), (cid, name)
+    if pattern == "group_dup":
+        assert adj.narrow_slices_for(k) == 0, cid                 # the plan's own slice set at every width
 
 
 @pytest.mark.parametrize("weighted", [False, True], ids=["value_free", "weighted"])

@@ -541,6 +541,11 @@ def exact_pattern(name):
         rp, ci, _ = banded_csr(n, 150, 3, seed=5, hub=(777, 2600))
         rp, ci = reshape_rows(rp, ci, n, seed=48, spare=(777,))
         rp, ci = dup(rp, ci, 6)
+    elif name == "lds_all":                              # every entry inside its panel's 128 x 512 window: nothing is left for
+        m = n = 2000                                     # the accumulate pass.  No hub row (exempt from HUB_MIN): 1000 distinct
+        rp, ci, _ = banded_csr(n, 100, 0, seed=3)        # columns cannot lie inside a 512-column window; empty rows it has
+        rp, ci = reshape_rows(rp, ci, n, seed=52)
+        rp, ci = dup(rp, ci, 9)
     elif name == "mfma":
         m = n = 2500
         rp, ci, _ = dense_band_csr(n, 200, 0.6, seed=4, sparse_from=1700)
@@ -559,7 +564,8 @@ def exact_pattern(name):
     else:
         raise KeyError(name)
     lens = np.diff(rp)
-    assert lens.max() >= HUB_MIN and lens.max() < 32768 and (lens <= (1 if "diag" in name else 0)).sum() >= 2, name
+    assert (lens.max() >= HUB_MIN or name == "lds_all") and lens.max() < 32768, name
+    assert (lens <= (1 if "diag" in name else 0)).sum() >= 2, name
     _EXACT_PATTERNS[name] = (rp, ci, m, n)
     return _EXACT_PATTERNS[name]
 
@@ -596,3 +602,45 @@ EXACT_CASES = [("unsliced", "int", (4, 8, 15, 16, 36, 100, 128, 256)),
 WIDE_CASES = [("unsliced", "wide", (4, 8, 15, 16, 36, 100, 128, 256)),
               ("group", "wide", (16, 41, 128)), ("group_dup", "wide_factored", (16, 41, 128)),
               ("vcsr", "wide", (64,)), ("col16", "wide_factored", (64,)), ("lds", "wide", (64, 100)), ("mfma", "wide", (36, 128))]
+
+
+# ---- the fused epilogue C = dropout(act(A.B + bias)) in exact arithmetic (test_exact_cpu.py, test_exact_gpu.py) ----
+EPILOGUES = [dict(bias=True), dict(relu=True), dict(bias=True, relu=True), dict(bias=True, relu=True, dropout=True), dict(dropout=True)]
+EPILOGUE_DROPOUT = (0.5, 0x1234567, 11)                # p (scale 1 / (1 - p) = 2 exactly), seed, offset (no multiple of 4)
+
+
+def epilogue_reference(Cref64, bias, relu, keep, scale, u_row=None):
+    """dropout(act(C* + bias)) in fp64, in the order of include/gcn_spmm.h: [row factor,] bias, ReLU, mask, scale.
+    bias [k] or None; keep [m x k] bool (util.dropout_keep, the independent Philox twin) or None: no dropout; kept
+    elements are multiplied by `scale`.  u_row [m]: Cref64 holds the sums BEFORE the row factor (what a value-free
+    kernel accumulates from u_col * B); the factor goes on first, the bias after it."""
+    Z = np.asarray(Cref64, np.float64)
+    if u_row is not None:
+        Z = Z * np.asarray(u_row, np.float64)[:, None]
+    if bias is not None:
+        Z = Z + np.asarray(bias, np.float64)[None, :]
+    if relu:
+        Z = np.maximum(Z, 0.0)
+    if keep is not None:
+        Z = np.where(keep, scale * Z, 0.0)
+    return Z
+
+
+def epilogue_inputs(m, n, k):
+    """the operands of one exact epilogue case beside the matrix -> (B [n x k] integers in [-8, 8], bias [k] integers in
+    [-8, 8], keep [m x k] at p = 0.5): the same on the CPU, where their discrimination is proven, and on the GPU"""
+    p, seed, offset = EPILOGUE_DROPOUT
+    B = int_features(n, k, seed=3000 + k)
+    bias = np.random.default_rng(k).integers(-8, 9, k).astype(np.float32)
+    keep = dropout_keep(m * k, p, seed, offset).reshape(m, k)
+    return B, bias, keep
+
+
+# (pattern, kind, widths) of every case of test_exact_gpu.py::test_exact_epilogue; the 9-slice plan runs
+# EPILOGUE_NINE_SLICES[pattern] of them again
+EXACT_EPILOGUE_CASES = [("unsliced", "int", (4, 8, 15, 16, 36, 41, 64, 100, 128, 256)),
+                        ("group_dup", "pow2", (16, 21, 32, 40, 41, 64, 128, 136, 260)),
+                        ("group_dup", "int", (16, 32, 40, 41, 64, 128, 136, 260)),
+                        ("vcsr", "int", (64,)), ("col16", "pow2", (64,)), ("lds", "int", (64, 100)),
+                        ("mfma", "int", (36, 64, 128)), ("lds_all", "int", (64, 100))]
+EPILOGUE_NINE_SLICES = {"group_dup": (16, 64, 128)}
