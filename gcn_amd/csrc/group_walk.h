@@ -34,7 +34,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // trailing s_nop keeps the compiler's next instruction off the data registers until the store has read them,
 // cdna_hip_programming.md §5.7.)
 // GCN_ABLATE (development builds only, tools/ablate_group.sh: wrong results, exact costs): bit 0 no partial-row stores,
-// bit 1 no row-end handling, bit 2 no stream loads after the first run, bit 3 partial rows at a stride of one tile;
+// bit 1 no row-end handling, bit 2 no stream loads after the first run (value-free: every load reads the chunk's first
+// run), bit 3 partial rows at a stride of one tile;
 // weighted walk (r04): bit 4 the value stream read from its first 4 KiB only (cache-resident: its bytes without its
 // traffic), bit 5 no value broadcast (every lane multiplies by its OWN entry's value), bit 6 adds instead of FMAs — these
 // seven act on both row formats; bit 7 the value-free walk WITHOUT the LDS ring, bit 8 the weighted walk WITH it (these
@@ -58,9 +59,20 @@ __device__ __forceinline__ void store_row_piece(float* dst, const f32x4& t) {
 
 // A lane's share of a row is four accumulator units (Unit: what one add handles — an fp32, or a pair for the packed
 // instructions) and leaves as kPieces 16-byte pieces (piece i: columns 4i .. 4i + 3 of the share).
+// kStage: runs of 64 entries whose stream words the value-free walk fetches together (group_walk below).  fp32: 8, a whole
+// chunk at the default T = 512 (124 VGPRs against 112 with the next run alone, four waves per SIMD either way).  bf16: 8
+// would take 136 VGPRs and the fourth wave, 4 takes 128 and keeps it — Reddit-shaped, whole SpMM, k = 128 / 256: fp32
+// 2.68 -> 2.51 / 5.47 -> 5.17 ms at 8 (2.54 / 5.22 at 4); bf16 1.80 -> 1.67 / 3.50 -> 3.37 at 4 (1.68 / 3.42 at 8):
+// profiles/stream_stage_measure.log, registers in profiles/stream_stage_registers.log.  (GCN_GROUP_STAGE, development
+// builds: one length for both.)
+#ifdef GCN_GROUP_STAGE
+#define GCN_ROW_STAGE(N) GCN_GROUP_STAGE
+#else
+#define GCN_ROW_STAGE(N) N
+#endif
 struct RowF32 {
   typedef float Unit;
-  static constexpr int kLaneCols = 4, kTileCols = 64, kElemBytes = 4, kPieces = 1;
+  static constexpr int kLaneCols = 4, kTileCols = 64, kElemBytes = 4, kPieces = 1, kStage = GCN_ROW_STAGE(8);
   static __device__ __forceinline__ void widen(const uint4& raw, Unit (&w)[4]) {
     w[0] = __uint_as_float(raw.x); w[1] = __uint_as_float(raw.y); w[2] = __uint_as_float(raw.z); w[3] = __uint_as_float(raw.w);
   }
@@ -68,7 +80,7 @@ struct RowF32 {
 };
 struct RowBf16 {
   typedef f32x2 Unit;
-  static constexpr int kLaneCols = 8, kTileCols = 128, kElemBytes = 2, kPieces = 2;
+  static constexpr int kLaneCols = 8, kTileCols = 128, kElemBytes = 2, kPieces = 2, kStage = GCN_ROW_STAGE(4);
   static __device__ __forceinline__ Unit pair(unsigned word) {    // columns 2i and 2i + 1 of a word
     return Unit{__uint_as_float(word << 16), __uint_as_float(word & 0xFFFF0000u)};
   }
@@ -269,7 +281,7 @@ struct RowSink {
   }
 };
 
-template <class Row, bool VALS, bool RING, bool BIG>
+template <class Row, bool VALS, bool RING, bool BIG, int STAGE = Row::kStage>
 __device__ __forceinline__ void
 group_walk(const unsigned short* __restrict__ stream, const float* __restrict__ vals, const int2* __restrict__ chunk_meta,
            const void* __restrict__ table, float* __restrict__ Cv, float* __restrict__ P,
@@ -281,34 +293,62 @@ group_walk(const unsigned short* __restrict__ stream, const float* __restrict__ 
   // (GCN_ABLATE bit 3: partial rows of a tile contiguous — a layout experiment)
   GroupChunk<Row, 4, 16, BIG> ch(table, nchunks, dyn, tb.bx, tb.col_tile, k, (GCN_ABLATE & 8) ? (size_t)TC : (size_t)k, ld);
   if (ch.none()) return;
+  // the stream is stored in runs of 64 entries, lane-major (slicing.hip, group_phys): lane f reads its entries of
+  // four consecutive blocks with one 8-byte load (16 bytes for the values)
+  const u32x2* __restrict__ sp = reinterpret_cast<const u32x2*>(stream + (size_t)ch.c * T) + ch.f;
+  // The stream words of the runs ahead, w[0] the current run's; a run's end shifts them down by one (static indices:
+  // registers).  Value-free: a STAGE of runs, fetched back to back at the chunk's start and again where a stage ends
+  // inside the chunk (T > 64 * STAGE).  Vector-memory results return in order, and with one load per run — issued in
+  // front of that run's first gathers, from HBM for a large stream — the compiler's wait in front of the gathers was
+  // vmcnt(0): every run began by sitting out a stream load, eight times per chunk.  Fetched together the loads of a stage
+  // overlap into ONE such wait: main kernel, Reddit-shaped k = 128, 2.30 -> 2.14 ms, and tile-major order, which reads
+  // the whole stream from HBM once per tile, 2.44 -> 2.18 (profiles/stream_stage_gate.log).  Runs past the chunk's end
+  // read its last run again (nothing is read beyond the chunk; the last chunk ends the buffer).  Weighted: the next run
+  // only, a whole run ahead of its use, beside its values (126 VGPRs: no room for a stage of 16-byte value words).
+  constexpr int NW = VALS ? 2 : STAGE;
+  static_assert(NW >= 2 && (NW & (NW - 1)) == 0, "a stage is a power of two of runs, at least two");
+  const int last_run = (GCN_ABLATE & 4) ? 0 : T / 64 - 1;
+  u32x2 w[NW];
+  auto load_stage = [&](int r0) {
+#pragma unroll
+    for (int i = 0; i < NW; ++i) w[i] = stream_load(sp + 16 * (r0 + i < last_run ? r0 + i : last_run), stream_nt);
+  };
   ch.open(chunk_meta, Cv, P);
   RowSink<Row, 4, 16, RING> sink(ch, block_ring<Row, 4, 16, RING>());
   const int f = ch.f, base = ch.base;
   const unsigned row_bytes = ch.row_bytes, foff = ch.foff;
   const char* Bb = ch.Bb;
 
-  // the stream is stored in runs of 64 entries, lane-major (slicing.hip, group_phys): lane f reads its entries of
-  // four consecutive blocks with one 8-byte load (16 bytes for the values)
-  const u32x2* __restrict__ sp = reinterpret_cast<const u32x2*>(stream + (size_t)ch.c * T) + f;
   // (GCN_ABLATE bit 4: every chunk reads the values of the first one, 1 KiB)
   const f32x4* __restrict__ vp = VALS ? reinterpret_cast<const f32x4*>(vals + ((GCN_ABLATE & 16) ? 0 : (size_t)ch.c * T)) + f : nullptr;
   typename Row::Unit acc[4] = {};
-  u32x2 eq = stream_load(sp, stream_nt), eq_nx = eq;
+  if constexpr (VALS) { w[0] = stream_load(sp, stream_nt); w[1] = w[0]; }
+  else load_stage(0);
   f32x4 vq = {0.f, 0.f, 0.f, 0.f}, vq_nx = vq;
   if constexpr (VALS) { vq = (GCN_ABLATE & 16) ? vp[0] : stream_load(vp, stream_nt); vq_nx = vq; }
   unsigned fl = 0;
 #pragma unroll 1
   for (int blk = 0; blk < T / 16; ++blk) {
     const int j = blk & 3;
-    if (j == 0 && blk + 4 < T / 16 && !(GCN_ABLATE & 4)) {      // the next run, a whole run ahead of its use
-      const int nx = (blk / 4 + 1) * 16;
-      eq_nx = stream_load(sp + nx, stream_nt);
-      if constexpr (VALS) vq_nx = (GCN_ABLATE & 16) ? vp[nx & 63] : stream_load(vp + nx, stream_nt);
+    if constexpr (VALS) {
+      if (j == 0 && blk + 4 < T / 16 && !(GCN_ABLATE & 4)) {    // the next run, a whole run ahead of its use
+        const int nx = (blk / 4 + 1) * 16;
+        w[1] = stream_load(sp + nx, stream_nt);
+        vq_nx = (GCN_ABLATE & 16) ? vp[nx & 63] : stream_load(vp + nx, stream_nt);
+      }
+    } else {
+      if (blk != 0 && (blk & (4 * NW - 1)) == 0) {              // a stage ends: the next one
+        load_stage(blk >> 2);
+      }
     }
-    const unsigned e = ((j & 2 ? eq.y : eq.x) >> (16 * (j & 1))) & 0xFFFFu;
+    const unsigned e = ((j & 2 ? w[0].y : w[0].x) >> (16 * (j & 1))) & 0xFFFFu;
     int vbits = 0;                                              // this lane's entry's value; step u takes lane u's
     if constexpr (VALS) vbits = __builtin_bit_cast(int, j == 0 ? vq.x : j == 1 ? vq.y : j == 2 ? vq.z : vq.w);
-    if (j == 3) { eq = eq_nx; vq = vq_nx; }
+    if (j == 3) {
+#pragma unroll
+      for (int i = 0; i + 1 < NW; ++i) w[i] = w[i + 1];
+      vq = vq_nx;
+    }
     const int rowoff = (int)(__umul24((e & 0x7FFFu) + (unsigned)base, row_bytes));
     fl = e >> 15;
     uint4 b[16];

@@ -78,7 +78,15 @@ bool group_fused_fixup() { static const bool v = env_on("GCN_AMD_GROUP_FUSED_FIX
 // (profiles/r02zg_chunk_length_slices.log); a matrix of a few rounds — a rank's row block of an 8-way partition: 1.7
 // rounds at 512 — leaves the last round partly empty, so the length is picked from the multiples of 64 in [256, 1024]
 // that fill whole rounds best (ties: the one closest to 512).
+// GCN_AMD_GROUP_T (development / tests, read once per process): that length for every plan — a multiple of 64 in
+// [64, 1024], anything else is ignored — so that small graphs reach the stage boundaries of the walk (group_walk.h).
 int group_chunk(long long entries, int cu) {
+  static const int forced = [] {
+    const char* e = std::getenv("GCN_AMD_GROUP_T");
+    const int t = e ? std::atoi(e) : 0;
+    return t >= 64 && t <= 1024 && t % 64 == 0 ? t : 0;
+  }();
+  if (forced) return forced;
   if (cu <= 0) cu = 256;
   const double round = (double)cu * 4.0;
   if ((double)entries / (16.0 * 512.0) >= 6.0 * round) return 512;
