@@ -561,6 +561,19 @@ def exact_pattern(name):
         rp, ci, _ = sym_norm_graph(n, 1200000, seed=12)
         rp, ci = reshape_rows(rp, ci, n, seed=51, empty=0.02, hub=(9999, 3000), keep_diagonal=name.endswith("_diag"))
         rp, ci = dup(rp, ci, 2)
+    elif name == "auto_diag":                            # the smallest square matrix on which the automatic rules act: n * 128 B
+        m = n = 32769                                    # is just above one L2 (4 slices, narrow set of 2: tests/stress_plan.py),
+        lens = np.random.default_rng(53).poisson(140, m)  # mean degree >= 128, a stored diagonal in every row
+        lens[np.random.default_rng(54).random(m) < 0.02] = 0
+        lens[[1, m - 1]] = 0
+        lens[12345] = 3000
+        rp, ci = random_rows_csr(m, n, lens, seed=55)
+        rows = np.concatenate([np.repeat(np.arange(m), np.diff(rp)), np.arange(m)])
+        cols = np.concatenate([ci.astype(np.int64), np.arange(m)])
+        order = np.lexsort((cols, rows))
+        rp = np.zeros(m + 1, np.int64)
+        rp[1:] = np.cumsum(np.bincount(rows, minlength=m))
+        rp, ci = rp.astype(np.int32), cols[order].astype(np.int32)
     else:
         raise KeyError(name)
     lens = np.diff(rp)
