@@ -32,6 +32,7 @@ NORM_SYM, NORM_ROW = 0, 1    # GCN_NORM_SYM / GCN_NORM_ROW (gcn_csr_normalize_f3
 SPGEMM_WAVE_MAX = 512        # GCN_SPGEMM_WAVE_MAX: rows of at most this many possible columns are taken by a wave (gcn_spgemm_*_csr)
 SPGEMM_BLOCK_MAX = 8192      # GCN_SPGEMM_BLOCK_MAX: ... by a workgroup with a table in LDS; above, a dense accumulator
 SPGEMM_DENSE_BLOCKS = 16     # GCN_SPGEMM_DENSE_BLOCKS: the workgroups (and accumulators in the workspace) of the dense rows
+SAMPLED_DOT_WS_BYTES = 16    # GCN_SAMPLED_DOT_WS_BYTES (gcn_csr_sampled_dot_f32)
 KNN_K_MAX = 64               # GCN_KNN_K_MAX: the most neighbours gcn_knn_f32 returns per query
 KNN_TILE_Q = 64              # GCN_KNN_TILE_Q: queries of a workgroup
 KNN_TILE_C = 64              # GCN_KNN_TILE_C: candidates of a tile; the candidate range is split in whole tiles
@@ -152,6 +153,8 @@ SIGNATURES = {
                                             ctypes.c_size_t, _c_p]),
     "gcn_spgemm_fill_csr": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p,
                                            _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_csr_sampled_dot_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i32, _c_p, _c_p, _c_p, _c_i32,
+                                               _c_i32, _c_i32, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_knn_splits": (ctypes.c_int, [_c_i32, _c_i32, _c_i32]),
     "gcn_knn_ws_bytes": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i32, ctypes.POINTER(ctypes.c_size_t)]),
     "gcn_knn_f32": (ctypes.c_int, [_c_p, ctypes.c_int64, _c_p, ctypes.c_int64, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32,

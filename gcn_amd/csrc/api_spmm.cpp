@@ -9,7 +9,7 @@
 #include <algorithm>
 #include <cstring>
 
-#define GCN_VERSION_STR "0.3.0"
+#define GCN_VERSION_STR "0.4.0"
 
 using namespace gcn;
 
@@ -421,7 +421,22 @@ int gcn_spgemm_fill_csr(const int32_t* a_rowptr, const int32_t* a_col, const flo
                             ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
 }
 
-static_assert(kKnnKMax == GCN_KNN_K_MAX && kKnnTileQ == GCN_KNN_TILE_Q && kKnnTileC == GCN_KNN_TILE_C, "include/gcn_spmm.h");
+static_assert(kSampledDotWsBytes == GCN_SAMPLED_DOT_WS_BYTES, "include/gcn_spmm.h");
+
+int gcn_csr_sampled_dot_f32(const int32_t* p_rowptr, const int32_t* p_col, int32_t mp, int32_t np, int32_t nnz_p,
+                            const int32_t* x_rowptr, const int32_t* x_col, const float* x_val, int32_t nnz_x,
+                            const int32_t* y_rowptr, const int32_t* y_col, const float* y_val, int32_t nnz_y, int32_t w,
+                            int32_t x_by_col, float* out, void* ws, size_t ws_bytes, void* stream) {
+  if (mp < 0 || np < 0 || nnz_p < 0 || nnz_x < 0 || nnz_y < 0 || w < 0) return GCN_ERR_INVALID_ARG;
+  if (mp == 0 || nnz_p == 0) return GCN_OK;
+  if (!p_rowptr || !p_col || !x_rowptr || !y_rowptr || (nnz_x > 0 && !x_col) || (nnz_y > 0 && !y_col) || !out || !ws ||
+      ws_bytes < kSampledDotWsBytes)
+    return GCN_ERR_INVALID_ARG;
+  return launch_csr_sampled_dot(p_rowptr, p_col, mp, np, nnz_p, x_rowptr, x_col, x_val, nnz_x, y_rowptr, y_col, y_val, nnz_y, w,
+                                x_by_col, out, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+static_assert(kKnnKMax == GCN_KNN_K_MAX &&kKnnTileQ == GCN_KNN_TILE_Q && kKnnTileC == GCN_KNN_TILE_C, "include/gcn_spmm.h");
 
 namespace {
 // the sizes every knn entry point refuses: negative, k outside [1, GCN_KNN_K_MAX], or more workgroups / part keys than fit

@@ -259,6 +259,15 @@ hipError_t launch_spgemm_fill(const int* a_rowptr, const int* a_col, const float
                               const int* b_rowptr, const int* b_col, const float* b_val, int n, int nnz_b,
                               const int* out_rowptr, int* out_col, float* out_val, void* ws, hipStream_t st);
 
+// sampled_dot.hip — the product of two CSR matrices sampled on a pattern: out[e] for the entry e = (i, j) of P is the dot
+// product of X's row i (x_by_col: j) and Y's row j (x_by_col: i) over their common columns in [0, w), the products added in
+// X's entry order; Y's rows ascend strictly (plan-free, no atomics: see the file's header and include/gcn_spmm.h).  A wave per
+// row of P, a 256-thread workgroup per row of more than kSampleLongRow entries; ws: kSampledDotWsBytes (a flag).
+constexpr size_t kSampledDotWsBytes = 16;
+hipError_t launch_csr_sampled_dot(const int* p_rowptr, const int* p_col, int mp, int np, int nnz_p, const int* x_rowptr,
+                                  const int* x_col, const float* x_val, int nnz_x, const int* y_rowptr, const int* y_col,
+                                  const float* y_val, int nnz_y, int w, int x_by_col, float* out, void* ws, hipStream_t st);
+
 // knn.hip — brute-force k nearest neighbours of fp32 rows by squared Euclidean distance (plan-free, no floating-point
 // atomics: see the file's header and include/gcn_spmm.h).  A 256-thread workgroup owns kKnnTileQ queries and streams its part
 // of the candidates through in tiles of kKnnTileC; `eff_splits` = knn_effective_splits(...) parts per query block, merged by

@@ -4,6 +4,8 @@
 * ``GraphConvolution2`` — (AX)W layer  (gcn6.py:151-199)
 * ``GCN``               — the 2-layer model with gcn6's four preprocessing steps in ``fit``
                           (renumber → schedule → to GPU → permute features; gcn6.py:262-410)
+* ``HGNNConv`` / ``HGNN`` — the hypergraph convolution and the two-layer model of pyhgnn/models/HGNN.py, optionally with
+                          learnable hyperedge weights through ``HypergraphLaplacian``
 
 Same constructor arguments, parameter initialisation, layer-order rule (A(XW) for layer 2 on
 pubmed/flickr, (AX)W otherwise, gcn6.py:214-218), per-layer ``xw / af / bi`` timers and training
@@ -24,6 +26,7 @@ from torch.nn.parameter import Parameter
 from . import preprocess, reorder, timers
 from .aggregate import aggregate
 from .attention import gat_edge_softmax
+from .spgemm import HypergraphLaplacian
 from .spmm import CsrAdjacency, _SpmmFunction, dropout_rows, gather_rows, spmm
 
 
@@ -296,6 +299,81 @@ class GraphSAGE(nn.Module):
         hidden = f" -> {first.out_features}" if len(self.layers) > 1 else ""
         return (f"GraphSAGE ({first.in_features}{hidden} -> {last.out_features}, layers={len(self.layers)}, "
                 f"aggr={first.aggr}, dropout={self.dropout})")
+
+
+class HGNNConv(nn.Module):
+    """The hypergraph convolution of HGNN (Feng et al. 2019; pyhgnn/models/HGNN.py ``HGNN_conv``): ``G · (x·W + b)`` — the
+    bias is added BEFORE the aggregation, unlike GraphConvolution.  ``weight`` [in x out] and ``bias`` [out] are drawn from
+    uniform(±1/sqrt(out)) as the reference does.
+
+    forward(x, G, values=None): ``G`` is a CsrAdjacency (``hypergraph_laplacian``, or ``HypergraphLaplacian(...).adj``);
+    ``values``: nnz fp32 values that replace G's own and may require a gradient (``spmm(G, ·, values=values)``: G must be
+    a mutable adjacency).  Returns the output only, not the reference's timing tuple."""
+
+    def __init__(self, in_features, out_features, with_bias=True):
+        super().__init__()
+        self.in_features, self.out_features = int(in_features), int(out_features)
+        self.weight = Parameter(torch.empty(self.in_features, self.out_features))
+        if with_bias:
+            self.bias = Parameter(torch.empty(self.out_features))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        stdv = 1.0 / math.sqrt(self.weight.size(1))
+        self.weight.data.uniform_(-stdv, stdv)
+        if self.bias is not None:
+            self.bias.data.uniform_(-stdv, stdv)
+
+    def forward(self, x, G, values=None):
+        x = x.matmul(self.weight)
+        if self.bias is not None:
+            x = x + self.bias
+        return spmm(G, _spmm_operand(x), values=values)
+
+    def __repr__(self):
+        return f"HGNNConv ({self.in_features} -> {self.out_features})"
+
+
+class HGNN(nn.Module):
+    """The two-layer hypergraph network of pyhgnn/models/HGNN.py: ``hgc1 -> relu -> dropout -> hgc2``, with the reference's
+    parameter names (``hgc1.weight``, ``hgc1.bias``, ``hgc2.weight``, ``hgc2.bias``), so its checkpoints load strictly.
+
+    forward(x, G) returns the logits only (the reference returns them with four timings).  Dropout follows
+    ``self.training``; the reference calls ``F.dropout(x, p)`` without the flag, which is ALWAYS on, evaluation included.
+    ``G`` is a CsrAdjacency (``hypergraph_laplacian``).  learn_edge_weights=True: ``G`` is a ``HypergraphLaplacian`` and the
+    model owns ``log_edge_weight`` [n_edges], zeros at the start; the hyperedge weights are ``w = exp(log_edge_weight)``,
+    which stay positive and whose gradient never dies, and ``G.values(w)`` is computed once per forward and used by both
+    layers, so the loss reaches the weights through the Laplacian (``n_edges`` is then required)."""
+
+    def __init__(self, in_ch, n_class, n_hid, dropout=0.5, learn_edge_weights=False, n_edges=None):
+        super().__init__()
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f"HGNN: dropout must lie in [0, 1), not {dropout!r}")
+        self.dropout = float(dropout)
+        self.hgc1 = HGNNConv(in_ch, n_hid)
+        self.hgc2 = HGNNConv(n_hid, n_class)
+        self.learn_edge_weights = bool(learn_edge_weights)
+        if self.learn_edge_weights:
+            if isinstance(n_edges, bool) or not isinstance(n_edges, int) or n_edges < 1:
+                raise ValueError(f"HGNN: learn_edge_weights=True needs n_edges, an int >= 1, not {n_edges!r}")
+            self.log_edge_weight = Parameter(torch.zeros(n_edges))
+
+    def forward(self, x, G):
+        values = None
+        if self.learn_edge_weights:
+            if not isinstance(G, HypergraphLaplacian):
+                raise TypeError("HGNN: with learn_edge_weights=True, G must be a HypergraphLaplacian")
+            values = G.values(torch.exp(self.log_edge_weight))
+            G = G.adj
+        x = F.relu(self.hgc1(x, G, values))
+        x = F.dropout(x, self.dropout, training=self.training)
+        return self.hgc2(x, G, values)
+
+    def __repr__(self):
+        return (f"HGNN ({self.hgc1.in_features} -> {self.hgc1.out_features} -> {self.hgc2.out_features}, "
+                f"dropout={self.dropout}, learn_edge_weights={self.learn_edge_weights})")
 
 
 class GCN(nn.Module):

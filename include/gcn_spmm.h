@@ -555,6 +555,40 @@ int gcn_spgemm_fill_csr(const int32_t* a_rowptr_dev, const int32_t* a_col_dev, c
                         int32_t* out_col_dev, float* out_val_dev /* NULL iff both values are */, void* ws, size_t ws_bytes,
                         void* stream);
 
+/* The product of two CSR matrices SAMPLED ON A PATTERN (an SDDMM with sparse operands): one fp32 value for every entry of a
+ * pattern P [mp x np], given as p_rowptr_dev [mp + 1] and p_col_dev [nnz_p].  X and Y are two CSR operands over a common column
+ * range [0, w): int32 row pointers and columns, fp32 values, a NULL value pointer meaning ones.  It is what flows back through
+ * gcn_spgemm_*: dC/dA on A's pattern, dC/dB on B's, and — on C's own pattern with X = A and Y = B transposed — the values of
+ * C, bit for bit as gcn_spgemm_fill_csr gives them (for a fixed output entry every entry of A's row contributes at most one
+ * product, so "A's entries in entry order" is the same fold order in both), with no count, no scan and no host read.
+ * Plan-free under the rules of the merge above: the caller's arrays and workspace only, one memset node and two kernels (one
+ * linear chain under graph capture), no allocation, no host read of device data, no synchronisation, no floating-point
+ * atomic; the same bits at every call.  Every access is a 4-byte one and 4-byte alignment is enough.  The contract, exact and
+ * meant to be re-implemented (tests/sampled_dot_ref.py is the numpy twin):
+ *   ROWS.  For the entry e = (i, j) of P: (xr, yr) = (i, j) when x_by_col == 0 and (j, i) otherwise.  So X has mp rows and Y
+ *   has np when x_by_col == 0, and the other way round otherwise (x_rowptr_dev and y_rowptr_dev hold one more word).
+ *   VALUE.  out_dev[e] = the sum of x_t * Y[yr, col_t] over the entries t of X's row xr, IN ENTRY ORDER, for which Y's row yr
+ *   holds the column col_t.  Each product is fl32(x * y), one rounding, never contracted into an FMA; the value is the first
+ *   product, then acc = fl32(acc + product) left to right ("the first product", not 0 + product: a lone -0.0 stays -0.0).  No
+ *   match gives +0.0 (all bits zero).  NaN and infinities propagate as the arithmetic gives them.
+ *   PRECONDITIONS.  Y's rows ascend strictly by column (sorted, no repeats: what gcn_csr_coalesce_* and the transpose of such
+ *   a matrix return).  Where a row of Y does not, the values of the entries that use it are unspecified; every search still
+ *   terminates and nothing is accessed out of bounds.  X is free: any order, and repeated columns are more products.
+ *   OUT OF RANGE.  An X column outside [0, w) contributes nothing.  A P column outside [0, np) gives +0.0.  A row pointer pair
+ *   of X or Y outside [0, nnz] or descending makes that row empty; one of P means nothing is written for that row of P.
+ * The work of an entry is the length of its X row.  A row of P of at most GCN_SAMPLE_LONG_ROW entries is taken by one wave,
+ * a longer one by a 256-thread workgroup; an X row of any length is walked 16 entries at a time by a 16-lane group (rows of
+ * at most 64 entries) or 64 at a time by a wave, never by one lane.
+ * ws: GCN_SAMPLED_DOT_WS_BYTES of device scratch, owned by the call until it has run.  Negative sizes, a null pointer where
+ * data is required (x_col_dev / y_col_dev may be null when the operand has no entries) or a short workspace:
+ * GCN_ERR_INVALID_ARG, before any GPU work.  mp == 0 or nnz_p == 0: GCN_OK, nothing written. */
+#define GCN_SAMPLED_DOT_WS_BYTES 16
+int gcn_csr_sampled_dot_f32(const int32_t* p_rowptr_dev, const int32_t* p_col_dev, int32_t mp, int32_t np, int32_t nnz_p,
+                            const int32_t* x_rowptr_dev, const int32_t* x_col_dev, const float* x_val_dev /* may be NULL */,
+                            int32_t nnz_x, const int32_t* y_rowptr_dev, const int32_t* y_col_dev,
+                            const float* y_val_dev /* may be NULL */, int32_t nnz_y, int32_t w, int32_t x_by_col, float* out_dev,
+                            void* ws, size_t ws_bytes, void* stream);
+
 /* Brute-force k nearest neighbours: for every query row x_i (fp32 [q x d], row stride ldx >= d floats) the k candidate rows
  * y_j (fp32 [n x d], row stride ldy >= d) of smallest squared Euclidean distance.  The q x n distance matrix is never written
  * to memory.  Plan-free: the caller's arrays and workspace, two kernels enqueued on the stream, no allocation, no host read
