@@ -19,7 +19,10 @@
 
 #include "reorder.h"
 
-namespace gcn { bool csr_ok(const int32_t* rowptr, const int32_t* col, int32_t n, int32_t nnz); }
+namespace gcn {
+bool csr_ok(const int32_t* rowptr, const int32_t* col, int32_t n, int32_t nnz);
+bool csr_ok(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t n, int32_t nnz);    // m rows, columns below n
+}
 using gcn::csr_ok;
 using gcn::auto_chunk_nnz;
 using gcn::auto_slices;
@@ -323,7 +326,10 @@ void csr2tile(int* rowPtr, int* colIdx, float* vals, int m, int n, int nnz, int*
     std::fprintf(stderr, "libgcnspmm: csr2tile: tm must be 8 (got %d); nothing packed\n", tm);
     return;
   }
-  if (!csr_checked("csr2tile", rowPtr, colIdx, m, nnz)) return;
+  if (!csr_ok(rowPtr, colIdx, m, n, nnz)) {            // rows bounded by m, columns by n (flexspmm gathers B's row colIdx[e])
+    std::fprintf(stderr, "libgcnspmm: csr2tile: malformed CSR input (m=%d n=%d nnz=%d); nothing packed\n", m, n, nnz);
+    return;
+  }
   SortedCsr sc;
   sort_rows(rowPtr, colIdx, vals, m, nnz, &sc);
   std::vector<float> u;

@@ -8,13 +8,16 @@
 
 namespace gcn {
 
-bool csr_ok(const int32_t* rowptr, const int32_t* col, int32_t n, int32_t nnz) {
-  if (n < 0 || nnz < 0 || !rowptr || (nnz > 0 && !col)) return false;
-  if (rowptr[0] != 0 || rowptr[n] != nnz) return false;
-  for (int32_t i = 0; i < n; ++i) if (rowptr[i + 1] < rowptr[i]) return false;
+// m rows, columns in [0, n)
+bool csr_ok(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t n, int32_t nnz) {
+  if (m < 0 || n < 0 || nnz < 0 || !rowptr || (nnz > 0 && !col)) return false;
+  if (rowptr[0] != 0 || rowptr[m] != nnz) return false;
+  for (int32_t i = 0; i < m; ++i) if (rowptr[i + 1] < rowptr[i]) return false;
   for (int32_t e = 0; e < nnz; ++e) if (col[e] < 0 || col[e] >= n) return false;
   return true;
 }
+
+bool csr_ok(const int32_t* rowptr, const int32_t* col, int32_t n, int32_t nnz) { return csr_ok(rowptr, col, n, n, nnz); }
 
 }  // namespace gcn
 

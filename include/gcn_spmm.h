@@ -819,7 +819,9 @@ void rabbit(int* rowPtr, int* col, float* vals, int* vomp, int m, int n, int nnz
  * floats, segVoMap nnz ints, grouped_tailSeg/next_seg 256 ints (gcn6.py:334-339).
  * n_segs[0] = nnz / 9, or one less so that its lowest bit tells flexspmm whether the values are u[r]*u[c] (n_segs is the
  * only scalar gcn6 carries from csr2tile to flexspmm, gcn6.py:353-366); needs nnz >= m + 19, else nothing is packed
- * and n_segs[0] = 0.  Encoding documented in INTEGRATION.md. */
+ * and n_segs[0] = 0.  The matrix is m x n: the row pointer has m + 1 entries and every column index lies in [0, n) —
+ * anything else is refused with one line that names m, n and nnz (n_segs[0] = 0, every buffer untouched).  Encoding
+ * documented in INTEGRATION.md. */
 void csr2tile(int* rowPtr, int* colIdx, float* vals, int m, int n, int nnz,
               int* vo_mp, int* segVoMap, int* seg_rowPtr, float* segNzCV,
               int* grouped_tailSeg, int* next_seg, int tm, int* n_segs);

@@ -136,17 +136,23 @@ def _group_format_offsets(n, n_segs, S):
     return (16 + 2 * nchunks_ub + 3) // 4 * 4, (total_ub * 2 + 15) // 16 * 4
 
 
-def _unpack_group_format(seg_rowPtr, segNzCV, segVoMap, n):
+def _np(t):
+    return t.numpy() if hasattr(t, "numpy") else np.asarray(t)
+
+
+def _unpack_group_format(seg_rowPtr, segNzCV, segVoMap, n, n_segs=None):
     """decode what csr2tile packs for graphs that qualify for slicing (api_dropin.cpp: the group-kernel format)
-    → (header dict, rows, cols, vals or None, u or None, logical stream)"""
-    h = seg_rowPtr.numpy()[:16]
+    → (header dict, rows, cols, vals or None, u or None, logical stream).  n_segs: what csr2tile returned (default: the
+    buffers were shrunk by it, as gcn6.py:353-354 does)"""
+    seg_rowPtr, segNzCV, segVoMap = _np(seg_rowPtr), _np(segNzCV), _np(segVoMap)
+    h = seg_rowPtr[:16]
     hd = dict(magic=int(h[0]), S=int(h[1]), T=int(h[2]), w=int(h[3]), nchunks=int(h[4]), nfix=int(h[5]),
               value_free=int(h[6]), total=int(h[7]), nnz=int(h[8]))
     total, S, w = hd["total"], hd["S"], hd["w"]
     p = np.arange(total, dtype=np.int64)
     r = p & 63
     phys = (p & ~np.int64(63)) + (r & 15) * 4 + (r >> 4)              # lane-major runs of 64 entries
-    stream = segNzCV.numpy().view(np.uint16)[:total][phys]
+    stream = segNzCV.view(np.uint16)[:total][phys]
     ends, off = (stream >> 15).astype(np.int64), (stream & 0x7FFF).astype(np.int64)
     vrow = np.concatenate([[0], np.cumsum(ends)[:-1]])
     assert int(ends.sum()) == S * n                                    # every virtual row ends exactly once
@@ -154,19 +160,57 @@ def _unpack_group_format(seg_rowPtr, segNzCV, segVoMap, n):
     rows, cols = (vrow % n)[real], ((vrow // n) * w + off)[real]
     vals = u = None
     if hd["value_free"]:
-        u = segVoMap.numpy()[:n].view(np.float32)
+        u = segVoMap[:n].view(np.float32)
     else:
-        voff = _group_format_offsets(n, seg_rowPtr.numel() // 9, S)[1]
-        vals = segNzCV.numpy()[voff: voff + total][phys][real]
-        assert np.all(segNzCV.numpy()[voff: voff + total][phys][~real] == 0)      # padding weighs nothing
+        voff = _group_format_offsets(n, len(seg_rowPtr) // 9 if n_segs is None else n_segs, S)[1]
+        vals = segNzCV[voff: voff + total][phys][real]
+        assert np.all(segNzCV[voff: voff + total][phys][~real] == 0)      # padding weighs nothing
     return hd, rows, cols, vals, u, (vrow, ends, real)
+
+
+def _check_group_format(seg_rowPtr, segNzCV, segVoMap, n, n_segs, rowptr, col, val, S, value_free):
+    """what csr2tile's group format must obey for the n x n matrix (rowptr, col, val), rows in any order, entries repeated
+    or not: the header; unpacking gives back the matrix as a multiset of (row, col, val) — value-free: u[row] * u[col] is
+    the value; the chunk metadata and the list of cut rows are the stream's → the header"""
+    seg_rowPtr = _np(seg_rowPtr)
+    nnz = len(col)
+    hd, rows, cols, vals, u, (vrow, ends, real) = _unpack_group_format(seg_rowPtr, segNzCV, segVoMap, n, n_segs)
+    assert hd["magic"] == 0x47434E47 and hd["S"] == S and hd["T"] == 512 and hd["w"] == (n + S - 1) // S
+    assert hd["nnz"] == nnz and hd["total"] == hd["nchunks"] * 512 and hd["nchunks"] % 64 == 0
+    assert hd["value_free"] == (1 if value_free else 0)
+    assert int(n_segs) % 2 == hd["value_free"]                            # the flag flexspmm reads on the host
+    in_rows = np.repeat(np.arange(n), np.diff(rowptr))
+    assert len(rows) == nnz
+    if value_free:
+        oi, oo = np.lexsort((col, in_rows)), np.lexsort((cols, rows))
+        assert np.array_equal(rows[oo], in_rows[oi]) and np.array_equal(cols[oo], col[oi])     # the same pattern
+        assert np.allclose(u[rows[oo]] * u[cols[oo]], val[oi], rtol=1e-6, atol=0)
+    else:
+        oi, oo = np.lexsort((val, col, in_rows)), np.lexsort((vals, cols, rows))
+        assert np.array_equal(rows[oo], in_rows[oi]) and np.array_equal(cols[oo], col[oi])
+        assert np.array_equal(vals[oo], val[oi])                                               # the values, exactly
+    # chunk metadata: chunk c starts inside virtual row vrow[c*T]; flag = the row began in an earlier chunk
+    meta = seg_rowPtr[16: 16 + 2 * hd["nchunks"]].reshape(-1, 2)
+    starts = np.arange(hd["nchunks"], dtype=np.int64) * 512
+    assert np.array_equal(meta[:, 0] >> 1, vrow[starts])
+    began = np.concatenate([[0], (ends[starts[1:] - 1] == 0).astype(np.int64)])
+    assert np.array_equal(meta[:, 0] & 1, began)
+    assert np.array_equal(meta[:, 1], (vrow[starts] // n) * (hd["w"] + 1))
+    # fix list: exactly the rows that begin in chunk c-1 and run on into chunk c
+    foff = _group_format_offsets(n, int(n_segs), hd["S"])[0]
+    fix = seg_rowPtr[foff: foff + 4 * hd["nfix"]].reshape(-1, 4)
+    cut = np.flatnonzero(began[1:] == 1) + 1
+    first_of_row = np.concatenate([[0], np.flatnonzero(ends[:-1] == 1) + 1])              # start entry of every vrow
+    cut = cut[first_of_row[vrow[starts[cut]]] // 512 == cut - 1]
+    assert hd["nfix"] == len(cut) and np.array_equal(np.sort(fix[:, 1]), cut)
+    assert np.array_equal(fix[np.argsort(fix[:, 1]), 0], vrow[starts[cut]])
+    return hd, (vrow, ends, real)
 
 
 def test_csr2tile_group_format_is_the_matrix():
     """host-only: for a graph that qualifies for slicing csr2tile packs the group kernels' format — slice-major 15-bit
     stream in lane-major runs, chunk metadata, list of cut rows; value-free when the values are u[r]*u[c], with the
     values beside the stream otherwise.  Unpacking gives back exactly the input matrix."""
-    import scipy.sparse as sp
     import torch
     from gcn_amd import dropin
     from util import sym_norm_graph
@@ -174,7 +218,6 @@ def test_csr2tile_group_format_is_the_matrix():
     rowptr, col, val = sym_norm_graph(n, 1200000, seed=2)
     nnz = len(col)
     assert nnz // n >= 128
-    A = sp.csr_matrix((val, col, rowptr), shape=(n, n))
     rng = np.random.default_rng(0)           # hand the rows over UNSORTED: csr2tile sorts them itself
     col_u, val_u = col.copy(), val.copy()
     for r in range(n):
@@ -187,35 +230,7 @@ def test_csr2tile_group_format_is_the_matrix():
         seg_rowPtr, segNzCV, segVoMap, tail, nxt, n_segs = dropin.csr2tile(
             torch.from_numpy(rowptr.copy()), torch.from_numpy(col_u.copy()), torch.from_numpy(vin), n, n, nnz,
             torch.arange(n, dtype=torch.int32))
-        hd, rows, cols, vals, u, (vrow, ends, real) = _unpack_group_format(seg_rowPtr, segNzCV, segVoMap, n)
-        assert hd["magic"] == 0x47434E47 and hd["S"] == 2 and hd["T"] == 512 and hd["w"] == (n + 1) // 2
-        assert hd["nnz"] == nnz and hd["total"] == hd["nchunks"] * 512 and hd["nchunks"] % 64 == 0
-        assert hd["value_free"] == (0 if weighted else 1)
-        Bm = sp.coo_matrix((np.ones(len(rows)), (rows, cols)), shape=(n, n)).tocsr()
-        Bm.sort_indices()
-        assert np.array_equal(Bm.indptr, A.indptr) and np.array_equal(Bm.indices, A.indices)   # the same pattern
-        if weighted:
-            got = sp.coo_matrix((vals, (rows, cols)), shape=(n, n)).tocsr(); got.sort_indices()
-            ref = sp.csr_matrix((vin, col_u, rowptr), shape=(n, n)); ref.sort_indices()
-            assert np.array_equal(got.data, ref.data)                                          # the values, exactly
-        else:
-            assert np.allclose(u[rows] * u[cols], np.asarray(A[rows, cols]).ravel(), rtol=1e-6, atol=0)
-        # chunk metadata: chunk c starts inside virtual row vrow[c*T]; flag = the row began in an earlier chunk
-        meta = seg_rowPtr.numpy()[16: 16 + 2 * hd["nchunks"]].reshape(-1, 2)
-        starts = np.arange(hd["nchunks"], dtype=np.int64) * 512
-        assert np.array_equal(meta[:, 0] >> 1, vrow[starts])
-        began = np.concatenate([[0], (ends[starts[1:] - 1] == 0).astype(np.int64)])
-        assert np.array_equal(meta[:, 0] & 1, began)
-        assert np.array_equal(meta[:, 1], (vrow[starts] // n) * (hd["w"] + 1))
-        # fix list: exactly the rows that begin in chunk c-1 and run on into chunk c
-        foff = _group_format_offsets(n, int(n_segs[0]), hd["S"])[0]
-        assert int(n_segs[0]) % 2 == hd["value_free"]                         # the flag flexspmm reads on the host
-        fix = seg_rowPtr.numpy()[foff: foff + 4 * hd["nfix"]].reshape(-1, 4)
-        cut = np.flatnonzero(began[1:] == 1) + 1
-        first_of_row = np.concatenate([[0], np.flatnonzero(ends[:-1] == 1) + 1])              # start entry of every vrow
-        cut = cut[first_of_row[vrow[starts[cut]]] // 512 == cut - 1]
-        assert hd["nfix"] == len(cut) and np.array_equal(np.sort(fix[:, 1]), cut)
-        assert np.array_equal(fix[np.argsort(fix[:, 1]), 0], vrow[starts[cut]])
+        _check_group_format(seg_rowPtr, segNzCV, segVoMap, n, int(n_segs[0]), rowptr, col_u, vin, S=2, value_free=not weighted)
 
 
 def test_csr2seg_cmajor_resolves_prints_and_touches_nothing(capfd):
