@@ -9,7 +9,7 @@ Drop-in shared objects for gcn6.py live in gcn_amd/dropin/ (see INTEGRATION.md).
 """
 from ._lib import GcnAmdError, LIB_PATH, DROPIN_DIR, load as load_library  # noqa: F401
 from .spmm import CsrAdjacency, spmm, gather_rows, dropout_rows, install, uninstall  # noqa: F401
-from .attention import edge_softmax, gat_edge_softmax, segment_sum  # noqa: F401
+from .attention import edge_softmax, gat_edge_softmax, sddmm_heads, segment_sum, spmm_heads  # noqa: F401
 from .aggregate import aggregate  # noqa: F401
 from .sampling import Block, NeighborLoader, sample_blocks, sample_neighbors  # noqa: F401
 from .subgraph import ClusterLoader, RandomWalkLoader, Subgraph, induced_subgraph, random_walk  # noqa: F401

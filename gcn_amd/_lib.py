@@ -128,6 +128,19 @@ SIGNATURES = {
     "gcn_gat_edge_softmax_backward_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p, ctypes.c_float, _c_p, _c_p,
                                                              _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_segment_sum_csr_f32": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_heads_ws_bytes": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i32, ctypes.POINTER(ctypes.c_size_t)]),
+    "gcn_edge_softmax_heads_csr_f32": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_edge_softmax_heads_backward_csr_f32": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t,
+                                                               _c_p]),
+    "gcn_gat_edge_softmax_heads_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, ctypes.c_float, _c_p, _c_p,
+                                                          ctypes.c_size_t, _c_p]),
+    "gcn_gat_edge_softmax_heads_backward_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, ctypes.c_float,
+                                                                   _c_p, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_segment_sum_heads_csr_f32": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_spmm_heads_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p,
+                                              ctypes.c_size_t, _c_p]),
+    "gcn_sddmm_heads_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t,
+                                               _c_p]),
     "gcn_aggregate_csr": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p,
                                          ctypes.c_size_t, _c_p]),
     "gcn_aggregate_backward_csr": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_p,

@@ -5,9 +5,19 @@ fused with GAT scores, and CSR row sums of a per-entry array — the autograd su
     p = gcn_amd.gat_edge_softmax(adj, a_dst, a_src, 0.2)     # scores leaky_relu(a_dst[row] + a_src[col]), never stored
     out = gcn_amd.spmm(adj, h, values=p)                     # the weighted aggregation
 
+All heads of a multi-head layer go through one pass (gcn_amd/csrc/multihead.hip): the same functions take 2-D operands
+with an entry's or a node's H heads contiguous, and the aggregation and its score counterpart are
+
+    p = gcn_amd.edge_softmax(adj, scores)                    # scores [nnz, H] -> p [nnz, H]
+    p = gcn_amd.gat_edge_softmax(adj, a_dst, a_src, 0.2)     # a_dst [m, H], a_src [n, H] -> p [nnz, H]
+    out = gcn_amd.spmm_heads(adj, x, p)                      # x [n, H*F]: out[r, hF+j] = sum_e p[e, h] x[col[e], hF+j]
+    s = gcn_amd.sddmm_heads(adj, a, b, heads)                # s[e, h] = <a[row(e), head h], b[col[e], head h]>
+
 The kernels take no plan and only enqueue, so all of this runs inside a captured step.  Unlike ``torch.softmax`` a row
 whose scores are all -inf gets zeros, not NaN (a fully masked row stays usable).  There is no CPU path: CPU tensors raise.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -83,18 +93,23 @@ def _loose_holder(device):
 def segment_sum(rowptr, x, perm=None):
     """out[r] = sum of x[e] over rowptr[r] <= e < rowptr[r+1] (x[perm[e]] with an int32 permutation `perm`): plain CSR row
     sums of a per-entry fp32 device array, in a fixed order (no atomics) — gcn_segment_sum_csr_f32.  No autograd.
+    x may be 2-D [nnz, H] (an entry's heads contiguous): the result is [m, H], from one pass over the entries.
     Its scratch is kept per (device, stream), so calls on different streams do not share one."""
     if not (isinstance(rowptr, torch.Tensor) and rowptr.dim() == 1 and rowptr.numel() >= 1):
         raise ValueError("segment_sum: rowptr must be a 1-D tensor of m + 1 entries")
-    if not isinstance(x, torch.Tensor) or x.dim() != 1:
-        raise ValueError("segment_sum: x must be a 1-D tensor with one entry per stored entry")
-    if perm is not None and (not isinstance(perm, torch.Tensor) or perm.shape != x.shape):
+    if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2) or (x.dim() == 2 and x.shape[1] < 1):
+        raise ValueError("segment_sum: x must be a 1-D tensor with one entry per stored entry, or 2-D [nnz, H]")
+    if perm is not None and (not isinstance(perm, torch.Tensor) or perm.shape != x.shape[:1]):
         raise ValueError("segment_sum: perm must have one entry per entry of x")
     if not (rowptr.is_cuda and x.is_cuda and (perm is None or perm.is_cuda)):
         raise _lib.GcnAmdError("segment_sum needs CUDA/HIP tensors (no CPU path in gcn_amd)")
     if x.dtype != torch.float32 or rowptr.dtype != torch.int32 or (perm is not None and perm.dtype != torch.int32):
         raise _lib.GcnAmdError("segment_sum: x must be fp32, rowptr and perm int32")
     m = int(rowptr.numel()) - 1
+    if x.dim() == 2:                                     # [nnz, H] -> [m, H]: one pass for all heads
+        out = torch.empty(m, x.shape[1], dtype=torch.float32, device=x.device)
+        return _segment_sum_heads_raw(_loose_holder(x.device), rowptr.contiguous(), m, x.detach().contiguous(),
+                                      perm.contiguous() if perm is not None else None, out)
     out = torch.empty(m, dtype=torch.float32, device=x.device)
     return _segment_sum_raw(_loose_holder(x.device), rowptr.contiguous(), m, x.detach().contiguous(),
                             perm.contiguous() if perm is not None else None, out)
@@ -136,9 +151,13 @@ def edge_softmax(adj, scores):
     """p[e] = exp(scores[e] - max_row) / sum_row exp(scores[e'] - max_row) over the stored entries of each row of `adj`
     (any CsrAdjacency: only its rowptr is used, its values are ignored).  `scores`: 1-D fp32 device tensor of nnz entries
     in adj's CSR order; differentiable.  Empty rows have no entries; an all -inf row gets zeros (torch.softmax: NaN); a NaN
-    stays in its row.  ValueError for a wrong shape, GcnAmdError for a CPU tensor or a dtype other than fp32."""
+    stays in its row.  `scores` may be 2-D [nnz, H]: the softmax is taken per head, all heads in one pass (p is [nnz, H]).
+    ValueError for a wrong shape, GcnAmdError for a CPU tensor or a dtype other than fp32."""
     if not isinstance(adj, CsrAdjacency):
         raise TypeError("edge_softmax: adj must be a CsrAdjacency")
+    if isinstance(scores, torch.Tensor) and scores.dim() == 2:           # [nnz, H]: all heads in one pass
+        _entry_tensor_heads(adj, scores, "edge_softmax: scores")
+        return _EdgeSoftmaxHeadsFunction.apply(adj, scores)
     _entry_tensor(adj, scores, "edge_softmax: scores")
     return _EdgeSoftmaxFunction.apply(adj, scores)
 
@@ -195,11 +214,268 @@ def gat_edge_softmax(adj, a_dst, a_src, negative_slope=0.2):
     """The edge softmax of the GAT scores s[e] = leaky_relu(a_dst[row(e)] + a_src[col(e)], negative_slope), computed inside
     the kernel: the nnz-sized score array is never written.  a_dst: [m] fp32, a_src: [n] fp32, both differentiable.
     `adj` must have been made with mutable_values=True — only because grad_a_src sums ds by column through the transpose
-    permutation such an adjacency keeps (and the result is meant for spmm(adj, h, values=p), which needs it anyway)."""
+    permutation such an adjacency keeps (and the result is meant for spmm(adj, h, values=p), which needs it anyway).
+    With a_dst [m, H] and a_src [n, H] all heads run in one pass, p is [nnz, H] (for spmm_heads) and any adjacency will do."""
     if not isinstance(adj, CsrAdjacency):
         raise TypeError("gat_edge_softmax: adj must be a CsrAdjacency")
+    if isinstance(a_dst, torch.Tensor) and isinstance(a_src, torch.Tensor) and (a_dst.dim() == 2 or a_src.dim() == 2):
+        heads = int(a_dst.shape[-1])                     # a_dst [m, H], a_src [n, H]: all heads in one pass, any adjacency
+        _node_tensors_heads([(a_dst, adj.m, heads, "gat_edge_softmax: a_dst"), (a_src, adj.n, heads, "gat_edge_softmax: a_src")])
+        return _GatEdgeSoftmaxHeadsFunction.apply(adj, a_dst, a_src, float(negative_slope))
     if not adj.mutable_values:
         raise _lib.GcnAmdError("gat_edge_softmax needs an adjacency made with mutable_values=True (grad_a_src is summed "
                                "through the transpose permutation only a mutable adjacency keeps)")
     _node_tensors([(a_dst, adj.m, "gat_edge_softmax: a_dst"), (a_src, adj.n, "gat_edge_softmax: a_src")])
     return _GatEdgeSoftmaxFunction.apply(adj, a_dst, a_src, float(negative_slope))
+
+
+# ---- all heads in one pass (gcn_amd/csrc/multihead.hip) ---------------------------------------------------------------------------
+def _heads_workspace(owner, m, nnz, heads, k, device):
+    """one scratch per adjacency for the head-batched kernels (gcn_heads_ws_bytes: a flag and the chunk partials of long
+    rows), allocated at the first call and grown when a call needs more — so before a capture, with the transposed pattern"""
+    need = ctypes.c_size_t(0)
+    _lib.check(_lib.load().gcn_heads_ws_bytes(int(m), int(nnz), int(heads), int(k), ctypes.byref(need)), "gcn_heads_ws_bytes")
+    ws = getattr(owner, "_heads_ws", None)
+    if ws is None or ws.numel() < need.value or ws.device != device:
+        ws = torch.empty(need.value, dtype=torch.uint8, device=device)
+        owner._heads_ws = ws
+    return ws
+
+
+def _heads_tpattern(adj):
+    """(rowptr int32 [n + 1], source row of each entry int32 [nnz], its index in adj's order int32 [nnz]) of the transposed
+    pattern, built once per adjacency (on the device) and kept on it"""
+    tp = getattr(adj, "_heads_tp", None)
+    if tp is None:
+        trp, trow, perm = adj._transposed_pattern()
+        tp = adj._heads_tp = (trp.contiguous(), trow.contiguous(), perm.to(torch.int32).contiguous())
+    return tp
+
+
+def _entry_tensor_heads(adj, t, what):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != adj.nnz or t.shape[1] < 1:
+        raise ValueError(f"{what} must be a 2-D tensor [nnz = {adj.nnz}, H] in CSR order")
+    if not t.is_cuda:
+        raise _lib.GcnAmdError(f"{what} must be a CUDA/HIP tensor (no CPU path in gcn_amd)")
+    if t.dtype != torch.float32:
+        raise _lib.GcnAmdError(f"{what} must be fp32")
+
+
+def _node_tensors_heads(items):
+    """shapes of all of them first (ValueError), then device and dtype (GcnAmdError)"""
+    for t, rows, width, what in items:
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != rows or t.shape[1] != width or width < 1:
+            raise ValueError(f"{what} must be a 2-D tensor [{rows}, {width}]")
+    for t, _rows, _width, what in items:
+        if not t.is_cuda:
+            raise _lib.GcnAmdError(f"{what} must be a CUDA/HIP tensor (no CPU path in gcn_amd)")
+        if t.dtype != torch.float32:
+            raise _lib.GcnAmdError(f"{what} must be fp32")
+
+
+def _segment_sum_heads_raw(owner, rowptr, rows, x, perm, out):
+    nnz, heads = int(x.shape[0]), int(x.shape[1])
+    if rows == 0 or nnz == 0:
+        return out.zero_()
+    ws = _heads_workspace(owner, rows, nnz, heads, heads, x.device)
+    with torch.cuda.device(x.device):
+        st = _lib.load().gcn_segment_sum_heads_csr_f32(_ptr(rowptr), rows, nnz, heads, _ptr(x),
+                                                       _ptr(perm) if perm is not None else None, _ptr(out), _ptr(ws),
+                                                       ws.numel(), _stream_ptr(x.device))
+    _lib.check(st, "gcn_segment_sum_heads_csr_f32")
+    return out
+
+
+def _spmm_heads_raw(adj, rowptr, idx, perm, rows, vals, x, heads):
+    """out [rows, k] of gcn_spmm_heads_csr_f32 over (rowptr, idx, perm); vals [nnz, H], x [*, k]"""
+    k = int(x.shape[1])
+    out = torch.empty(rows, k, dtype=torch.float32, device=x.device)
+    if rows == 0 or adj.nnz == 0:
+        return out.zero_()
+    ws = _heads_workspace(adj, max(adj.m, adj.n), adj.nnz, heads, k, x.device)
+    with torch.cuda.device(x.device):
+        st = _lib.load().gcn_spmm_heads_csr_f32(_ptr(rowptr), _ptr(idx), _ptr(perm) if perm is not None else None, rows,
+                                                adj.nnz, heads, k, _ptr(vals), _ptr(x), _ptr(out), _ptr(ws), ws.numel(),
+                                                _stream_ptr(x.device))
+    _lib.check(st, "gcn_spmm_heads_csr_f32")
+    return out
+
+
+def _sddmm_heads_raw(adj, a, b, heads):
+    k = int(a.shape[1])
+    out = torch.empty(adj.nnz, heads, dtype=torch.float32, device=a.device)
+    if adj.m == 0 or adj.nnz == 0:
+        return out
+    ws = _heads_workspace(adj, max(adj.m, adj.n), adj.nnz, heads, k, a.device)
+    with torch.cuda.device(a.device):
+        st = _lib.load().gcn_sddmm_heads_csr_f32(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, heads, k, _ptr(a), _ptr(b),
+                                                 _ptr(out), _ptr(ws), ws.numel(), _stream_ptr(a.device))
+    _lib.check(st, "gcn_sddmm_heads_csr_f32")
+    return out
+
+
+class _EdgeSoftmaxHeadsFunction(torch.autograd.Function):
+    """p [nnz, H] = per-head softmax of scores [nnz, H] over each row's entries; saves p"""
+
+    @staticmethod
+    def forward(ctx, adj, scores):
+        s = scores.detach().contiguous()
+        p = torch.empty_like(s)
+        heads = int(s.shape[1])
+        if adj.m and adj.nnz:
+            ws = _heads_workspace(adj, max(adj.m, adj.n), adj.nnz, heads, heads, s.device)
+            with torch.cuda.device(s.device):
+                st = _lib.load().gcn_edge_softmax_heads_csr_f32(_ptr(adj.rowptr), adj.m, adj.nnz, heads, _ptr(s), _ptr(p),
+                                                                _ptr(ws), ws.numel(), _stream_ptr(s.device))
+            _lib.check(st, "gcn_edge_softmax_heads_csr_f32")
+        ctx.adj = adj
+        ctx.save_for_backward(p)
+        return p
+
+    @staticmethod
+    def backward(ctx, g):
+        (p,) = ctx.saved_tensors
+        adj = ctx.adj
+        g = g.contiguous()
+        ds = torch.empty_like(p)
+        heads = int(p.shape[1])
+        if adj.m and adj.nnz:
+            ws = _heads_workspace(adj, max(adj.m, adj.n), adj.nnz, heads, heads, p.device)
+            with torch.cuda.device(p.device):
+                st = _lib.load().gcn_edge_softmax_heads_backward_csr_f32(_ptr(adj.rowptr), adj.m, adj.nnz, heads, _ptr(p),
+                                                                         _ptr(g), _ptr(ds), _ptr(ws), ws.numel(),
+                                                                         _stream_ptr(p.device))
+            _lib.check(st, "gcn_edge_softmax_heads_backward_csr_f32")
+        return None, ds
+
+
+class _GatEdgeSoftmaxHeadsFunction(torch.autograd.Function):
+    """p [nnz, H] = per-head edge softmax of leaky_relu(a_dst[row, h] + a_src[col, h]); the backward recomputes the scores:
+    grad_a_dst [m, H] = row sums of ds (same kernel), grad_a_src [n, H] = the segment sum of ds over the transposed pattern
+    through its permutation (one writer per output, no atomics; one gather brings an entry's H values)."""
+
+    @staticmethod
+    def forward(ctx, adj, a_dst, a_src, slope):
+        ad, asrc = a_dst.detach().contiguous(), a_src.detach().contiguous()
+        heads = int(ad.shape[1])
+        p = torch.empty(adj.nnz, heads, dtype=torch.float32, device=ad.device)
+        if adj.m and adj.nnz:
+            ws = _heads_workspace(adj, max(adj.m, adj.n), adj.nnz, heads, heads, ad.device)
+            with torch.cuda.device(ad.device):
+                st = _lib.load().gcn_gat_edge_softmax_heads_csr_f32(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, heads,
+                                                                    _ptr(ad), _ptr(asrc), slope, _ptr(p), _ptr(ws), ws.numel(),
+                                                                    _stream_ptr(ad.device))
+            _lib.check(st, "gcn_gat_edge_softmax_heads_csr_f32")
+        ctx.adj, ctx.slope = adj, slope
+        ctx.save_for_backward(ad, asrc, p)
+        return p
+
+    @staticmethod
+    def backward(ctx, g):
+        ad, asrc, p = ctx.saved_tensors
+        adj = ctx.adj
+        dev = p.device
+        heads = int(p.shape[1])
+        g = g.contiguous()
+        ds = torch.empty_like(p)
+        g_dst = torch.empty(adj.m, heads, dtype=torch.float32, device=dev)
+        g_src = torch.empty(adj.n, heads, dtype=torch.float32, device=dev)
+        if not (adj.m and adj.nnz):
+            return None, g_dst.zero_(), g_src.zero_(), None
+        ws = _heads_workspace(adj, max(adj.m, adj.n), adj.nnz, heads, heads, dev)
+        with torch.cuda.device(dev):
+            st = _lib.load().gcn_gat_edge_softmax_heads_backward_csr_f32(
+                _ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, heads, _ptr(ad), _ptr(asrc), ctx.slope, _ptr(p), _ptr(g),
+                _ptr(ds), _ptr(g_dst), _ptr(ws), ws.numel(), _stream_ptr(dev))
+        _lib.check(st, "gcn_gat_edge_softmax_heads_backward_csr_f32")
+        if ctx.needs_input_grad[2]:
+            trp, _trow, tperm = _heads_tpattern(adj)
+            _segment_sum_heads_raw(adj, trp, adj.n, ds, tperm, g_src)
+        else:
+            g_src = None
+        return None, g_dst, g_src, None
+
+
+class _SpmmHeadsFunction(torch.autograd.Function):
+    """out = spmm_heads(adj, x, values); grad x = the same kernel on the transposed pattern (values read through its
+    permutation), grad values = sddmm_heads(grad_out, x)"""
+
+    @staticmethod
+    def forward(ctx, adj, x, values):
+        xd, v = x.detach().contiguous(), values.detach().contiguous()
+        heads = int(v.shape[1])
+        out = _spmm_heads_raw(adj, adj.rowptr, adj.col, None, adj.m, v, xd, heads)
+        ctx.adj, ctx.heads = adj, heads
+        ctx.save_for_backward(xd, v)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xd, v = ctx.saved_tensors
+        adj = ctx.adj
+        g = g.contiguous()
+        gx = gv = None
+        if ctx.needs_input_grad[1]:
+            trp, trow, tperm = _heads_tpattern(adj)
+            gx = _spmm_heads_raw(adj, trp, trow, tperm, adj.n, v, g, ctx.heads)
+        if ctx.needs_input_grad[2]:
+            gv = _sddmm_heads_raw(adj, g, xd, ctx.heads)
+        return None, gx, gv
+
+
+class _SddmmHeadsFunction(torch.autograd.Function):
+    """s = sddmm_heads(adj, a, b); grad a = spmm_heads on the pattern (b weighted by grad s), grad b = spmm_heads on the
+    transposed pattern (a weighted by grad s through the permutation)"""
+
+    @staticmethod
+    def forward(ctx, adj, a, b, heads):
+        ad, bd = a.detach().contiguous(), b.detach().contiguous()
+        ctx.adj, ctx.heads = adj, heads
+        ctx.save_for_backward(ad, bd)
+        return _sddmm_heads_raw(adj, ad, bd, heads)
+
+    @staticmethod
+    def backward(ctx, g):
+        ad, bd = ctx.saved_tensors
+        adj = ctx.adj
+        g = g.contiguous()
+        ga = gb = None
+        if ctx.needs_input_grad[1]:
+            ga = _spmm_heads_raw(adj, adj.rowptr, adj.col, None, adj.m, g, bd, ctx.heads)
+        if ctx.needs_input_grad[2]:
+            trp, trow, tperm = _heads_tpattern(adj)
+            gb = _spmm_heads_raw(adj, trp, trow, tperm, adj.n, g, ad, ctx.heads)
+        return None, ga, gb, None
+
+
+def spmm_heads(adj, x, values):
+    """out[r, hF + j] = sum over the stored entries e of row r of values[e, h] * x[col[e], hF + j]: the aggregation of all H
+    heads in one walk of the adjacency (gcn_spmm_heads_csr_f32).  x: [n, H*F] fp32, head h in columns hF .. hF + F - 1;
+    values: [nnz, H] fp32 in adj's CSR order (adj's own values are ignored; any CsrAdjacency, no plan is used).
+    Differentiable in x (the same kernel on the transposed pattern) and in values (sddmm_heads)."""
+    if not isinstance(adj, CsrAdjacency):
+        raise TypeError("spmm_heads: adj must be a CsrAdjacency")
+    if not isinstance(values, torch.Tensor) or values.dim() != 2 or values.shape[0] != adj.nnz or values.shape[1] < 1:
+        raise ValueError(f"spmm_heads: values must be a 2-D tensor [nnz = {adj.nnz}, H] in CSR order")
+    heads = int(values.shape[1])
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != adj.n or x.shape[1] < heads or x.shape[1] % heads:
+        raise ValueError(f"spmm_heads: x must be a 2-D tensor [n = {adj.n}, H*F] with H = {heads} heads")
+    _node_tensors_heads([(x, adj.n, int(x.shape[1]), "spmm_heads: x")])
+    _entry_tensor_heads(adj, values, "spmm_heads: values")
+    return _SpmmHeadsFunction.apply(adj, x, values)
+
+
+def sddmm_heads(adj, a, b, heads):
+    """s[e, h] = sum over j < F of a[row(e), hF + j] * b[col[e], hF + j] for every stored entry e of adj: per-head dot-product
+    scores (gcn_sddmm_heads_csr_f32).  a: [m, H*F], b: [n, H*F] fp32; returns [nnz, H] in adj's CSR order.  Differentiable in
+    a and b (spmm_heads on the pattern and on its transpose)."""
+    if not isinstance(adj, CsrAdjacency):
+        raise TypeError("sddmm_heads: adj must be a CsrAdjacency")
+    heads = int(heads)
+    if heads < 1:
+        raise ValueError("sddmm_heads: heads must be at least 1")
+    if not isinstance(a, torch.Tensor) or a.dim() != 2 or a.shape[1] < heads or a.shape[1] % heads:
+        raise ValueError(f"sddmm_heads: a must be a 2-D tensor [m = {adj.m}, H*F] with H = {heads} heads")
+    k = int(a.shape[1])
+    _node_tensors_heads([(a, adj.m, k, "sddmm_heads: a"), (b, adj.n, k, "sddmm_heads: b")])
+    return _SddmmHeadsFunction.apply(adj, a, b, heads)

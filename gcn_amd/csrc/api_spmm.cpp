@@ -219,6 +219,96 @@ int gcn_segment_sum_csr_f32(const int32_t* rowptr, int32_t m, int32_t nnz, const
   return launch_segment_sum(rowptr, m, nnz, x, perm, out, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
 }
 
+// Head-batched attention primitives (multihead.hip).  Sizes first — heads, k and nnz * heads < 2^31 before any pointer is
+// looked at — then the empty problem, then the row pointer and the workspace; 1 = return *status.  k = 0: the call takes no k.
+static int heads_args(const int32_t* rowptr, int32_t rows, int32_t nnz, int32_t heads, int32_t k, const void* ws, size_t ws_bytes,
+                      size_t ws_need, int* status) {
+  *status = GCN_ERR_INVALID_ARG;
+  if (rows < 0 || nnz < 0 || heads < 1 || k < 0) return 1;
+  if ((long long)nnz * heads >= (1LL << 31)) return 1;
+  if (k && (k < heads || k % heads != 0 || k > 16 * 65535)) return 1;
+  *status = GCN_OK;
+  if (rows == 0 || nnz == 0) return 1;
+  if (!rowptr || !ws || ws_bytes < ws_need) { *status = GCN_ERR_INVALID_ARG; return 1; }
+  return 0;
+}
+
+int gcn_heads_ws_bytes(int32_t m, int32_t nnz, int32_t heads, int32_t k, size_t* bytes) {
+  int rc;
+  if (!bytes || k < 1) return GCN_ERR_INVALID_ARG;
+  heads_args(nullptr, 0, nnz, heads, k, nullptr, 0, 0, &rc);                  // (the size rules alone)
+  if (rc != GCN_OK || m < 0) return GCN_ERR_INVALID_ARG;
+  const size_t e = heads_edge_workspace_bytes(nnz, heads), s = heads_spmm_workspace_bytes(nnz, k);
+  *bytes = e > s ? e : s;
+  return GCN_OK;
+}
+
+int gcn_edge_softmax_heads_csr_f32(const int32_t* rowptr, int32_t m, int32_t nnz, int32_t heads, const float* scores, float* p,
+                                   void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (heads_args(rowptr, m, nnz, heads, 0, ws, ws_bytes, heads_edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
+  if (!scores || !p) return GCN_ERR_INVALID_ARG;
+  return launch_edge_softmax_heads(rowptr, m, nnz, heads, scores, p, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_edge_softmax_heads_backward_csr_f32(const int32_t* rowptr, int32_t m, int32_t nnz, int32_t heads, const float* p,
+                                            const float* g, float* ds, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (heads_args(rowptr, m, nnz, heads, 0, ws, ws_bytes, heads_edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
+  if (!p || !g || !ds) return GCN_ERR_INVALID_ARG;
+  return launch_edge_softmax_heads_backward(rowptr, m, nnz, heads, p, g, ds, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK
+                                                                                                                     : GCN_ERR_HIP;
+}
+
+int gcn_gat_edge_softmax_heads_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t nnz, int32_t heads,
+                                       const float* a_dst, const float* a_src, float negative_slope, float* p, void* ws,
+                                       size_t ws_bytes, void* stream) {
+  int rc;
+  if (heads_args(rowptr, m, nnz, heads, 0, ws, ws_bytes, heads_edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
+  if (!col || !a_dst || !a_src || !p) return GCN_ERR_INVALID_ARG;
+  return launch_gat_edge_softmax_heads(rowptr, col, m, nnz, heads, a_dst, a_src, negative_slope, p, ws, (hipStream_t)stream) ==
+                 hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_gat_edge_softmax_heads_backward_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t nnz, int32_t heads,
+                                                const float* a_dst, const float* a_src, float negative_slope, const float* p,
+                                                const float* g, float* ds, float* grad_a_dst, void* ws, size_t ws_bytes,
+                                                void* stream) {
+  int rc;
+  if (heads_args(rowptr, m, nnz, heads, 0, ws, ws_bytes, heads_edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
+  if (!col || !a_dst || !a_src || !p || !g || !ds || !grad_a_dst) return GCN_ERR_INVALID_ARG;
+  return launch_gat_edge_softmax_heads_backward(rowptr, col, m, nnz, heads, a_dst, a_src, negative_slope, p, g, ds, grad_a_dst, ws,
+                                                (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_segment_sum_heads_csr_f32(const int32_t* rowptr, int32_t rows, int32_t nnz, int32_t heads, const float* x,
+                                  const int32_t* perm, float* out, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (heads_args(rowptr, rows, nnz, heads, 0, ws, ws_bytes, heads_edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
+  if (!x || !out) return GCN_ERR_INVALID_ARG;
+  return launch_segment_sum_heads(rowptr, rows, nnz, heads, x, perm, out, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK
+                                                                                                                  : GCN_ERR_HIP;
+}
+
+int gcn_spmm_heads_csr_f32(const int32_t* rowptr, const int32_t* idx, const int32_t* perm, int32_t rows, int32_t nnz, int32_t heads,
+                           int32_t k, const float* vals, const float* x, float* out, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (k < 1) return GCN_ERR_INVALID_ARG;
+  if (heads_args(rowptr, rows, nnz, heads, k, ws, ws_bytes, heads_spmm_workspace_bytes(nnz, k), &rc)) return rc;
+  if (!idx || !vals || !x || !out) return GCN_ERR_INVALID_ARG;
+  return launch_spmm_heads(rowptr, idx, perm, rows, nnz, heads, k, vals, x, out, ws, (hipStream_t)stream) == hipSuccess
+             ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_sddmm_heads_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t nnz, int32_t heads, int32_t k,
+                            const float* a, const float* b, float* out, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (k < 1) return GCN_ERR_INVALID_ARG;
+  if (heads_args(rowptr, m, nnz, heads, k, ws, ws_bytes, kHeadsSddmmWsBytes, &rc)) return rc;
+  if (!col || !a || !b || !out) return GCN_ERR_INVALID_ARG;
+  return launch_sddmm_heads(rowptr, col, m, nnz, heads, k, a, b, out, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
 // k, op / dtype and the sizes first; then what an empty problem still needs; 1 = return *status
 static int aggregate_args(int32_t rows_out, int32_t rows_in, int32_t nnz, int32_t dtype, int32_t k, int* status) {
   *status = GCN_OK;

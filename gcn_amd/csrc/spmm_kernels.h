@@ -191,6 +191,28 @@ hipError_t launch_aggregate(const int* rowptr, const int* col, int m, int nnz, c
 hipError_t launch_aggregate_backward(const int* trowptr, const int* trow, const int* tperm, int n, int nnz, const void* g, int bf16,
                                      const int* arg, int k, void* gx, void* ws, hipStream_t st);
 
+// multihead.hip — the attention primitives for H heads in one pass: per-head edge softmax (plain and fused GAT scores) with
+// their backwards, row sums of an [nnz, H] array, the head-weighted SpMM and the per-head SDDMM (plan-free, capturable, no
+// atomics: see the file's header).  Per-entry arrays are [nnz, H] with an entry's heads contiguous, node arrays [rows, H * F]
+// with k = H * F; nnz * H < 2^31.  ws: heads_*_workspace_bytes of device memory (a flag and the long rows' chunk partials).
+size_t heads_edge_workspace_bytes(int nnz, int H);
+size_t heads_spmm_workspace_bytes(int nnz, int k);
+constexpr size_t kHeadsSddmmWsBytes = 16;
+hipError_t launch_edge_softmax_heads(const int* rowptr, int m, int nnz, int H, const float* s, float* p, void* ws, hipStream_t st);
+hipError_t launch_edge_softmax_heads_backward(const int* rowptr, int m, int nnz, int H, const float* p, const float* g, float* ds,
+                                              void* ws, hipStream_t st);
+hipError_t launch_gat_edge_softmax_heads(const int* rowptr, const int* col, int m, int nnz, int H, const float* a_dst,
+                                         const float* a_src, float slope, float* p, void* ws, hipStream_t st);
+hipError_t launch_gat_edge_softmax_heads_backward(const int* rowptr, const int* col, int m, int nnz, int H, const float* a_dst,
+                                                  const float* a_src, float slope, const float* p, const float* g, float* ds,
+                                                  float* grad_a_dst, void* ws, hipStream_t st);
+hipError_t launch_segment_sum_heads(const int* rowptr, int rows, int nnz, int H, const float* x, const int* perm, float* out,
+                                    void* ws, hipStream_t st);
+hipError_t launch_spmm_heads(const int* rowptr, const int* idx, const int* perm, int rows, int nnz, int H, int k, const float* vals,
+                             const float* x, float* out, void* ws, hipStream_t st);
+hipError_t launch_sddmm_heads(const int* rowptr, const int* col, int m, int nnz, int H, int k, const float* a, const float* b,
+                              float* out, void* ws, hipStream_t st);
+
 // sample.hip — uniform neighbour sampling without replacement from the rows of seeds[n_seeds], a pure function of (seed,
 // offset, entry index) (plan-free, no global atomics: see the file's header and include/gcn_spmm.h).  fanout < 0: every entry.
 // out_rowptr [n_seeds + 1] is an INPUT (row i holds min(row length, fanout) entries); ws: kSampleWsBytes of device memory (a

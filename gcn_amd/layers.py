@@ -25,7 +25,7 @@ from torch.nn.parameter import Parameter
 
 from . import preprocess, reorder, timers
 from .aggregate import aggregate
-from .attention import gat_edge_softmax
+from .attention import gat_edge_softmax, spmm_heads
 from .spgemm import HypergraphLaplacian
 from .spmm import CsrAdjacency, _SpmmFunction, dropout_rows, gather_rows, spmm
 
@@ -134,15 +134,22 @@ class GraphAttention(nn.Module):
     included or not, as the caller built it) and its own values are ignored — they are overwritten with p.  Heads are a
     Python loop over that one plan: each head's backward re-lays the values its forward saved, so interleaving is safe.
 
+    ``head_batched=True`` runs all heads in one pass instead (gcn_amd/csrc/multihead.hip): a_dst and a_src
+    as [n, heads] from one batched reduction of h viewed as [n, heads, out_features], p [nnz, heads] from one fused softmax
+    and ``spmm_heads(adj, h, p)`` — one walk of the adjacency per direction that gathers whole heads·out_features-wide rows,
+    no plan and no value refresh, so any CsrAdjacency will do.  Same parameters and state_dict; the results differ from the
+    loop's by rounding only (other summation orders).  The default stays the loop.
+
     Parameters: ``weight`` [in_features, heads·out_features], ``att_dst`` and ``att_src`` [heads, out_features] — Glorot
     uniform, as in the paper's code — and ``bias`` [heads·out_features] (concat) or [out_features] (mean), zeros.
     Under a bf16 autocast region x·W runs in bf16 like any matmul; the scores, the softmax and the weighted SpMM run in
     fp32 (h is widened): there is no bf16 softmax kernel, and p's gradient comes from the fp32 SDDMM."""
 
-    def __init__(self, in_features, out_features, heads=1, concat=True, negative_slope=0.2, with_bias=True):
+    def __init__(self, in_features, out_features, heads=1, concat=True, negative_slope=0.2, with_bias=True, head_batched=False):
         super().__init__()
         self.in_features, self.out_features, self.heads = int(in_features), int(out_features), int(heads)
         self.concat, self.negative_slope = bool(concat), float(negative_slope)
+        self.head_batched = bool(head_batched)
         if self.heads < 1:
             raise ValueError("heads must be at least 1")
         self.weight = Parameter(torch.empty(self.in_features, self.heads * self.out_features))
@@ -170,6 +177,15 @@ class GraphAttention(nn.Module):
         # bf16 (mv is on its lower-precision list), and the scores must be fp32 dot products of the widened h
         with torch.autocast("cuda", enabled=False):
             h = h.float()
+            if self.head_batched:
+                hv = h.view(h.shape[0], self.heads, self.out_features)
+                a_dst = (hv * self.att_dst.float()).sum(-1)
+                a_src = (hv * self.att_src.float()).sum(-1)
+                p = gat_edge_softmax(adj, a_dst, a_src, self.negative_slope)
+                out = spmm_heads(adj, h, p)
+                if not self.concat and self.heads > 1:
+                    out = out.view(h.shape[0], self.heads, self.out_features).mean(1)
+                return out + self.bias.float() if self.bias is not None else out
             outs = []
             for k in range(self.heads):
                 hk = h[:, k * self.out_features:(k + 1) * self.out_features].contiguous()
@@ -185,7 +201,7 @@ class GraphAttention(nn.Module):
 
     def __repr__(self):
         return (f"GraphAttention ({self.in_features} -> {self.out_features}, heads={self.heads}, "
-                f"{'concat' if self.concat else 'mean'})")
+                f"{'concat' if self.concat else 'mean'}{', head-batched' if self.head_batched else ''})")
 
 
 class SAGEConv(nn.Module):

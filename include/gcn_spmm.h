@@ -299,6 +299,56 @@ int gcn_aggregate_backward_csr(const int32_t* trowptr_dev, const int32_t* trow_d
                                int32_t m, int32_t nnz, const void* g, int32_t dtype, const int32_t* arg, int32_t k, void* gx,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* Head-batched attention primitives (multihead.hip): the edge softmax family, the weighted SpMM and the SDDMM for H heads
+ * in one pass over the adjacency.  Plan-free like the two families above: the caller's CSR, one 4-byte memset node and
+ * kernels (legal inside a stream capture), no host read of device data, no atomics, the same bits at every call; any row
+ * length, rows of more than 8192 (softmax family) or 4096 (SpMM, SDDMM) entries are spread over the chip in chunks whose
+ * partials are merged in chunk order.  All operands fp32.
+ *   Layouts.  H = heads >= 1, F columns per head, k = H * F.  Node arrays are [rows, k] row-major and head h owns columns
+ *   hF .. hF + F - 1; per-entry arrays are [nnz, H] in CSR entry order with an entry's heads contiguous; per-node scalars
+ *   are [rows, H].  nnz * H must stay below 2^31.
+ *   Power-of-two H <= 16 is the fast case of the softmax family and the segment sum (a lane owns one head and the row's
+ *   [len, H] block is read as one contiguous stream); any other H walks the row once per head with stride H.  The SpMM and
+ *   the SDDMM use 16-byte accesses when every operand is 16-byte aligned and F % 4 == 0, element accesses otherwise.
+ * ws: device scratch of at least the bytes gcn_heads_ws_bytes reports for (m, nnz, heads, k) — enough for every entry
+ * point below on that pattern and its transpose — 16-byte aligned, owned by the call until it has run.
+ * GCN_ERR_INVALID_ARG: null pointers, negative sizes, heads < 1, k < heads or k % heads != 0 where k is taken,
+ * nnz * heads >= 2^31 (checked before any pointer), k > 16 * 65535, a short workspace.  rows == 0 or nnz == 0: GCN_OK,
+ * nothing is launched and nothing written (as in the edge softmax family: the caller zeroes per-row outputs). */
+int gcn_heads_ws_bytes(int32_t m, int32_t nnz, int32_t heads, int32_t k, size_t* bytes);
+/* p[e, h] = softmax over the entries of row(e), separately per head, of scores[e, h]; the conventions of
+ * gcn_edge_softmax_csr_f32 per (row, head): all -inf gives zeros, a NaN poisons its own (row, head) only.  p may alias scores. */
+int gcn_edge_softmax_heads_csr_f32(const int32_t* rowptr_dev, int32_t m, int32_t nnz, int32_t heads, const float* scores,
+                                   float* p, void* ws, size_t ws_bytes, void* stream);
+/* ds[e, h] = p[e, h] * (g[e, h] - sum over row(e) of p[., h] g[., h]) (row sums in fp64).  ds may alias g. */
+int gcn_edge_softmax_heads_backward_csr_f32(const int32_t* rowptr_dev, int32_t m, int32_t nnz, int32_t heads, const float* p,
+                                            const float* g, float* ds, void* ws, size_t ws_bytes, void* stream);
+/* the same softmax of s[e, h] = leaky_relu(a_dst[row(e), h] + a_src[col[e], h], negative_slope), never stored.
+ * a_dst [m, H], a_src [n, H]. */
+int gcn_gat_edge_softmax_heads_csr_f32(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz, int32_t heads,
+                                       const float* a_dst, const float* a_src, float negative_slope, float* p, void* ws,
+                                       size_t ws_bytes, void* stream);
+/* its backward: ds [nnz, H] (times the leaky_relu derivative, the slope at 0) and grad_a_dst [m, H] = row sums of ds.
+ * grad_a_src [n, H] is gcn_segment_sum_heads_csr_f32 of ds over the transposed pattern with its permutation. */
+int gcn_gat_edge_softmax_heads_backward_csr_f32(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz,
+                                                int32_t heads, const float* a_dst, const float* a_src, float negative_slope,
+                                                const float* p, const float* g, float* ds, float* grad_a_dst, void* ws,
+                                                size_t ws_bytes, void* stream);
+/* out[r, h] = sum over the entries e of row r of x[perm ? perm[e] : e, h], carried in fp64 (0 for an empty row). */
+int gcn_segment_sum_heads_csr_f32(const int32_t* rowptr_dev, int32_t rows, int32_t nnz, int32_t heads, const float* x,
+                                  const int32_t* perm_dev, float* out, void* ws, size_t ws_bytes, void* stream);
+/* out[r, hF + j] = sum over the entries e of row r of vals[perm ? perm[e] : e, h] * x[idx[e], hF + j].  Forward: idx = col,
+ * perm = NULL.  Gradient with respect to x: the transposed pattern (rowptr = trowptr, idx = the source row of each entry,
+ * perm = the entry's index in the forward's order).  out [rows, k]; x has a row for every value of idx. */
+int gcn_spmm_heads_csr_f32(const int32_t* rowptr_dev, const int32_t* idx_dev, const int32_t* perm_dev, int32_t rows, int32_t nnz,
+                           int32_t heads, int32_t k, const float* vals, const float* x, float* out, void* ws, size_t ws_bytes,
+                           void* stream);
+/* out[e, h] = sum over j < F of a[row(e), hF + j] * b[col[e], hF + j]: per-head dot-product scores, and the gradient of
+ * the SpMM above with respect to vals (a = grad_out, b = x).  The summation order of an (entry, head) depends on F and on
+ * the aligned / element form only. */
+int gcn_sddmm_heads_csr_f32(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz, int32_t heads, int32_t k,
+                            const float* a, const float* b, float* out, void* ws, size_t ws_bytes, void* stream);
+
 /* Uniform neighbour sampling without replacement from the rows of a CSR matrix (GraphSAGE's mini-batch sampler).  Plan-free
  * like the aggregation family: the caller's CSR, one memset node and kernels, no allocation, no host read of device data, no
  * global atomics; every output element has one writer, so a call gives the same bits every time.  The stored values are
