@@ -5,8 +5,9 @@ fused with GAT scores, and CSR row sums of a per-entry array — the autograd su
     p = gcn_amd.gat_edge_softmax(adj, a_dst, a_src, 0.2)     # scores leaky_relu(a_dst[row] + a_src[col]), never stored
     out = gcn_amd.spmm(adj, h, values=p)                     # the weighted aggregation
 
-All heads of a multi-head layer go through one pass (gcn_amd/csrc/multihead.hip): the same functions take 2-D operands
-with an entry's or a node's H heads contiguous, and the aggregation and its score counterpart are
+All heads of a multi-head layer go through one pass: the same functions take 2-D operands with an entry's or a node's H
+heads contiguous (the 1-D forms are their H = 1 case, through the same kernels' one-head instantiation), and the
+aggregation and its score counterpart (gcn_amd/csrc/multihead.hip) are
 
     p = gcn_amd.edge_softmax(adj, scores)                    # scores [nnz, H] -> p [nnz, H]
     p = gcn_amd.gat_edge_softmax(adj, a_dst, a_src, 0.2)     # a_dst [m, H], a_src [n, H] -> p [nnz, H]
@@ -17,60 +18,88 @@ The kernels take no plan and only enqueue, so all of this runs inside a captured
 whose scores are all -inf gets zeros, not NaN (a fully masked row stays usable).  There is no CPU path: CPU tensors raise.
 """
 import ctypes
+import functools
 
 import torch
 
 from . import _lib
 from .spmm import CsrAdjacency, _ptr, _stream_ptr
 
-_CHUNK = 8192                # entries per workspace partial: GCN_EDGE_WS_BYTES in include/gcn_spmm.h
+
+@functools.lru_cache(maxsize=None)
+def _ws_need(nnz, heads, k):
+    need = ctypes.c_size_t(0)
+    _lib.check(_lib.load().gcn_heads_ws_bytes(0, nnz, heads, k, ctypes.byref(need)), "gcn_heads_ws_bytes")
+    return need.value
 
 
-def _ws_bytes(nnz):
-    return 16 + 16 * ((int(nnz) + _CHUNK - 1) // _CHUNK)
-
-
-def _workspace(owner, nnz, device):
-    """the scratch the kernels want (a flag and the partials of rows longer than 8192 entries), kept on the adjacency:
-    allocated at the first call — so before a capture, with the plans — and shared by its calls, which one stream orders"""
+def _workspace(owner, nnz, device, heads=1, k=1):
+    """the scratch the kernels want (gcn_heads_ws_bytes: a flag and the chunk partials of long rows), kept on the adjacency:
+    allocated at the first call — so before a capture, with the plans and the transposed pattern — grown when a call needs
+    more, and shared by its calls, which one stream orders"""
+    need = _ws_need(int(nnz), int(heads), int(k))
     ws = getattr(owner, "_edge_ws", None)
-    if ws is None or ws.numel() < _ws_bytes(nnz) or ws.device != device:
-        ws = torch.empty(_ws_bytes(nnz), dtype=torch.uint8, device=device)
+    if ws is None or ws.numel() < need or ws.device != device:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
         owner._edge_ws = ws
     return ws
 
 
-def _entry_tensor(adj, t, what):
-    """the checks of spmm(values=...): shape first (ValueError), then device and dtype (GcnAmdError)"""
-    if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.numel() != adj.nnz:
-        raise ValueError(f"{what} must be a 1-D tensor of nnz = {adj.nnz} entries in CSR order")
-    if not t.is_cuda:
-        raise _lib.GcnAmdError(f"{what} must be a CUDA/HIP tensor (no CPU path in gcn_amd)")
-    if t.dtype != torch.float32:
-        raise _lib.GcnAmdError(f"{what} must be fp32")
-
-
-def _node_tensors(pairs):
-    """shapes of all of them first (ValueError), then device and dtype (GcnAmdError)"""
-    for t, count, what in pairs:
-        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.numel() != count:
-            raise ValueError(f"{what} must be a 1-D tensor of {count} entries")
-    for t, _count, what in pairs:
+def _fp32_tensors(items):
+    """items: (tensor, shape, what, form).  The checks of spmm(values=...): the shapes of all of them first (ValueError
+    "`what` must be `form`"; None in a shape: any size, and the width of a 2-D tensor is at least 1), then device and dtype
+    (GcnAmdError)"""
+    for t, shape, what, form in items:
+        if (not isinstance(t, torch.Tensor) or t.dim() != len(shape) or (t.dim() == 2 and t.shape[1] < 1)
+                or any(want is not None and have != want for have, want in zip(t.shape, shape))):
+            raise ValueError(f"{what} must be {form}")
+    for t, _shape, what, _form in items:
         if not t.is_cuda:
             raise _lib.GcnAmdError(f"{what} must be a CUDA/HIP tensor (no CPU path in gcn_amd)")
         if t.dtype != torch.float32:
             raise _lib.GcnAmdError(f"{what} must be fp32")
 
 
-def _segment_sum_raw(owner, rowptr, m, x, perm, out):
-    nnz = int(x.numel())
-    if m == 0 or nnz == 0:
+def _heads_of(t):
+    """H of a per-entry or per-node array: [count, H], or [count] for one head"""
+    return int(t.shape[1]) if t.dim() == 2 else 1
+
+
+def _heads_tpattern(adj):
+    """(rowptr int32 [n + 1], source row of each entry int32 [nnz], its index in adj's order int32 [nnz]) of the transposed
+    pattern, built once per adjacency (on the device) and kept on it"""
+    tp = getattr(adj, "_heads_tp", None)
+    if tp is None:
+        trp, trow, perm = adj._transposed_pattern()
+        tp = adj._heads_tp = (trp.contiguous(), trow.contiguous(), perm.to(torch.int32).contiguous())
+    return tp
+
+
+def _column_sums_pattern(adj):
+    """(rowptr int32 [n + 1], permutation int32 [nnz]) of the transposed pattern for sums by column: a mutable adjacency's
+    own (its mutable transpose is built from the same _transposed_pattern, so it is the same pattern and is never built
+    twice), _heads_tpattern otherwise"""
+    if not adj.mutable_values:
+        trp, _trow, tperm = _heads_tpattern(adj)
+        return trp, tperm
+    t = adj._mutable_transpose()                         # (its pattern and permutation; its values are not touched)
+    perm = getattr(adj, "_tperm32", None)
+    if perm is None:
+        perm = adj._tperm32 = adj._tperm.to(torch.int32)
+    return t.rowptr, perm
+
+
+def _segment_sum_raw(owner, rowptr, rows, x, perm, out):
+    """out [rows] or [rows, H] = the row sums over rowptr of x [nnz] or [nnz, H] (read through perm)"""
+    nnz, heads = int(x.shape[0]), _heads_of(x)
+    if rows == 0 or nnz == 0:
         return out.zero_()
-    ws = _workspace(owner, nnz, x.device)
+    ws = _workspace(owner, nnz, x.device, heads, heads)
     with torch.cuda.device(x.device):
-        st = _lib.load().gcn_segment_sum_csr_f32(_ptr(rowptr), m, nnz, _ptr(x), _ptr(perm) if perm is not None else None,
-                                                 _ptr(out), _ptr(ws), ws.numel(), _stream_ptr(x.device))
-    _lib.check(st, "gcn_segment_sum_csr_f32")
+        st = _lib.load().gcn_segment_sum_heads_csr_f32(_ptr(rowptr), rows, nnz, heads, _ptr(x),
+                                                       _ptr(perm) if perm is not None else None, _ptr(out), _ptr(ws),
+                                                       ws.numel(), _stream_ptr(x.device))
+    _lib.check(st, "gcn_segment_sum_heads_csr_f32")
     return out
 
 
@@ -92,7 +121,7 @@ def _loose_holder(device):
 
 def segment_sum(rowptr, x, perm=None):
     """out[r] = sum of x[e] over rowptr[r] <= e < rowptr[r+1] (x[perm[e]] with an int32 permutation `perm`): plain CSR row
-    sums of a per-entry fp32 device array, in a fixed order (no atomics) — gcn_segment_sum_csr_f32.  No autograd.
+    sums of a per-entry fp32 device array, in a fixed order (no atomics) — gcn_segment_sum_heads_csr_f32.  No autograd.
     x may be 2-D [nnz, H] (an entry's heads contiguous): the result is [m, H], from one pass over the entries.
     Its scratch is kept per (device, stream), so calls on different streams do not share one."""
     if not (isinstance(rowptr, torch.Tensor) and rowptr.dim() == 1 and rowptr.numel() >= 1):
@@ -106,28 +135,25 @@ def segment_sum(rowptr, x, perm=None):
     if x.dtype != torch.float32 or rowptr.dtype != torch.int32 or (perm is not None and perm.dtype != torch.int32):
         raise _lib.GcnAmdError("segment_sum: x must be fp32, rowptr and perm int32")
     m = int(rowptr.numel()) - 1
-    if x.dim() == 2:                                     # [nnz, H] -> [m, H]: one pass for all heads
-        out = torch.empty(m, x.shape[1], dtype=torch.float32, device=x.device)
-        return _segment_sum_heads_raw(_loose_holder(x.device), rowptr.contiguous(), m, x.detach().contiguous(),
-                                      perm.contiguous() if perm is not None else None, out)
-    out = torch.empty(m, dtype=torch.float32, device=x.device)
+    out = torch.empty((m,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
     return _segment_sum_raw(_loose_holder(x.device), rowptr.contiguous(), m, x.detach().contiguous(),
                             perm.contiguous() if perm is not None else None, out)
 
 
 class _EdgeSoftmaxFunction(torch.autograd.Function):
-    """p = softmax of `scores` over each row's stored entries; saves p: ds = p (g - sum_row p g)"""
+    """p = per-head softmax of `scores` ([nnz] or [nnz, H]) over each row's stored entries; saves p: ds = p (g - sum_row p g)"""
 
     @staticmethod
     def forward(ctx, adj, scores):
         s = scores.detach().contiguous()
         p = torch.empty_like(s)
+        heads = _heads_of(s)
         if adj.m and adj.nnz:
-            ws = _workspace(adj, adj.nnz, s.device)
+            ws = _workspace(adj, adj.nnz, s.device, heads, heads)
             with torch.cuda.device(s.device):
-                st = _lib.load().gcn_edge_softmax_csr_f32(_ptr(adj.rowptr), adj.m, adj.nnz, _ptr(s), _ptr(p), _ptr(ws),
-                                                          ws.numel(), _stream_ptr(s.device))
-            _lib.check(st, "gcn_edge_softmax_csr_f32")
+                st = _lib.load().gcn_edge_softmax_heads_csr_f32(_ptr(adj.rowptr), adj.m, adj.nnz, heads, _ptr(s), _ptr(p),
+                                                                _ptr(ws), ws.numel(), _stream_ptr(s.device))
+            _lib.check(st, "gcn_edge_softmax_heads_csr_f32")
         ctx.adj = adj
         ctx.save_for_backward(p)
         return p
@@ -138,12 +164,14 @@ class _EdgeSoftmaxFunction(torch.autograd.Function):
         adj = ctx.adj
         g = g.contiguous()
         ds = torch.empty_like(p)
+        heads = _heads_of(p)
         if adj.m and adj.nnz:
-            ws = _workspace(adj, adj.nnz, p.device)
+            ws = _workspace(adj, adj.nnz, p.device, heads, heads)
             with torch.cuda.device(p.device):
-                st = _lib.load().gcn_edge_softmax_backward_csr_f32(_ptr(adj.rowptr), adj.m, adj.nnz, _ptr(p), _ptr(g), _ptr(ds),
-                                                                   _ptr(ws), ws.numel(), _stream_ptr(p.device))
-            _lib.check(st, "gcn_edge_softmax_backward_csr_f32")
+                st = _lib.load().gcn_edge_softmax_heads_backward_csr_f32(_ptr(adj.rowptr), adj.m, adj.nnz, heads, _ptr(p),
+                                                                         _ptr(g), _ptr(ds), _ptr(ws), ws.numel(),
+                                                                         _stream_ptr(p.device))
+            _lib.check(st, "gcn_edge_softmax_heads_backward_csr_f32")
         return None, ds
 
 
@@ -156,28 +184,30 @@ def edge_softmax(adj, scores):
     if not isinstance(adj, CsrAdjacency):
         raise TypeError("edge_softmax: adj must be a CsrAdjacency")
     if isinstance(scores, torch.Tensor) and scores.dim() == 2:           # [nnz, H]: all heads in one pass
-        _entry_tensor_heads(adj, scores, "edge_softmax: scores")
-        return _EdgeSoftmaxHeadsFunction.apply(adj, scores)
-    _entry_tensor(adj, scores, "edge_softmax: scores")
+        _fp32_tensors([(scores, (adj.nnz, None), "edge_softmax: scores", f"a 2-D tensor [nnz = {adj.nnz}, H] in CSR order")])
+    else:
+        _fp32_tensors([(scores, (adj.nnz,), "edge_softmax: scores", f"a 1-D tensor of nnz = {adj.nnz} entries in CSR order")])
     return _EdgeSoftmaxFunction.apply(adj, scores)
 
 
 class _GatEdgeSoftmaxFunction(torch.autograd.Function):
-    """p = edge softmax of leaky_relu(a_dst[row] + a_src[col]); backward recomputes the scores from a_dst, a_src:
-    grad_a_dst = row sums of ds (same kernel), grad_a_src = column sums of ds = row sums over the transpose's rowptr of
-    ds read through the transpose permutation (segment sum: one writer per output, no atomics)."""
+    """p = per-head edge softmax of leaky_relu(a_dst[row] + a_src[col]) (a_dst [m] or [m, H]); the backward recomputes the
+    scores from a_dst, a_src: grad_a_dst = row sums of ds (same kernel), grad_a_src = column sums of ds = row sums over the
+    transposed pattern's rowptr of ds read through its permutation (segment sum: one writer per output, no atomics; one
+    gather brings an entry's H values)."""
 
     @staticmethod
     def forward(ctx, adj, a_dst, a_src, slope):
         ad, asrc = a_dst.detach().contiguous(), a_src.detach().contiguous()
-        p = torch.empty(adj.nnz, dtype=torch.float32, device=ad.device)
+        heads = _heads_of(ad)
+        p = torch.empty((adj.nnz,) + tuple(ad.shape[1:]), dtype=torch.float32, device=ad.device)
         if adj.m and adj.nnz:
-            ws = _workspace(adj, adj.nnz, ad.device)
+            ws = _workspace(adj, adj.nnz, ad.device, heads, heads)
             with torch.cuda.device(ad.device):
-                st = _lib.load().gcn_gat_edge_softmax_csr_f32(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, _ptr(ad),
-                                                              _ptr(asrc), slope, _ptr(p), _ptr(ws), ws.numel(),
-                                                              _stream_ptr(ad.device))
-            _lib.check(st, "gcn_gat_edge_softmax_csr_f32")
+                st = _lib.load().gcn_gat_edge_softmax_heads_csr_f32(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, heads,
+                                                                    _ptr(ad), _ptr(asrc), slope, _ptr(p), _ptr(ws), ws.numel(),
+                                                                    _stream_ptr(ad.device))
+            _lib.check(st, "gcn_gat_edge_softmax_heads_csr_f32")
         ctx.adj, ctx.slope = adj, slope
         ctx.save_for_backward(ad, asrc, p)
         return p
@@ -187,24 +217,22 @@ class _GatEdgeSoftmaxFunction(torch.autograd.Function):
         ad, asrc, p = ctx.saved_tensors
         adj = ctx.adj
         dev = p.device
+        heads = _heads_of(p)
         g = g.contiguous()
         ds = torch.empty_like(p)
-        g_dst = torch.empty(adj.m, dtype=torch.float32, device=dev)
-        g_src = torch.empty(adj.n, dtype=torch.float32, device=dev)
+        g_dst = torch.empty_like(ad)
+        g_src = torch.empty_like(asrc)
         if not (adj.m and adj.nnz):
             return None, g_dst.zero_(), g_src.zero_(), None
-        ws = _workspace(adj, adj.nnz, dev)
+        ws = _workspace(adj, adj.nnz, dev, heads, heads)
         with torch.cuda.device(dev):
-            st = _lib.load().gcn_gat_edge_softmax_backward_csr_f32(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, _ptr(ad),
-                                                                   _ptr(asrc), ctx.slope, _ptr(p), _ptr(g), _ptr(ds),
-                                                                   _ptr(g_dst), _ptr(ws), ws.numel(), _stream_ptr(dev))
-        _lib.check(st, "gcn_gat_edge_softmax_backward_csr_f32")
+            st = _lib.load().gcn_gat_edge_softmax_heads_backward_csr_f32(
+                _ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, heads, _ptr(ad), _ptr(asrc), ctx.slope, _ptr(p), _ptr(g),
+                _ptr(ds), _ptr(g_dst), _ptr(ws), ws.numel(), _stream_ptr(dev))
+        _lib.check(st, "gcn_gat_edge_softmax_heads_backward_csr_f32")
         if ctx.needs_input_grad[2]:
-            t = adj._mutable_transpose()                 # (its pattern and permutation; its values are not touched)
-            perm = getattr(adj, "_tperm32", None)
-            if perm is None:
-                perm = adj._tperm32 = adj._tperm.to(torch.int32)
-            _segment_sum_raw(adj, t.rowptr, adj.n, ds, perm, g_src)
+            trp, tperm = _column_sums_pattern(adj)
+            _segment_sum_raw(adj, trp, adj.n, ds, tperm, g_src)
         else:
             g_src = None
         return None, g_dst, g_src, None
@@ -220,79 +248,25 @@ def gat_edge_softmax(adj, a_dst, a_src, negative_slope=0.2):
         raise TypeError("gat_edge_softmax: adj must be a CsrAdjacency")
     if isinstance(a_dst, torch.Tensor) and isinstance(a_src, torch.Tensor) and (a_dst.dim() == 2 or a_src.dim() == 2):
         heads = int(a_dst.shape[-1])                     # a_dst [m, H], a_src [n, H]: all heads in one pass, any adjacency
-        _node_tensors_heads([(a_dst, adj.m, heads, "gat_edge_softmax: a_dst"), (a_src, adj.n, heads, "gat_edge_softmax: a_src")])
-        return _GatEdgeSoftmaxHeadsFunction.apply(adj, a_dst, a_src, float(negative_slope))
-    if not adj.mutable_values:
-        raise _lib.GcnAmdError("gat_edge_softmax needs an adjacency made with mutable_values=True (grad_a_src is summed "
-                               "through the transpose permutation only a mutable adjacency keeps)")
-    _node_tensors([(a_dst, adj.m, "gat_edge_softmax: a_dst"), (a_src, adj.n, "gat_edge_softmax: a_src")])
+        _fp32_tensors([(a_dst, (adj.m, heads), "gat_edge_softmax: a_dst", f"a 2-D tensor [{adj.m}, {heads}]"),
+                       (a_src, (adj.n, heads), "gat_edge_softmax: a_src", f"a 2-D tensor [{adj.n}, {heads}]")])
+    else:
+        if not adj.mutable_values:
+            raise _lib.GcnAmdError("gat_edge_softmax needs an adjacency made with mutable_values=True (grad_a_src is summed "
+                                   "through the transpose permutation only a mutable adjacency keeps)")
+        _fp32_tensors([(a_dst, (adj.m,), "gat_edge_softmax: a_dst", f"a 1-D tensor of {adj.m} entries"),
+                       (a_src, (adj.n,), "gat_edge_softmax: a_src", f"a 1-D tensor of {adj.n} entries")])
     return _GatEdgeSoftmaxFunction.apply(adj, a_dst, a_src, float(negative_slope))
 
 
-# ---- all heads in one pass (gcn_amd/csrc/multihead.hip) ---------------------------------------------------------------------------
-def _heads_workspace(owner, m, nnz, heads, k, device):
-    """one scratch per adjacency for the head-batched kernels (gcn_heads_ws_bytes: a flag and the chunk partials of long
-    rows), allocated at the first call and grown when a call needs more — so before a capture, with the transposed pattern"""
-    need = ctypes.c_size_t(0)
-    _lib.check(_lib.load().gcn_heads_ws_bytes(int(m), int(nnz), int(heads), int(k), ctypes.byref(need)), "gcn_heads_ws_bytes")
-    ws = getattr(owner, "_heads_ws", None)
-    if ws is None or ws.numel() < need.value or ws.device != device:
-        ws = torch.empty(need.value, dtype=torch.uint8, device=device)
-        owner._heads_ws = ws
-    return ws
-
-
-def _heads_tpattern(adj):
-    """(rowptr int32 [n + 1], source row of each entry int32 [nnz], its index in adj's order int32 [nnz]) of the transposed
-    pattern, built once per adjacency (on the device) and kept on it"""
-    tp = getattr(adj, "_heads_tp", None)
-    if tp is None:
-        trp, trow, perm = adj._transposed_pattern()
-        tp = adj._heads_tp = (trp.contiguous(), trow.contiguous(), perm.to(torch.int32).contiguous())
-    return tp
-
-
-def _entry_tensor_heads(adj, t, what):
-    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != adj.nnz or t.shape[1] < 1:
-        raise ValueError(f"{what} must be a 2-D tensor [nnz = {adj.nnz}, H] in CSR order")
-    if not t.is_cuda:
-        raise _lib.GcnAmdError(f"{what} must be a CUDA/HIP tensor (no CPU path in gcn_amd)")
-    if t.dtype != torch.float32:
-        raise _lib.GcnAmdError(f"{what} must be fp32")
-
-
-def _node_tensors_heads(items):
-    """shapes of all of them first (ValueError), then device and dtype (GcnAmdError)"""
-    for t, rows, width, what in items:
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != rows or t.shape[1] != width or width < 1:
-            raise ValueError(f"{what} must be a 2-D tensor [{rows}, {width}]")
-    for t, _rows, _width, what in items:
-        if not t.is_cuda:
-            raise _lib.GcnAmdError(f"{what} must be a CUDA/HIP tensor (no CPU path in gcn_amd)")
-        if t.dtype != torch.float32:
-            raise _lib.GcnAmdError(f"{what} must be fp32")
-
-
-def _segment_sum_heads_raw(owner, rowptr, rows, x, perm, out):
-    nnz, heads = int(x.shape[0]), int(x.shape[1])
-    if rows == 0 or nnz == 0:
-        return out.zero_()
-    ws = _heads_workspace(owner, rows, nnz, heads, heads, x.device)
-    with torch.cuda.device(x.device):
-        st = _lib.load().gcn_segment_sum_heads_csr_f32(_ptr(rowptr), rows, nnz, heads, _ptr(x),
-                                                       _ptr(perm) if perm is not None else None, _ptr(out), _ptr(ws),
-                                                       ws.numel(), _stream_ptr(x.device))
-    _lib.check(st, "gcn_segment_sum_heads_csr_f32")
-    return out
-
-
+# ---- the gathers of all heads in one pass (gcn_amd/csrc/multihead.hip) ------------------------------------------------------------
 def _spmm_heads_raw(adj, rowptr, idx, perm, rows, vals, x, heads):
     """out [rows, k] of gcn_spmm_heads_csr_f32 over (rowptr, idx, perm); vals [nnz, H], x [*, k]"""
     k = int(x.shape[1])
     out = torch.empty(rows, k, dtype=torch.float32, device=x.device)
     if rows == 0 or adj.nnz == 0:
         return out.zero_()
-    ws = _heads_workspace(adj, max(adj.m, adj.n), adj.nnz, heads, k, x.device)
+    ws = _workspace(adj, adj.nnz, x.device, heads, k)
     with torch.cuda.device(x.device):
         st = _lib.load().gcn_spmm_heads_csr_f32(_ptr(rowptr), _ptr(idx), _ptr(perm) if perm is not None else None, rows,
                                                 adj.nnz, heads, k, _ptr(vals), _ptr(x), _ptr(out), _ptr(ws), ws.numel(),
@@ -306,94 +280,12 @@ def _sddmm_heads_raw(adj, a, b, heads):
     out = torch.empty(adj.nnz, heads, dtype=torch.float32, device=a.device)
     if adj.m == 0 or adj.nnz == 0:
         return out
-    ws = _heads_workspace(adj, max(adj.m, adj.n), adj.nnz, heads, k, a.device)
+    ws = _workspace(adj, adj.nnz, a.device, heads, k)
     with torch.cuda.device(a.device):
         st = _lib.load().gcn_sddmm_heads_csr_f32(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, heads, k, _ptr(a), _ptr(b),
                                                  _ptr(out), _ptr(ws), ws.numel(), _stream_ptr(a.device))
     _lib.check(st, "gcn_sddmm_heads_csr_f32")
     return out
-
-
-class _EdgeSoftmaxHeadsFunction(torch.autograd.Function):
-    """p [nnz, H] = per-head softmax of scores [nnz, H] over each row's entries; saves p"""
-
-    @staticmethod
-    def forward(ctx, adj, scores):
-        s = scores.detach().contiguous()
-        p = torch.empty_like(s)
-        heads = int(s.shape[1])
-        if adj.m and adj.nnz:
-            ws = _heads_workspace(adj, max(adj.m, adj.n), adj.nnz, heads, heads, s.device)
-            with torch.cuda.device(s.device):
-                st = _lib.load().gcn_edge_softmax_heads_csr_f32(_ptr(adj.rowptr), adj.m, adj.nnz, heads, _ptr(s), _ptr(p),
-                                                                _ptr(ws), ws.numel(), _stream_ptr(s.device))
-            _lib.check(st, "gcn_edge_softmax_heads_csr_f32")
-        ctx.adj = adj
-        ctx.save_for_backward(p)
-        return p
-
-    @staticmethod
-    def backward(ctx, g):
-        (p,) = ctx.saved_tensors
-        adj = ctx.adj
-        g = g.contiguous()
-        ds = torch.empty_like(p)
-        heads = int(p.shape[1])
-        if adj.m and adj.nnz:
-            ws = _heads_workspace(adj, max(adj.m, adj.n), adj.nnz, heads, heads, p.device)
-            with torch.cuda.device(p.device):
-                st = _lib.load().gcn_edge_softmax_heads_backward_csr_f32(_ptr(adj.rowptr), adj.m, adj.nnz, heads, _ptr(p),
-                                                                         _ptr(g), _ptr(ds), _ptr(ws), ws.numel(),
-                                                                         _stream_ptr(p.device))
-            _lib.check(st, "gcn_edge_softmax_heads_backward_csr_f32")
-        return None, ds
-
-
-class _GatEdgeSoftmaxHeadsFunction(torch.autograd.Function):
-    """p [nnz, H] = per-head edge softmax of leaky_relu(a_dst[row, h] + a_src[col, h]); the backward recomputes the scores:
-    grad_a_dst [m, H] = row sums of ds (same kernel), grad_a_src [n, H] = the segment sum of ds over the transposed pattern
-    through its permutation (one writer per output, no atomics; one gather brings an entry's H values)."""
-
-    @staticmethod
-    def forward(ctx, adj, a_dst, a_src, slope):
-        ad, asrc = a_dst.detach().contiguous(), a_src.detach().contiguous()
-        heads = int(ad.shape[1])
-        p = torch.empty(adj.nnz, heads, dtype=torch.float32, device=ad.device)
-        if adj.m and adj.nnz:
-            ws = _heads_workspace(adj, max(adj.m, adj.n), adj.nnz, heads, heads, ad.device)
-            with torch.cuda.device(ad.device):
-                st = _lib.load().gcn_gat_edge_softmax_heads_csr_f32(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, heads,
-                                                                    _ptr(ad), _ptr(asrc), slope, _ptr(p), _ptr(ws), ws.numel(),
-                                                                    _stream_ptr(ad.device))
-            _lib.check(st, "gcn_gat_edge_softmax_heads_csr_f32")
-        ctx.adj, ctx.slope = adj, slope
-        ctx.save_for_backward(ad, asrc, p)
-        return p
-
-    @staticmethod
-    def backward(ctx, g):
-        ad, asrc, p = ctx.saved_tensors
-        adj = ctx.adj
-        dev = p.device
-        heads = int(p.shape[1])
-        g = g.contiguous()
-        ds = torch.empty_like(p)
-        g_dst = torch.empty(adj.m, heads, dtype=torch.float32, device=dev)
-        g_src = torch.empty(adj.n, heads, dtype=torch.float32, device=dev)
-        if not (adj.m and adj.nnz):
-            return None, g_dst.zero_(), g_src.zero_(), None
-        ws = _heads_workspace(adj, max(adj.m, adj.n), adj.nnz, heads, heads, dev)
-        with torch.cuda.device(dev):
-            st = _lib.load().gcn_gat_edge_softmax_heads_backward_csr_f32(
-                _ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, heads, _ptr(ad), _ptr(asrc), ctx.slope, _ptr(p), _ptr(g),
-                _ptr(ds), _ptr(g_dst), _ptr(ws), ws.numel(), _stream_ptr(dev))
-        _lib.check(st, "gcn_gat_edge_softmax_heads_backward_csr_f32")
-        if ctx.needs_input_grad[2]:
-            trp, _trow, tperm = _heads_tpattern(adj)
-            _segment_sum_heads_raw(adj, trp, adj.n, ds, tperm, g_src)
-        else:
-            g_src = None
-        return None, g_dst, g_src, None
 
 
 class _SpmmHeadsFunction(torch.autograd.Function):
@@ -460,8 +352,8 @@ def spmm_heads(adj, x, values):
     heads = int(values.shape[1])
     if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != adj.n or x.shape[1] < heads or x.shape[1] % heads:
         raise ValueError(f"spmm_heads: x must be a 2-D tensor [n = {adj.n}, H*F] with H = {heads} heads")
-    _node_tensors_heads([(x, adj.n, int(x.shape[1]), "spmm_heads: x")])
-    _entry_tensor_heads(adj, values, "spmm_heads: values")
+    _fp32_tensors([(x, (adj.n, None), "spmm_heads: x", f"a 2-D tensor [{adj.n}, {int(x.shape[1])}]"),
+                   (values, (adj.nnz, None), "spmm_heads: values", f"a 2-D tensor [nnz = {adj.nnz}, H] in CSR order")])
     return _SpmmHeadsFunction.apply(adj, x, values)
 
 
@@ -477,5 +369,6 @@ def sddmm_heads(adj, a, b, heads):
     if not isinstance(a, torch.Tensor) or a.dim() != 2 or a.shape[1] < heads or a.shape[1] % heads:
         raise ValueError(f"sddmm_heads: a must be a 2-D tensor [m = {adj.m}, H*F] with H = {heads} heads")
     k = int(a.shape[1])
-    _node_tensors_heads([(a, adj.m, k, "sddmm_heads: a"), (b, adj.n, k, "sddmm_heads: b")])
+    _fp32_tensors([(a, (adj.m, k), "sddmm_heads: a", f"a 2-D tensor [{adj.m}, {k}]"),
+                   (b, (adj.n, k), "sddmm_heads: b", f"a 2-D tensor [{adj.n}, {k}]")])
     return _SddmmHeadsFunction.apply(adj, a, b, heads)

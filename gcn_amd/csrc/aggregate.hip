@@ -333,24 +333,17 @@ __global__ void __launch_bounds__(256) agg_long_partial_kernel(Op op, const int*
   const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = gridDim.x * 4;
   const int j = (blockIdx.y * 16 + (lane & 15)) * Op::VEC;
   const bool jok = j < op.k;
-  for (int c = wave; c < nchunks; c += nwaves) {
-    const int e0 = c * kChunk;
-    const int e1 = (long long)e0 + kChunk < nnz ? e0 + kChunk : nnz;
-    const int rh = find_row(rowptr, rows, e0, lane), rt = find_row(rowptr, rows, e1 - 1, lane);
-    for (int slot = 0; slot < 2; ++slot) {
-      Segment sg;
-      if (!long_segment<kLongRow>(rowptr, slot, rh, rt, e0, e1, sg)) continue;   // (wave-uniform)
-      State<Op::VEC> s;
-      Op::init(s);
-      walk(op, sg.sb, sg.se - sg.sb, lane, j, jok, s);
-      merge_slots<Op>(s);
-      if (lane < 16 && jok) {
-        Partial* p = part + (2 * (size_t)c + slot) * op.k + j;
+  for_long_segments<kChunk, kLongRow>(rowptr, rows, nnz, nchunks, wave, nwaves, lane, [&](int c, int slot, const Segment& sg) {
+    State<Op::VEC> s;
+    Op::init(s);
+    walk(op, sg.sb, sg.se - sg.sb, lane, j, jok, s);
+    merge_slots<Op>(s);
+    if (lane < 16 && jok) {
+      Partial* p = part + (2 * (size_t)c + slot) * op.k + j;
 #pragma unroll
-        for (int i = 0; i < Op::VEC; ++i) p[i] = Partial{s.v[i], s.e[i]};
-      }
+      for (int i = 0; i < Op::VEC; ++i) p[i] = Partial{s.v[i], s.e[i]};
     }
-  }
+  });
 }
 
 template <class Op>
@@ -361,25 +354,18 @@ __global__ void __launch_bounds__(256) agg_long_finish_kernel(Op op, const int* 
   const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = gridDim.x * 4;
   const int j0 = blockIdx.y * tile_width<Op>();
   const int j1 = j0 + tile_width<Op>() < op.k ? j0 + tile_width<Op>() : op.k;
-  for (int c = wave; c < nchunks; c += nwaves) {
-    const int e0 = c * kChunk;
-    const int e1 = (long long)e0 + kChunk < nnz ? e0 + kChunk : nnz;
-    const int rh = find_row(rowptr, rows, e0, lane), rt = find_row(rowptr, rows, e1 - 1, lane);
-    for (int slot = 0; slot < 2; ++slot) {
-      Segment sg;
-      if (!long_segment<kLongRow>(rowptr, slot, rh, rt, e0, e1, sg)) continue;
-      // the row's partials: chunks c_first..c_last, the first in slot 1 unless the row starts on the chunk's first entry.
-      // One writer per row: the wave whose chunk holds the row's first entry merges them, in chunk order, a column per lane.
-      const int c_first = sg.rb / kChunk, c_last = (sg.re - 1) / kChunk;
-      if (c != c_first) continue;
-      const int first_slot = sg.rb > c_first * kChunk ? 1 : 0;
-      for (int j = j0 + lane; j < j1; j += 64) {
-        Partial acc = part[(2 * (size_t)c_first + first_slot) * op.k + j];
-        for (int cc = c_first + 1; cc <= c_last; ++cc) Op::merge_next(acc, part[2 * (size_t)cc * op.k + j]);
-        op.store_one(sg.r, j, acc);
-      }
+  for_long_segments<kChunk, kLongRow>(rowptr, rows, nnz, nchunks, wave, nwaves, lane, [&](int c, int slot, const Segment& sg) {
+    // the row's partials: chunks c_first..c_last, the first in slot 1 unless the row starts on the chunk's first entry.
+    // One writer per row: the wave whose chunk holds the row's first entry merges them, in chunk order, a column per lane.
+    const int c_first = sg.rb / kChunk, c_last = (sg.re - 1) / kChunk;
+    if (c != c_first) return;
+    const int first_slot = sg.rb > c_first * kChunk ? 1 : 0;
+    for (int j = j0 + lane; j < j1; j += 64) {
+      Partial acc = part[(2 * (size_t)c_first + first_slot) * op.k + j];
+      for (int cc = c_first + 1; cc <= c_last; ++cc) Op::merge_next(acc, part[2 * (size_t)cc * op.k + j]);
+      op.store_one(sg.r, j, acc);
     }
-  }
+  });
 }
 
 template <class Op>

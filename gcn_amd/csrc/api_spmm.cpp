@@ -219,7 +219,7 @@ int gcn_segment_sum_csr_f32(const int32_t* rowptr, int32_t m, int32_t nnz, const
   return launch_segment_sum(rowptr, m, nnz, x, perm, out, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
 }
 
-// Head-batched attention primitives (multihead.hip).  Sizes first — heads, k and nnz * heads < 2^31 before any pointer is
+// Head-batched attention primitives (edge_softmax.hip with H heads, multihead.hip).  Sizes first — heads, k and nnz * heads < 2^31 before any pointer is
 // looked at — then the empty problem, then the row pointer and the workspace; 1 = return *status.  k = 0: the call takes no k.
 static int heads_args(const int32_t* rowptr, int32_t rows, int32_t nnz, int32_t heads, int32_t k, const void* ws, size_t ws_bytes,
                       size_t ws_need, int* status) {
@@ -238,7 +238,7 @@ int gcn_heads_ws_bytes(int32_t m, int32_t nnz, int32_t heads, int32_t k, size_t*
   if (!bytes || k < 1) return GCN_ERR_INVALID_ARG;
   heads_args(nullptr, 0, nnz, heads, k, nullptr, 0, 0, &rc);                  // (the size rules alone)
   if (rc != GCN_OK || m < 0) return GCN_ERR_INVALID_ARG;
-  const size_t e = heads_edge_workspace_bytes(nnz, heads), s = heads_spmm_workspace_bytes(nnz, k);
+  const size_t e = edge_workspace_bytes(nnz, heads), s = heads_spmm_workspace_bytes(nnz, k);
   *bytes = e > s ? e : s;
   return GCN_OK;
 }
@@ -246,7 +246,7 @@ int gcn_heads_ws_bytes(int32_t m, int32_t nnz, int32_t heads, int32_t k, size_t*
 int gcn_edge_softmax_heads_csr_f32(const int32_t* rowptr, int32_t m, int32_t nnz, int32_t heads, const float* scores, float* p,
                                    void* ws, size_t ws_bytes, void* stream) {
   int rc;
-  if (heads_args(rowptr, m, nnz, heads, 0, ws, ws_bytes, heads_edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
+  if (heads_args(rowptr, m, nnz, heads, 0, ws, ws_bytes, edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
   if (!scores || !p) return GCN_ERR_INVALID_ARG;
   return launch_edge_softmax_heads(rowptr, m, nnz, heads, scores, p, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
 }
@@ -254,7 +254,7 @@ int gcn_edge_softmax_heads_csr_f32(const int32_t* rowptr, int32_t m, int32_t nnz
 int gcn_edge_softmax_heads_backward_csr_f32(const int32_t* rowptr, int32_t m, int32_t nnz, int32_t heads, const float* p,
                                             const float* g, float* ds, void* ws, size_t ws_bytes, void* stream) {
   int rc;
-  if (heads_args(rowptr, m, nnz, heads, 0, ws, ws_bytes, heads_edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
+  if (heads_args(rowptr, m, nnz, heads, 0, ws, ws_bytes, edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
   if (!p || !g || !ds) return GCN_ERR_INVALID_ARG;
   return launch_edge_softmax_heads_backward(rowptr, m, nnz, heads, p, g, ds, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK
                                                                                                                      : GCN_ERR_HIP;
@@ -264,7 +264,7 @@ int gcn_gat_edge_softmax_heads_csr_f32(const int32_t* rowptr, const int32_t* col
                                        const float* a_dst, const float* a_src, float negative_slope, float* p, void* ws,
                                        size_t ws_bytes, void* stream) {
   int rc;
-  if (heads_args(rowptr, m, nnz, heads, 0, ws, ws_bytes, heads_edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
+  if (heads_args(rowptr, m, nnz, heads, 0, ws, ws_bytes, edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
   if (!col || !a_dst || !a_src || !p) return GCN_ERR_INVALID_ARG;
   return launch_gat_edge_softmax_heads(rowptr, col, m, nnz, heads, a_dst, a_src, negative_slope, p, ws, (hipStream_t)stream) ==
                  hipSuccess ? GCN_OK : GCN_ERR_HIP;
@@ -275,7 +275,7 @@ int gcn_gat_edge_softmax_heads_backward_csr_f32(const int32_t* rowptr, const int
                                                 const float* g, float* ds, float* grad_a_dst, void* ws, size_t ws_bytes,
                                                 void* stream) {
   int rc;
-  if (heads_args(rowptr, m, nnz, heads, 0, ws, ws_bytes, heads_edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
+  if (heads_args(rowptr, m, nnz, heads, 0, ws, ws_bytes, edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
   if (!col || !a_dst || !a_src || !p || !g || !ds || !grad_a_dst) return GCN_ERR_INVALID_ARG;
   return launch_gat_edge_softmax_heads_backward(rowptr, col, m, nnz, heads, a_dst, a_src, negative_slope, p, g, ds, grad_a_dst, ws,
                                                 (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
@@ -284,7 +284,7 @@ int gcn_gat_edge_softmax_heads_backward_csr_f32(const int32_t* rowptr, const int
 int gcn_segment_sum_heads_csr_f32(const int32_t* rowptr, int32_t rows, int32_t nnz, int32_t heads, const float* x,
                                   const int32_t* perm, float* out, void* ws, size_t ws_bytes, void* stream) {
   int rc;
-  if (heads_args(rowptr, rows, nnz, heads, 0, ws, ws_bytes, heads_edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
+  if (heads_args(rowptr, rows, nnz, heads, 0, ws, ws_bytes, edge_workspace_bytes(nnz, heads > 0 ? heads : 1), &rc)) return rc;
   if (!x || !out) return GCN_ERR_INVALID_ARG;
   return launch_segment_sum_heads(rowptr, rows, nnz, heads, x, perm, out, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK
                                                                                                                   : GCN_ERR_HIP;

@@ -1,6 +1,9 @@
-// long_chunks.h — what the chunked long-row kernels of edge_softmax.hip and aggregate.hip share: finding the at most two
-// long rows that meet a chunk of consecutive entries.  The chunk loops, the partials and the finish kernels are each unit's
-// own.  Device code only; the long-row threshold is the caller's (LONG_ROW, at least the chunk length).
+// long_chunks.h — what the chunked long-row kernels of edge_softmax.hip, aggregate.hip and multihead.hip share: finding the
+// at most two long rows that meet a chunk of consecutive entries, and the walk over the chunks that the wave-per-chunk
+// kernels make (edge_softmax.hip's block-per-chunk kernels write the same loop out: through the helper one of them comes
+// out with other registers and another occupancy).  The partials and what a kernel does with a segment are
+// each unit's own.  Device code only; the chunk length and the long-row threshold are the caller's (CHUNK and LONG_ROW,
+// at least the chunk length).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +37,22 @@ __device__ __forceinline__ bool long_segment(const int* __restrict__ rowptr, int
   s.sb = s.rb > e0 ? s.rb : e0;
   s.se = s.re < e1 ? s.re : e1;
   return true;
+}
+
+// the chunks first, first + stride, ... (< nchunks) of CHUNK consecutive entries, a chunk per wave: f(c, slot, segment) for
+// the part of each long row inside chunk c (wave-uniform: whole waves call this, find_row votes).
+template <int CHUNK, int LONG_ROW, class F>
+__device__ __forceinline__ void for_long_segments(const int* __restrict__ rowptr, int rows, int nnz, int nchunks, int first,
+                                                  int stride, int lane, F f) {
+  for (int c = first; c < nchunks; c += stride) {
+    const int e0 = c * CHUNK;
+    const int e1 = (long long)e0 + CHUNK < nnz ? e0 + CHUNK : nnz;
+    const int rh = find_row(rowptr, rows, e0, lane), rt = find_row(rowptr, rows, e1 - 1, lane);
+    for (int slot = 0; slot < 2; ++slot) {
+      Segment s;
+      if (long_segment<LONG_ROW>(rowptr, slot, rh, rt, e0, e1, s)) f(c, slot, s);
+    }
+  }
 }
 
 }  // namespace gcn

@@ -164,10 +164,12 @@ hipError_t launch_sddmm(const SddmmArgs& s, hipStream_t st);
 bool sddmm_vec(const float* A, const float* B, int k);   // 16-byte loads (k % 4 == 0, aligned operands)
 
 // edge_softmax.hip — softmax over the stored entries of each CSR row, its backward, the fused GAT-score forms and CSR row
-// sums (plan-free, capturable, no atomics: see the file's header).  ws: edge_workspace_bytes(nnz) bytes of device memory —
-// a flag and one partial per (chunk of kEdgeChunk entries, long row) — owned by the call while it runs.
+// sums, for one head ([nnz] arrays) and for H heads in one pass ([nnz, H] arrays with an entry's heads contiguous, per-node
+// scalars [rows, H]; nnz * H < 2^31) (plan-free, capturable, no atomics: see the file's header).  The one-head launchers
+// are the H = 1 case of the _heads ones.  ws: edge_workspace_bytes(nnz, H) bytes of device memory — a flag and one partial
+// per (chunk of kEdgeChunk entries, long row, head) — owned by the call while it runs.
 constexpr int kEdgeChunk = 8192;
-size_t edge_workspace_bytes(int nnz);
+size_t edge_workspace_bytes(int nnz, int H = 1);
 hipError_t launch_edge_softmax(const int* rowptr, int m, int nnz, const float* s, float* p, void* ws, hipStream_t st);
 hipError_t launch_edge_softmax_backward(const int* rowptr, int m, int nnz, const float* p, const float* g, float* ds, void* ws,
                                         hipStream_t st);
@@ -178,6 +180,16 @@ hipError_t launch_gat_edge_softmax_backward(const int* rowptr, const int* col, i
                                             float* grad_a_dst, void* ws, hipStream_t st);
 hipError_t launch_segment_sum(const int* rowptr, int m, int nnz, const float* x, const int* perm, float* out, void* ws,
                               hipStream_t st);
+hipError_t launch_edge_softmax_heads(const int* rowptr, int m, int nnz, int H, const float* s, float* p, void* ws, hipStream_t st);
+hipError_t launch_edge_softmax_heads_backward(const int* rowptr, int m, int nnz, int H, const float* p, const float* g, float* ds,
+                                              void* ws, hipStream_t st);
+hipError_t launch_gat_edge_softmax_heads(const int* rowptr, const int* col, int m, int nnz, int H, const float* a_dst,
+                                         const float* a_src, float slope, float* p, void* ws, hipStream_t st);
+hipError_t launch_gat_edge_softmax_heads_backward(const int* rowptr, const int* col, int m, int nnz, int H, const float* a_dst,
+                                                  const float* a_src, float slope, const float* p, const float* g, float* ds,
+                                                  float* grad_a_dst, void* ws, hipStream_t st);
+hipError_t launch_segment_sum_heads(const int* rowptr, int rows, int nnz, int H, const float* x, const int* perm, float* out,
+                                    void* ws, hipStream_t st);
 
 // aggregate.hip — element-wise max / min over each CSR row's stored entries with the winning entry index, and its backward
 // as a walk of the transposed pattern (plan-free, capturable, no atomics: see the file's header).  x / out / g / gx are
@@ -191,23 +203,12 @@ hipError_t launch_aggregate(const int* rowptr, const int* col, int m, int nnz, c
 hipError_t launch_aggregate_backward(const int* trowptr, const int* trow, const int* tperm, int n, int nnz, const void* g, int bf16,
                                      const int* arg, int k, void* gx, void* ws, hipStream_t st);
 
-// multihead.hip — the attention primitives for H heads in one pass: per-head edge softmax (plain and fused GAT scores) with
-// their backwards, row sums of an [nnz, H] array, the head-weighted SpMM and the per-head SDDMM (plan-free, capturable, no
-// atomics: see the file's header).  Per-entry arrays are [nnz, H] with an entry's heads contiguous, node arrays [rows, H * F]
-// with k = H * F; nnz * H < 2^31.  ws: heads_*_workspace_bytes of device memory (a flag and the long rows' chunk partials).
-size_t heads_edge_workspace_bytes(int nnz, int H);
+// multihead.hip — the gather primitives of multi-head attention, H heads in one pass: the head-weighted SpMM and the
+// per-head SDDMM (plan-free, capturable, no atomics: see the file's header).  Per-entry arrays are [nnz, H] with an entry's
+// heads contiguous, node arrays [rows, H * F] with k = H * F; nnz * H < 2^31.  ws: heads_spmm_workspace_bytes /
+// kHeadsSddmmWsBytes of device memory (a flag and the long rows' chunk partials).
 size_t heads_spmm_workspace_bytes(int nnz, int k);
 constexpr size_t kHeadsSddmmWsBytes = 16;
-hipError_t launch_edge_softmax_heads(const int* rowptr, int m, int nnz, int H, const float* s, float* p, void* ws, hipStream_t st);
-hipError_t launch_edge_softmax_heads_backward(const int* rowptr, int m, int nnz, int H, const float* p, const float* g, float* ds,
-                                              void* ws, hipStream_t st);
-hipError_t launch_gat_edge_softmax_heads(const int* rowptr, const int* col, int m, int nnz, int H, const float* a_dst,
-                                         const float* a_src, float slope, float* p, void* ws, hipStream_t st);
-hipError_t launch_gat_edge_softmax_heads_backward(const int* rowptr, const int* col, int m, int nnz, int H, const float* a_dst,
-                                                  const float* a_src, float slope, const float* p, const float* g, float* ds,
-                                                  float* grad_a_dst, void* ws, hipStream_t st);
-hipError_t launch_segment_sum_heads(const int* rowptr, int rows, int nnz, int H, const float* x, const int* perm, float* out,
-                                    void* ws, hipStream_t st);
 hipError_t launch_spmm_heads(const int* rowptr, const int* idx, const int* perm, int rows, int nnz, int H, int k, const float* vals,
                              const float* x, float* out, void* ws, hipStream_t st);
 hipError_t launch_sddmm_heads(const int* rowptr, const int* col, int m, int nnz, int H, int k, const float* a, const float* b,

@@ -1,4 +1,4 @@
-"""All attention heads in one pass (gcn_amd/csrc/multihead.hip) on the GPU, against the fp64 twins of tests/heads_ref.py.
+"""All attention heads in one pass (gcn_amd/csrc/edge_softmax.hip, multihead.hip) on the GPU, against the fp64 twins of tests/heads_ref.py.
 
 * spmm_heads (forward and the transposed form through its permutation) and sddmm_heads: bit for bit on an exact grid (x
   integers in [-3, 3], values eighths in [0, 7/8]: every partial sum of at most 300 000 terms is below 2^24 eighths, so any
@@ -219,6 +219,7 @@ def test_segment_sum_heads_matches_fp64(name, H):
                           f"segment sum {name} H={H} {what}")
     if H == 1:                                             # the one-head 2-D form and the 1-D form are the same numbers
         one = gcn_amd.segment_sum(rpd, x[:, 0].contiguous().to(DEV))
+        assert torch.equal(one[:, None], out)
         assert_rows_close(g, one[:, None], heads_ref.segment_sum(g.rp_live, x64), heads_ref.segment_sum(g.rp_live, np.abs(x64)),
                           f"segment sum {name} 1-D")
 
@@ -538,6 +539,52 @@ def test_two_calls_are_bit_identical_and_p_may_alias_scores():
         assert st == 0
         torch.cuda.synchronize()
         assert torch.equal(buf, p1)
+
+
+@pytest.mark.parametrize("name", ["boundaries", "hubs"])
+def test_one_head_2d_forms_and_1d_forms_give_the_same_bits(name):
+    """[nnz, 1] / [rows, 1] operands and 1-D operands: the 1-D forms are the H = 1 case of the 2-D forms, bit for bit, forward
+    and backward, on a row either side of every threshold (boundaries) and on rows of 5 000 and 300 000 entries (hubs)"""
+    g = Graph.get(name)
+    madj = gcn_amd.CsrAdjacency(g.adj.rowptr, g.adj.col, torch.ones(g.nnz, device=DEV), (g.m, g.n), mutable_values=True)
+    gout = torch.randn(g.nnz, 1, generator=torch.Generator().manual_seed(13)).to(DEV)
+
+    def both(f2, f1, ops):
+        """[output, gradients ...] of f2 on the 2-D operands and of f1 on their 1-D forms, under the same upstream gradient"""
+        res = []
+        for f, flat in ((f2, False), (f1, True)):
+            leaves = [(o[:, 0].contiguous() if flat else o.clone()).requires_grad_(True) for o in ops]
+            out = f(*leaves)
+            out.backward(gout[:, 0].contiguous() if flat else gout)
+            res.append([out.detach()] + [t.grad for t in leaves])
+        return res
+
+    def same(two, one, what):
+        assert len(two) == len(one)
+        for i, (a, b) in enumerate(zip(two, one)):
+            assert a.shape == b.shape + (1,) and torch.equal(a[:, 0], b), (what, i)
+
+    same(*both(lambda s: gcn_amd.edge_softmax(g.adj, s), lambda s: gcn_amd.edge_softmax(g.adj, s), [scores_for(g, 1, seed=3)]),
+         "edge_softmax: p, ds")
+    a_dst, a_src = gat_inputs(g, 1, seed=4)
+    two, one = both(lambda d, s: gcn_amd.gat_edge_softmax(g.adj, d, s, 0.2), lambda d, s: gcn_amd.gat_edge_softmax(madj, d, s, 0.2),
+                    [a_dst, a_src])
+    same(two, one, "gat_edge_softmax: p, grad_a_dst, grad_a_src")
+    ds2, gd2 = raw_gat_backward(g.adj, a_dst, a_src, 0.2, two[0], gout)
+    ds1, gd1 = torch.empty(g.nnz, device=DEV), torch.empty(g.m, device=DEV)
+    ws = raw_ws(g.m, g.nnz, 1, 1)
+    st = gcn_amd.load_library().gcn_gat_edge_softmax_backward_csr_f32(
+        vp(g.adj.rowptr), vp(g.adj.col), g.m, g.nnz, vp(a_dst[:, 0].contiguous()), vp(a_src[:, 0].contiguous()), 0.2, vp(one[0]),
+        vp(gout[:, 0].contiguous()), vp(ds1), vp(gd1), vp(ws), ws.numel(), stream())
+    torch.cuda.synchronize()
+    assert st == 0
+    same([ds2, gd2], [ds1, gd1], "fused backward: ds, grad_a_dst")
+    assert torch.equal(gd1, one[1])
+    x = torch.randn(g.nnz, 1, generator=torch.Generator().manual_seed(14)).to(DEV)
+    perm = torch.randperm(g.nnz, generator=torch.Generator().manual_seed(15)).to(DEV, torch.int32)
+    for pm in (None, perm):
+        same([gcn_amd.segment_sum(g.adj.rowptr, x, perm=pm)], [gcn_amd.segment_sum(g.adj.rowptr, x[:, 0].contiguous(), perm=pm)],
+             "segment_sum" + (" permuted" if pm is not None else ""))
 
 
 def _dense_gat(x, mask, weight, att_dst, att_src, bias, heads, out_f, concat, slope):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """All attention heads in one pass on the headline graph (Reddit-shaped, graphgen.make_graph("reddit")): milliseconds of
-each head-batched kernel (gcn_amd/csrc/multihead.hip) at H heads x F columns, of one GraphAttention forward + backward
+each head-batched kernel (gcn_amd/csrc/edge_softmax.hip, multihead.hip) at H heads x F columns, of one GraphAttention forward + backward
 with head_batched=True and, in the same run, with the per-head loop (head_batched=False) — and three yardsticks that are
 not the code under test: the weighted spmm(adj, x, values=) at the same k, and the single-head edge softmax and GAT
 softmax whose time x H is what the per-head loop pays.
