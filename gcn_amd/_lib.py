@@ -141,6 +141,11 @@ SIGNATURES = {
                                               ctypes.c_size_t, _c_p]),
     "gcn_sddmm_heads_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t,
                                                _c_p]),
+    "gcn_gatv2_ws_bytes": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i32, ctypes.POINTER(ctypes.c_size_t)]),
+    "gcn_gatv2_scores_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, ctypes.c_float, _c_p,
+                                                _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_gatv2_scores_backward_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p,
+                                                         ctypes.c_float, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_aggregate_csr": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p,
                                          ctypes.c_size_t, _c_p]),
     "gcn_aggregate_backward_csr": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_p,

@@ -13,6 +13,7 @@ aggregation and its score counterpart (gcn_amd/csrc/multihead.hip) are
     p = gcn_amd.gat_edge_softmax(adj, a_dst, a_src, 0.2)     # a_dst [m, H], a_src [n, H] -> p [nnz, H]
     out = gcn_amd.spmm_heads(adj, x, p)                      # x [n, H*F]: out[r, hF+j] = sum_e p[e, h] x[col[e], hF+j]
     s = gcn_amd.sddmm_heads(adj, a, b, heads)                # s[e, h] = <a[row(e), head h], b[col[e], head h]>
+    s = gcn_amd.gatv2_scores(adj, h_dst, h_src, att, 0.2)    # s[e, h] = <att[h], leaky_relu(h_dst[row(e)] + h_src[col[e]])>
 
 The kernels take no plan and only enqueue, so all of this runs inside a captured step.  Unlike ``torch.softmax`` a row
 whose scores are all -inf gets zeros, not NaN (a fully masked row stays usable).  There is no CPU path: CPU tensors raise.
@@ -372,3 +373,97 @@ def sddmm_heads(adj, a, b, heads):
     _fp32_tensors([(a, (adj.m, k), "sddmm_heads: a", f"a 2-D tensor [{adj.m}, {k}]"),
                    (b, (adj.n, k), "sddmm_heads: b", f"a 2-D tensor [{adj.n}, {k}]")])
     return _SddmmHeadsFunction.apply(adj, a, b, heads)
+
+
+# ---- GATv2 scores (gcn_amd/csrc/multihead.hip) -------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _gatv2_ws_need(nnz, heads, k):
+    need = ctypes.c_size_t(0)
+    _lib.check(_lib.load().gcn_gatv2_ws_bytes(0, nnz, heads, k, ctypes.byref(need)), "gcn_gatv2_ws_bytes")
+    return need.value
+
+
+def _gatv2_workspace(adj, device, heads, k):
+    """the scratch of the three GATv2 calls (gcn_gatv2_ws_bytes: a flag and the chunk partials of the backward's two sums),
+    kept on the adjacency like _workspace's and allocated at the first forward, so before a capture"""
+    need = _gatv2_ws_need(int(adj.nnz), int(heads), int(k))
+    ws = getattr(adj, "_gatv2_ws", None)
+    if ws is None or ws.numel() < need or ws.device != device:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        adj._gatv2_ws = ws
+    return ws
+
+
+def _gatv2_backward_raw(adj, rowptr, idx, perm, rows, own, other, att, slope, g, want_act):
+    """(grad_own [rows, k], act_sums [rows, k] or None) of gcn_gatv2_scores_backward_csr_f32 over (rowptr, idx, perm)"""
+    heads, k = int(att.shape[0]), int(own.shape[1])
+    grad = torch.empty(rows, k, dtype=torch.float32, device=own.device)
+    act = torch.empty(rows, k, dtype=torch.float32, device=own.device) if want_act else None
+    if rows == 0 or adj.nnz == 0:
+        return grad.zero_(), (act.zero_() if want_act else None)
+    ws = _gatv2_workspace(adj, own.device, heads, k)
+    with torch.cuda.device(own.device):
+        st = _lib.load().gcn_gatv2_scores_backward_csr_f32(
+            _ptr(rowptr), _ptr(idx), _ptr(perm) if perm is not None else None, rows, adj.nnz, heads, k, _ptr(own), _ptr(other),
+            _ptr(att), slope, _ptr(g), _ptr(grad), _ptr(act) if want_act else None, _ptr(ws), ws.numel(),
+            _stream_ptr(own.device))
+    _lib.check(st, "gcn_gatv2_scores_backward_csr_f32")
+    return grad, act
+
+
+class _Gatv2ScoresFunction(torch.autograd.Function):
+    """s = gatv2_scores(adj, h_dst, h_src, att); the backward recomputes t = h_dst[row] + h_src[col] in two row walks: the
+    pattern gives grad h_dst and the [m, k] sums whose column sums are grad att, the transposed pattern gives grad h_src"""
+
+    @staticmethod
+    def forward(ctx, adj, h_dst, h_src, att, slope):
+        hd, hs, a = h_dst.detach().contiguous(), h_src.detach().contiguous(), att.detach().contiguous()
+        heads, k = int(a.shape[0]), int(hd.shape[1])
+        out = torch.empty(adj.nnz, heads, dtype=torch.float32, device=hd.device)
+        if adj.m and adj.nnz:
+            ws = _gatv2_workspace(adj, hd.device, heads, k)
+            with torch.cuda.device(hd.device):
+                st = _lib.load().gcn_gatv2_scores_csr_f32(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, heads, k, _ptr(hd),
+                                                          _ptr(hs), _ptr(a), slope, _ptr(out), _ptr(ws), ws.numel(),
+                                                          _stream_ptr(hd.device))
+            _lib.check(st, "gcn_gatv2_scores_csr_f32")
+        ctx.adj, ctx.slope = adj, slope
+        ctx.save_for_backward(hd, hs, a)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        hd, hs, a = ctx.saved_tensors
+        adj = ctx.adj
+        g = g.contiguous()
+        g_dst = g_src = g_att = None
+        need_dst, need_src, need_att = ctx.needs_input_grad[1:4]
+        if need_dst or need_att:
+            g_dst, act = _gatv2_backward_raw(adj, adj.rowptr, adj.col, None, adj.m, hd, hs, a, ctx.slope, g, need_att)
+            if need_att:
+                g_att = act.sum(0).view_as(a)
+            if not need_dst:
+                g_dst = None
+        if need_src:
+            trp, trow, tperm = _heads_tpattern(adj)
+            g_src, _ = _gatv2_backward_raw(adj, trp, trow, tperm, adj.n, hs, hd, a, ctx.slope, g, False)
+        return None, g_dst, g_src, g_att, None
+
+
+def gatv2_scores(adj, h_dst, h_src, att, negative_slope=0.2):
+    """s[e, h] = sum over j < F of att[h, j] * leaky_relu(h_dst[row(e), hF + j] + h_src[col[e], hF + j], negative_slope) for
+    every stored entry e of adj: the attention scores of GATv2 (Brody et al. 2022), computed per entry inside the kernel —
+    no [nnz, H*F] array is formed, forward or backward (gcn_gatv2_scores_csr_f32).  h_dst: [m, H*F], h_src: [n, H*F],
+    att: [H, F], all fp32; returns [nnz, H] in adj's CSR order, for edge_softmax and then spmm_heads.  Any CsrAdjacency,
+    square or rectangular; its values are ignored.  Differentiable in all three operands (two row walks, on the pattern and
+    on its transpose, and one [m, H*F] column sum); the same tensor may be passed as h_dst and h_src.  The derivative of
+    leaky_relu at 0 is the slope."""
+    if not isinstance(adj, CsrAdjacency):
+        raise TypeError("gatv2_scores: adj must be a CsrAdjacency")
+    if not isinstance(att, torch.Tensor) or att.dim() != 2 or att.shape[0] < 1 or att.shape[1] < 1:
+        raise ValueError("gatv2_scores: att must be a 2-D tensor [H, F]")
+    heads, k = int(att.shape[0]), int(att.shape[0]) * int(att.shape[1])
+    _fp32_tensors([(h_dst, (adj.m, k), "gatv2_scores: h_dst", f"a 2-D tensor [{adj.m}, {k}]"),
+                   (h_src, (adj.n, k), "gatv2_scores: h_src", f"a 2-D tensor [{adj.n}, {k}]"),
+                   (att, (heads, None), "gatv2_scores: att", "a 2-D tensor [H, F]")])
+    return _Gatv2ScoresFunction.apply(adj, h_dst, h_src, att, float(negative_slope))

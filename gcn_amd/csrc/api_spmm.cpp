@@ -309,6 +309,38 @@ int gcn_sddmm_heads_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t m
   return launch_sddmm_heads(rowptr, col, m, nnz, heads, k, a, b, out, ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
 }
 
+int gcn_gatv2_ws_bytes(int32_t m, int32_t nnz, int32_t heads, int32_t k, size_t* bytes) {
+  int rc;
+  if (!bytes || k < 1) return GCN_ERR_INVALID_ARG;
+  heads_args(nullptr, 0, nnz, heads, k, nullptr, 0, 0, &rc);                  // (the size rules alone)
+  if (rc != GCN_OK || m < 0) return GCN_ERR_INVALID_ARG;
+  *bytes = gatv2_workspace_bytes(nnz, k);
+  return GCN_OK;
+}
+
+int gcn_gatv2_scores_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t nnz, int32_t heads, int32_t k,
+                             const float* h_dst, const float* h_src, const float* att, float negative_slope, float* out, void* ws,
+                             size_t ws_bytes, void* stream) {
+  int rc;
+  if (k < 1) return GCN_ERR_INVALID_ARG;
+  if (heads_args(rowptr, m, nnz, heads, k, ws, ws_bytes, gatv2_workspace_bytes(nnz, k), &rc)) return rc;
+  if (!col || !h_dst || !h_src || !att || !out) return GCN_ERR_INVALID_ARG;
+  return launch_gatv2_scores(rowptr, col, m, nnz, heads, k, h_dst, h_src, att, negative_slope, out, ws, (hipStream_t)stream) ==
+                 hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_gatv2_scores_backward_csr_f32(const int32_t* rowptr, const int32_t* idx, const int32_t* perm, int32_t rows, int32_t nnz,
+                                      int32_t heads, int32_t k, const float* own, const float* other, const float* att,
+                                      float negative_slope, const float* g, float* grad_own, float* act_sums, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  int rc;
+  if (k < 1) return GCN_ERR_INVALID_ARG;
+  if (heads_args(rowptr, rows, nnz, heads, k, ws, ws_bytes, gatv2_workspace_bytes(nnz, k), &rc)) return rc;
+  if (!idx || !own || !other || !att || !g || !grad_own) return GCN_ERR_INVALID_ARG;
+  return launch_gatv2_scores_backward(rowptr, idx, perm, rows, nnz, heads, k, own, other, att, negative_slope, g, grad_own, act_sums,
+                                      ws, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
 // k, op / dtype and the sizes first; then what an empty problem still needs; 1 = return *status
 static int aggregate_args(int32_t rows_out, int32_t rows_in, int32_t nnz, int32_t dtype, int32_t k, int* status) {
   *status = GCN_OK;

@@ -26,6 +26,17 @@
 //    Fixed order of an (entry, head) sum, a function of F and VEC only — not of the row, the chunk, the slot or H:
 //    s_p = fma chain over the units p, p + P, ... in ascending order, a unit's elements in ascending order; then
 //    P = 2: s0 + s1, P = 4: (s0 + s2) + (s1 + s3).
+//
+// 3. gatv2_scores: the walk of 2 with another per-element op — s[e, h] = sum_j att[h, j] leaky_relu(a[row(e), hF + j] +
+//    b[col[e], hF + j]): t = a + b; t = t > 0 ? t : slope * t; acc = fma(att[j], t, acc) — so the same routes and the same
+//    fixed order of an (entry, head) sum as sddmm_heads; att [H, F] is read with the unit's 16-byte (or one-word) load.
+//    Its backward is the walk of 1 with another per-element op, run once on the pattern and once on its transpose: with
+//    t = own[r, j] + other[idx[e], j] and D = t > 0 ? 1 : slope (the slope at 0) a lane keeps
+//    mask[j] += g[e, h] * D and, where asked for, act[j] += g[e, h] * (t * D); grad_own[r, j] = att[j] * mask[j], multiplied
+//    once after the merge, act_sums[r, j] = act[j] (grad_att is its column sums).  Long rows keep chunk partials of both
+//    sums (the second set behind the first).  Fixed order, as in 1: slot s adds the entries s, s + SLOTS, ... in ascending
+//    order (fma), the slots are merged by the xor butterfly LPS .. 32, chunk partials in chunk order.  An empty row
+//    writes zeros.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -69,9 +80,72 @@ struct HeadsSpmmArgs {
   int H, F, k;
 };
 
+// The per-element op of the row walk.  A lane keeps NS running sums for its VEC columns of a row, sum q in acc[q VEC ..],
+// and in Row what begin() fetched of the row itself; a gathered element x of an entry with value w adds
+// fma(w, term(q, row, v, x), .) to sum q; store() is what the merged sums of a row become (store_one: one element, for the
+// long rows).  The fma stays in the walk: an op that did the accumulation itself cost the existing kernels registers.
+// spmm_heads: out[r, j] = sum of w * x[j].
+struct WeightedSumOp {
+  static constexpr int NS = 1;
+  template <int VEC>
+  struct Row {};
+  template <int VEC>
+  __device__ __forceinline__ void begin(const HeadsSpmmArgs&, int, int, Row<VEC>&) const {}
+  template <int VEC>
+  __device__ __forceinline__ float term(int, const Row<VEC>&, int, float x) const { return x; }
+  template <int VEC>
+  __device__ __forceinline__ void store(const HeadsSpmmArgs& a, int r, int j, const float (&acc)[VEC]) const {
+    store_row<VEC>(a.out + (size_t)r * a.k + j, acc);
+  }
+  __device__ __forceinline__ void store_one(const HeadsSpmmArgs& a, int r, int j, int, float v) const { a.out[(size_t)r * a.k + j] = v; }
+};
+
+// the backward of gatv2_scores on one side (a.vals = g, a.x = the gathered side, a.out = grad_own): with t = own + x and
+// D = t > 0 ? 1 : slope, sum 0 (mask) takes w * D and, with ACT, sum 1 (act) takes w * (t * D); grad_own = att * mask,
+// act_sums = act
+template <bool ACT>
+struct Gatv2BackwardOp {
+  static constexpr int NS = ACT ? 2 : 1;
+  const float *own, *att;
+  float* act_sums;
+  float slope;
+  template <int VEC>
+  struct Row {
+    float own[VEC];
+  };
+  template <int VEC>
+  __device__ __forceinline__ void begin(const HeadsSpmmArgs& a, int r, int jl, Row<VEC>& row) const {
+    load_row<VEC>(own + (size_t)r * a.k + jl, row.own);
+  }
+  template <int VEC>
+  __device__ __forceinline__ float term(int q, const Row<VEC>& row, int v, float x) const {
+    const float t = row.own[v] + x;
+    const float d = t > 0.f ? 1.f : slope;
+    return q == 0 ? d : t * d;
+  }
+  template <int VEC>
+  __device__ __forceinline__ void store(const HeadsSpmmArgs& a, int r, int j, const float (&acc)[NS * VEC]) const {
+    float w[VEC], gr[VEC], ac[VEC];
+    load_row<VEC>(att + j, w);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) gr[v] = w[v] * acc[v];
+    store_row<VEC>(a.out + (size_t)r * a.k + j, gr);
+    if constexpr (ACT) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) ac[v] = acc[VEC + v];
+      store_row<VEC>(act_sums + (size_t)r * a.k + j, ac);
+    }
+  }
+  __device__ __forceinline__ void store_one(const HeadsSpmmArgs& a, int r, int j, int q, float v) const {
+    if (q == 0) a.out[(size_t)r * a.k + j] = att[j] * v;
+    else act_sums[(size_t)r * a.k + j] = v;
+  }
+};
+
 // entries [b, b + n) of one row (n <= kGChunk) on a wave; the lane's columns are j .. j + VEC of head `head` (jok: they exist)
-template <int VEC, int LPS>
-__device__ __forceinline__ void spmm_walk(const HeadsSpmmArgs& a, int b, int n, int lane, int j, bool jok, int head, float (&acc)[VEC]) {
+template <int VEC, int LPS, class Op>
+__device__ __forceinline__ void spmm_walk(const HeadsSpmmArgs& a, const Op& op, int b, int n, int lane, int j, bool jok, int head,
+                                          const typename Op::template Row<VEC>& row, float (&acc)[Op::NS * VEC]) {
   constexpr int SLOTS = 64 / LPS, BATCH = 4 * SLOTS;
   const int slot = lane / LPS;
   const int jl = jok ? j : 0, hl = jok ? head : 0;     // (lanes past k gather column 0 and add nothing)
@@ -93,7 +167,11 @@ __device__ __forceinline__ void spmm_walk(const HeadsSpmmArgs& a, int b, int n, 
       for (int u = 0; u < 4; ++u) {                    // (slot s takes entries s, s + SLOTS, ...: ascending inside a lane)
         const bool ok = jok && i0 + SLOTS * u + slot < cnt;
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[v] = ok ? __builtin_fmaf(w[u], xv[u][v], acc[v]) : acc[v];
+        for (int v = 0; v < VEC; ++v) {
+#pragma unroll
+          for (int q = 0; q < Op::NS; ++q)
+            acc[q * VEC + v] = ok ? __builtin_fmaf(w[u], op.term(q, row, v, xv[u][v]), acc[q * VEC + v]) : acc[q * VEC + v];
+        }
       }
     }
   }
@@ -108,8 +186,8 @@ __device__ __forceinline__ void merge_slots(float (&acc)[VEC]) {
   }
 }
 
-template <int VEC, int LPS>
-__global__ void __launch_bounds__(256) spmm_heads_rows_kernel(HeadsSpmmArgs a, const int* __restrict__ rowptr, int rows,
+template <int VEC, int LPS, class Op>
+__global__ void __launch_bounds__(256) spmm_heads_rows_kernel(HeadsSpmmArgs a, Op op, const int* __restrict__ rowptr, int rows,
                                                               int* __restrict__ long_flag) {
   const int lane = threadIdx.x & 63;
   const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
@@ -127,17 +205,19 @@ __global__ void __launch_bounds__(256) spmm_heads_rows_kernel(HeadsSpmmArgs a, c
       if (lane == 0) *long_flag = 1;
       continue;
     }
-    float acc[VEC];
+    typename Op::template Row<VEC> row;
+    float acc[Op::NS * VEC];
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-    spmm_walk<VEC, LPS>(a, b, n, lane, j, jok, head, acc);
-    merge_slots<VEC, LPS>(acc);
-    if (lane < LPS && jok) store_row<VEC>(a.out + (size_t)(r0 + q) * a.k + j, acc);
+    for (int v = 0; v < Op::NS * VEC; ++v) acc[v] = 0.f;
+    op.begin(a, r0 + q, jok ? j : 0, row);
+    spmm_walk<VEC, LPS>(a, op, b, n, lane, j, jok, head, row, acc);
+    merge_slots<Op::NS * VEC, LPS>(acc);
+    if (lane < LPS && jok) op.template store<VEC>(a, r0 + q, j, acc);
   }
 }
 
-template <int VEC, int LPS>
-__global__ void __launch_bounds__(256) spmm_heads_long_partial_kernel(HeadsSpmmArgs a, const int* __restrict__ rowptr, int rows, int nnz,
+template <int VEC, int LPS, class Op>
+__global__ void __launch_bounds__(256) spmm_heads_long_partial_kernel(HeadsSpmmArgs a, Op op, const int* __restrict__ rowptr, int rows, int nnz,
                                                                       int nchunks, const int* __restrict__ long_flag,
                                                                       float* __restrict__ part) {
   if (*long_flag == 0) return;
@@ -147,21 +227,26 @@ __global__ void __launch_bounds__(256) spmm_heads_long_partial_kernel(HeadsSpmmA
   const bool jok = j < a.k;
   const int head = jok ? j / a.F : 0;
   for_long_segments<kGChunk, kGLong>(rowptr, rows, nnz, nchunks, wave, nwaves, lane, [&](int c, int slot, const Segment& sg) {
-    float acc[VEC];
+    typename Op::template Row<VEC> row;
+    float acc[Op::NS * VEC];
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-    spmm_walk<VEC, LPS>(a, sg.sb, sg.se - sg.sb, lane, j, jok, head, acc);
-    merge_slots<VEC, LPS>(acc);
+    for (int v = 0; v < Op::NS * VEC; ++v) acc[v] = 0.f;
+    op.begin(a, sg.r, jok ? j : 0, row);
+    spmm_walk<VEC, LPS>(a, op, sg.sb, sg.se - sg.sb, lane, j, jok, head, row, acc);
+    merge_slots<Op::NS * VEC, LPS>(acc);
     if (lane < LPS && jok) {
-      float* p = part + (2 * (size_t)c + slot) * a.k + j;
 #pragma unroll
-      for (int v = 0; v < VEC; ++v) p[v] = acc[v];
+      for (int t = 0; t < Op::NS; ++t) {               // (sum t's partials: the t-th set of 2 nchunks rows)
+        float* p = part + ((size_t)t * 2 * nchunks + 2 * (size_t)c + slot) * a.k + j;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) p[v] = acc[t * VEC + v];
+      }
     }
   });
 }
 
-template <int VEC, int LPS>
-__global__ void __launch_bounds__(256) spmm_heads_long_finish_kernel(HeadsSpmmArgs a, const int* __restrict__ rowptr, int rows, int nnz,
+template <int VEC, int LPS, class Op>
+__global__ void __launch_bounds__(256) spmm_heads_long_finish_kernel(HeadsSpmmArgs a, Op op, const int* __restrict__ rowptr, int rows, int nnz,
                                                                      int nchunks, const int* __restrict__ long_flag,
                                                                      const float* __restrict__ part) {
   if (*long_flag == 0) return;
@@ -175,39 +260,43 @@ __global__ void __launch_bounds__(256) spmm_heads_long_finish_kernel(HeadsSpmmAr
     if (c != c_first) return;
     const int first_slot = sg.rb > c_first * kGChunk ? 1 : 0;
     for (int j = j0 + lane; j < j1; j += 64) {
-      float acc = part[(2 * (size_t)c_first + first_slot) * a.k + j];
-      for (int cc = c_first + 1; cc <= c_last; ++cc) acc += part[2 * (size_t)cc * a.k + j];
-      a.out[(size_t)sg.r * a.k + j] = acc;
+#pragma unroll
+      for (int t = 0; t < Op::NS; ++t) {
+        const float* pt = part + (size_t)t * 2 * nchunks * a.k;
+        float acc = pt[(2 * (size_t)c_first + first_slot) * a.k + j];
+        for (int cc = c_first + 1; cc <= c_last; ++cc) acc += pt[2 * (size_t)cc * a.k + j];
+        op.store_one(a, sg.r, j, t, acc);
+      }
     }
   });
 }
 
-template <int VEC, int LPS>
-hipError_t run_spmm(const HeadsSpmmArgs& a, const int* rowptr, int rows, int nnz, void* ws, hipStream_t st) {
+template <int VEC, int LPS, class Op>
+hipError_t run_spmm(const HeadsSpmmArgs& a, const Op& op, const int* rowptr, int rows, int nnz, void* ws, hipStream_t st) {
   int* flag = static_cast<int*>(ws);
   float* part = reinterpret_cast<float*>(static_cast<char*>(ws) + 16);
   const long long tiles = ((long long)a.k + LPS * VEC - 1) / (LPS * VEC);
   if (tiles > 65535) return hipErrorInvalidValue;
   if (hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), st); e != hipSuccess) return e;
   const long long waves = ((long long)rows + kRowsPerWave - 1) / kRowsPerWave;
-  spmm_heads_rows_kernel<VEC, LPS><<<dim3((unsigned)((waves + 3) / 4), (unsigned)tiles), 256, 0, st>>>(a, rowptr, rows, flag);
+  spmm_heads_rows_kernel<VEC, LPS, Op><<<dim3((unsigned)((waves + 3) / 4), (unsigned)tiles), 256, 0, st>>>(a, op, rowptr, rows, flag);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   if (nnz <= kGLong) return hipSuccess;
   const int nchunks = (int)(((long long)nnz + kGChunk - 1) / kGChunk);
   const int nw = nchunks < kGLongWaves ? nchunks : kGLongWaves;
   const dim3 grid((unsigned)((nw + 3) / 4), (unsigned)tiles);
-  spmm_heads_long_partial_kernel<VEC, LPS><<<grid, 256, 0, st>>>(a, rowptr, rows, nnz, nchunks, flag, part);
+  spmm_heads_long_partial_kernel<VEC, LPS, Op><<<grid, 256, 0, st>>>(a, op, rowptr, rows, nnz, nchunks, flag, part);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  spmm_heads_long_finish_kernel<VEC, LPS><<<grid, 256, 0, st>>>(a, rowptr, rows, nnz, nchunks, flag, part);
+  spmm_heads_long_finish_kernel<VEC, LPS, Op><<<grid, 256, 0, st>>>(a, op, rowptr, rows, nnz, nchunks, flag, part);
   return hipGetLastError();
 }
 
-template <int VEC>
-hipError_t run_spmm_vec(const HeadsSpmmArgs& a, const int* rowptr, int rows, int nnz, void* ws, hipStream_t st) {
+template <int VEC, class Op>
+hipError_t run_spmm_vec(const HeadsSpmmArgs& a, const Op& op, const int* rowptr, int rows, int nnz, void* ws, hipStream_t st) {
   const int units = a.k / VEC;
-  if (units <= 16) return run_spmm<VEC, 16>(a, rowptr, rows, nnz, ws, st);
-  if (units <= 32) return run_spmm<VEC, 32>(a, rowptr, rows, nnz, ws, st);
-  return run_spmm<VEC, 64>(a, rowptr, rows, nnz, ws, st);
+  if (units <= 16) return run_spmm<VEC, 16>(a, op, rowptr, rows, nnz, ws, st);
+  if (units <= 32) return run_spmm<VEC, 32>(a, op, rowptr, rows, nnz, ws, st);
+  return run_spmm<VEC, 64>(a, op, rowptr, rows, nnz, ws, st);
 }
 
 // ---- SDDMM -----------------------------------------------------------------------------------------------------------------------
@@ -221,6 +310,32 @@ struct SddmmHeadsArgs {
   int nu;                                              // F / VEC units per head
 };
 
+// The per-element op of the entry walk: acc' = elem(w, a, b, acc) over a head's columns, w what weights() brings for the unit
+// at node column jj.  sddmm_heads: the dot product, acc' = fma(a, b, acc).
+struct DotOp {
+  template <int VEC>
+  __device__ __forceinline__ void weights(int, float (&w)[VEC]) const {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) w[v] = 0.f;
+  }
+  __device__ __forceinline__ float elem(float, float a, float b, float acc) const { return __builtin_fmaf(a, b, acc); }
+};
+
+// gatv2_scores: acc' = fma(att[jj], leaky_relu(a + b), acc); att [H, F] row-major, so its flat index is the node column
+struct Gatv2ScoreOp {
+  const float* att;
+  float slope;
+  template <int VEC>
+  __device__ __forceinline__ void weights(int jj, float (&w)[VEC]) const {
+    load_row<VEC>(att + jj, w);
+  }
+  __device__ __forceinline__ float elem(float w, float a, float b, float acc) const {
+    float t = a + b;
+    t = t > 0.f ? t : slope * t;
+    return __builtin_fmaf(w, t, acc);
+  }
+};
+
 // the merge of the P partial sums of an (entry, head): the butterfly's order, P = 2: s0 + s1, P = 4: (s0 + s2) + (s1 + s3)
 __device__ __forceinline__ float merge_parts(float s, int pshift) {
   if (pshift == 2) s += __shfl_xor(s, 2);
@@ -229,8 +344,8 @@ __device__ __forceinline__ float merge_parts(float s, int pshift) {
 }
 
 // entries [b0, b0 + n) of row r (0 < n <= kGChunk) on a wave
-template <int VEC>
-__device__ __forceinline__ void sddmm_entries(const SddmmHeadsArgs& s, int r, int b0, int n, int lane) {
+template <int VEC, class Op>
+__device__ __forceinline__ void sddmm_entries(const SddmmHeadsArgs& s, const Op& op, int r, int b0, int n, int lane) {
   const float* arow = s.a + (size_t)r * s.k;
   if (s.hshift >= 0) {                                 // fast route: H P adjacent lanes an entry, 64 / (H P) entries a step
     const int gshift = s.hshift + s.pshift;            // (H P <= 64)
@@ -250,14 +365,15 @@ __device__ __forceinline__ void sddmm_entries(const SddmmHeadsArgs& s, int r, in
       }
       for (int q = 0; q < upl; ++q) {
         const int jj = head * s.F + ((q << s.pshift) + part) * VEC;
-        float av[VEC], bv[4][VEC];
+        float av[VEC], wv[VEC], bv[4][VEC];
         load_row<VEC>(arow + jj, av);
+        op.weights(jj, wv);
 #pragma unroll
         for (int u = 0; u < 4; ++u) load_row<VEC>(s.b + (size_t)c[u] * s.k + jj, bv[u]);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
 #pragma unroll
-          for (int v = 0; v < VEC; ++v) acc[u] = __builtin_fmaf(av[v], bv[u][v], acc[u]);
+          for (int v = 0; v < VEC; ++v) acc[u] = op.elem(wv[v], av[v], bv[u][v], acc[u]);
         }
       }
 #pragma unroll
@@ -277,12 +393,13 @@ __device__ __forceinline__ void sddmm_entries(const SddmmHeadsArgs& s, int r, in
     for (int h = 0; h < s.H; ++h) {
       float ps[4] = {0.f, 0.f, 0.f, 0.f};
       for (int u = 0; u < s.nu; ++u) {
-        float av[VEC], bv[VEC];
+        float av[VEC], wv[VEC], bv[VEC];
         load_row<VEC>(arow + h * s.F + u * VEC, av);
+        op.weights(h * s.F + u * VEC, wv);
         load_row<VEC>(brow + h * s.F + u * VEC, bv);
         float t = ps[u & (P - 1)];
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) t = __builtin_fmaf(av[v], bv[v], t);
+        for (int v = 0; v < VEC; ++v) t = op.elem(wv[v], av[v], bv[v], t);
         ps[u & (P - 1)] = t;
       }
       const float t = P == 4 ? (ps[0] + ps[2]) + (ps[1] + ps[3]) : P == 2 ? ps[0] + ps[1] : ps[0];
@@ -291,8 +408,8 @@ __device__ __forceinline__ void sddmm_entries(const SddmmHeadsArgs& s, int r, in
   }
 }
 
-template <int VEC>
-__global__ void __launch_bounds__(256) sddmm_heads_rows_kernel(SddmmHeadsArgs s, const int* __restrict__ rowptr, int m,
+template <int VEC, class Op>
+__global__ void __launch_bounds__(256) sddmm_heads_rows_kernel(SddmmHeadsArgs s, Op op, const int* __restrict__ rowptr, int m,
                                                                int* __restrict__ long_flag) {
   const int lane = threadIdx.x & 63;
   const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
@@ -307,39 +424,47 @@ __global__ void __launch_bounds__(256) sddmm_heads_rows_kernel(SddmmHeadsArgs s,
       if (lane == 0) *long_flag = 1;
       continue;
     }
-    if (n > 0) sddmm_entries<VEC>(s, r0 + q, b, n, lane);
+    if (n > 0) sddmm_entries<VEC>(s, op, r0 + q, b, n, lane);
   }
 }
 
-template <int VEC>
-__global__ void __launch_bounds__(256) sddmm_heads_long_kernel(SddmmHeadsArgs s, const int* __restrict__ rowptr, int m, int nnz,
+template <int VEC, class Op>
+__global__ void __launch_bounds__(256) sddmm_heads_long_kernel(SddmmHeadsArgs s, Op op, const int* __restrict__ rowptr, int m, int nnz,
                                                                int nchunks, const int* __restrict__ long_flag) {
   if (*long_flag == 0) return;
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = gridDim.x * 4;
   for_long_segments<kGChunk, kGLong>(rowptr, m, nnz, nchunks, wave, nwaves, lane, [&](int c, int slot, const Segment& sg) {
-    sddmm_entries<VEC>(s, sg.r, sg.sb, sg.se - sg.sb, lane);
+    sddmm_entries<VEC>(s, op, sg.r, sg.sb, sg.se - sg.sb, lane);
   });
 }
 
-template <int VEC>
-hipError_t run_sddmm(SddmmHeadsArgs s, const int* rowptr, int m, int nnz, void* ws, hipStream_t st) {
+template <int VEC, class Op>
+hipError_t run_sddmm(SddmmHeadsArgs s, const Op& op, const int* rowptr, int m, int nnz, void* ws, hipStream_t st) {
   s.nu = s.F / VEC;
   const int low = s.nu & -s.nu;                        // the largest power of two dividing the units of a head
   s.pshift = low >= 4 ? 2 : low >= 2 ? 1 : 0;
   int* flag = static_cast<int*>(ws);
   if (hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), st); e != hipSuccess) return e;
   const long long waves = ((long long)m + kRowsPerWave - 1) / kRowsPerWave;
-  sddmm_heads_rows_kernel<VEC><<<(unsigned)((waves + 3) / 4), 256, 0, st>>>(s, rowptr, m, flag);
+  sddmm_heads_rows_kernel<VEC, Op><<<(unsigned)((waves + 3) / 4), 256, 0, st>>>(s, op, rowptr, m, flag);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   if (nnz <= kGLong) return hipSuccess;
   const int nchunks = (int)(((long long)nnz + kGChunk - 1) / kGChunk);
   const int nw = nchunks < kGLongWaves ? nchunks : kGLongWaves;
-  sddmm_heads_long_kernel<VEC><<<(unsigned)((nw + 3) / 4), 256, 0, st>>>(s, rowptr, m, nnz, nchunks, flag);
+  sddmm_heads_long_kernel<VEC, Op><<<(unsigned)((nw + 3) / 4), 256, 0, st>>>(s, op, rowptr, m, nnz, nchunks, flag);
   return hipGetLastError();
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// log2 H where the entry walk has its fast route (H a power of two <= kMaxFastHeads), -1 otherwise
+int fast_hshift(int H) {
+  if (H > kMaxFastHeads || (H & (H - 1)) != 0) return -1;
+  int hshift = 0;
+  while ((1 << hshift) < H) ++hshift;
+  return hshift;
+}
 
 }  // namespace
 
@@ -353,18 +478,42 @@ hipError_t launch_spmm_heads(const int* rowptr, const int* idx, const int* perm,
                              const float* x, float* out, void* ws, hipStream_t st) {
   const HeadsSpmmArgs a{idx, perm, vals, x, out, H, k / H, k};
   const bool wide = (k / H) % 4 == 0 && aligned16(x) && aligned16(out);
-  return wide ? run_spmm_vec<4>(a, rowptr, rows, nnz, ws, st) : run_spmm_vec<1>(a, rowptr, rows, nnz, ws, st);
+  const WeightedSumOp op;
+  return wide ? run_spmm_vec<4>(a, op, rowptr, rows, nnz, ws, st) : run_spmm_vec<1>(a, op, rowptr, rows, nnz, ws, st);
 }
 
 hipError_t launch_sddmm_heads(const int* rowptr, const int* col, int m, int nnz, int H, int k, const float* a, const float* b,
                               float* out, void* ws, hipStream_t st) {
-  const bool fast = H <= kMaxFastHeads && (H & (H - 1)) == 0;
-  int hshift = -1;
-  if (fast)
-    for (hshift = 0; (1 << hshift) < H; ++hshift) {}
-  const SddmmHeadsArgs s{col, a, b, out, H, k / H, k, hshift, 0, 0};
+  const SddmmHeadsArgs s{col, a, b, out, H, k / H, k, fast_hshift(H), 0, 0};
   const bool wide = (k / H) % 4 == 0 && aligned16(a) && aligned16(b);
-  return wide ? run_sddmm<4>(s, rowptr, m, nnz, ws, st) : run_sddmm<1>(s, rowptr, m, nnz, ws, st);
+  const DotOp op;
+  return wide ? run_sddmm<4>(s, op, rowptr, m, nnz, ws, st) : run_sddmm<1>(s, op, rowptr, m, nnz, ws, st);
+}
+
+size_t gatv2_workspace_bytes(int nnz, int k) {
+  return 16 + 2 * 8 * (size_t)k * (size_t)(((long long)nnz + kGChunk - 1) / kGChunk);
+}
+
+hipError_t launch_gatv2_scores(const int* rowptr, const int* col, int m, int nnz, int H, int k, const float* h_dst, const float* h_src,
+                               const float* att, float slope, float* out, void* ws, hipStream_t st) {
+  const SddmmHeadsArgs s{col, h_dst, h_src, out, H, k / H, k, fast_hshift(H), 0, 0};
+  const bool wide = (k / H) % 4 == 0 && aligned16(h_dst) && aligned16(h_src) && aligned16(att);
+  const Gatv2ScoreOp op{att, slope};
+  return wide ? run_sddmm<4>(s, op, rowptr, m, nnz, ws, st) : run_sddmm<1>(s, op, rowptr, m, nnz, ws, st);
+}
+
+hipError_t launch_gatv2_scores_backward(const int* rowptr, const int* idx, const int* perm, int rows, int nnz, int H, int k,
+                                        const float* own, const float* other, const float* att, float slope, const float* g,
+                                        float* grad_own, float* act_sums, void* ws, hipStream_t st) {
+  const HeadsSpmmArgs a{idx, perm, g, other, grad_own, H, k / H, k};
+  const bool wide = (k / H) % 4 == 0 && aligned16(own) && aligned16(other) && aligned16(att) && aligned16(grad_own) &&
+                    aligned16(act_sums);
+  if (act_sums) {
+    const Gatv2BackwardOp<true> op{own, att, act_sums, slope};
+    return wide ? run_spmm_vec<4>(a, op, rowptr, rows, nnz, ws, st) : run_spmm_vec<1>(a, op, rowptr, rows, nnz, ws, st);
+  }
+  const Gatv2BackwardOp<false> op{own, att, nullptr, slope};
+  return wide ? run_spmm_vec<4>(a, op, rowptr, rows, nnz, ws, st) : run_spmm_vec<1>(a, op, rowptr, rows, nnz, ws, st);
 }
 
 }  // namespace gcn

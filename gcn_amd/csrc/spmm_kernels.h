@@ -213,6 +213,15 @@ hipError_t launch_spmm_heads(const int* rowptr, const int* idx, const int* perm,
                              const float* x, float* out, void* ws, hipStream_t st);
 hipError_t launch_sddmm_heads(const int* rowptr, const int* col, int m, int nnz, int H, int k, const float* a, const float* b,
                               float* out, void* ws, hipStream_t st);
+// the GATv2 score s[e, h] = sum_j att[h, j] leaky_relu(h_dst[row(e), hF + j] + h_src[col[e], hF + j]) on the SDDMM's walk (ws:
+// kHeadsSddmmWsBytes will do) and its backward on one side on the SpMM's walk: grad_own [rows, k] and, where act_sums is not
+// null, act_sums [rows, k] whose column sums are grad_att.  ws: gatv2_workspace_bytes (a flag, the chunk partials of two sums).
+size_t gatv2_workspace_bytes(int nnz, int k);
+hipError_t launch_gatv2_scores(const int* rowptr, const int* col, int m, int nnz, int H, int k, const float* h_dst, const float* h_src,
+                               const float* att, float slope, float* out, void* ws, hipStream_t st);
+hipError_t launch_gatv2_scores_backward(const int* rowptr, const int* idx, const int* perm, int rows, int nnz, int H, int k,
+                                        const float* own, const float* other, const float* att, float slope, const float* g,
+                                        float* grad_own, float* act_sums, void* ws, hipStream_t st);
 
 // sample.hip — uniform neighbour sampling without replacement from the rows of seeds[n_seeds], a pure function of (seed,
 // offset, entry index) (plan-free, no global atomics: see the file's header and include/gcn_spmm.h).  fanout < 0: every entry.

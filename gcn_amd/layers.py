@@ -25,7 +25,7 @@ from torch.nn.parameter import Parameter
 
 from . import preprocess, reorder, timers
 from .aggregate import aggregate
-from .attention import gat_edge_softmax, spmm_heads
+from .attention import edge_softmax, gat_edge_softmax, gatv2_scores, spmm_heads
 from .spgemm import HypergraphLaplacian
 from .spmm import CsrAdjacency, _SpmmFunction, dropout_rows, gather_rows, spmm
 
@@ -202,6 +202,78 @@ class GraphAttention(nn.Module):
     def __repr__(self):
         return (f"GraphAttention ({self.in_features} -> {self.out_features}, heads={self.heads}, "
                 f"{'concat' if self.concat else 'mean'}{', head-batched' if self.head_batched else ''})")
+
+
+class GraphAttentionV2(nn.Module):
+    """GATv2 layer (Brody et al. 2022; PyG's ``GATv2Conv``) on the native kernels, all heads in one pass:
+
+        h_src = x_src·weight_src,  h_dst = x_dst·weight_dst                        ([n, heads·out_features], [m, ...])
+        s[e, k] = sum_j att[k, j] · leaky_relu(h_dst[row(e), kF + j] + h_src[col(e), kF + j], negative_slope)
+        p = edge_softmax(adj, s)                                                    (per head, over each row's entries)
+        out = spmm_heads(adj, h_src, p)
+
+    and the heads are concatenated (``concat=True``) or averaged, then the bias is added.  The nonlinearity sits between the
+    sum of the two node vectors and the dot with ``att`` — the "dynamic" attention GAT's score cannot express.  The score
+    kernel (``gatv2_scores``, gcn_amd/csrc/multihead.hip) gathers the rows per entry, forward and backward; nothing wider
+    than [nnz, heads] is stored per entry.
+
+    ``forward(input, adj)`` takes one feature matrix over a square adjacency; ``forward((x_src, x_dst), adj)`` takes the two
+    sides of a rectangular one (a sampled block: ``adj`` is m x n, x_src has n rows, x_dst m).  Any CsrAdjacency: no plan is
+    used and its values are ignored.
+
+    Parameters: ``weight_src`` [in_features, heads·out_features]; ``weight_dst`` of the same shape, absent with
+    ``share_weights=True`` (the one weight then serves both sides); ``att`` [heads, out_features]; ``bias``
+    [heads·out_features] (concat) or [out_features] (mean), zeros.  Glorot uniform, like GraphAttention.  Under a bf16
+    autocast region the two matmuls run in bf16; everything after them runs in fp32 with autocast off."""
+
+    def __init__(self, in_features, out_features, heads=1, concat=True, negative_slope=0.2, with_bias=True, share_weights=False):
+        super().__init__()
+        self.in_features, self.out_features, self.heads = int(in_features), int(out_features), int(heads)
+        self.concat, self.negative_slope = bool(concat), float(negative_slope)
+        self.share_weights = bool(share_weights)
+        if self.heads < 1:
+            raise ValueError("heads must be at least 1")
+        self.weight_src = Parameter(torch.empty(self.in_features, self.heads * self.out_features))
+        if self.share_weights:
+            self.register_parameter("weight_dst", None)
+        else:
+            self.weight_dst = Parameter(torch.empty(self.in_features, self.heads * self.out_features))
+        self.att = Parameter(torch.empty(self.heads, self.out_features))
+        if with_bias:
+            self.bias = Parameter(torch.empty(self.heads * self.out_features if self.concat else self.out_features))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.xavier_uniform_(self.weight_src)
+        if self.weight_dst is not None:
+            nn.init.xavier_uniform_(self.weight_dst)
+        nn.init.xavier_uniform_(self.att)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def forward(self, input, adj):
+        x_src, x_dst = input if isinstance(input, (tuple, list)) else (input, input)
+        if x_src.shape[0] != adj.n or x_dst.shape[0] != adj.m:
+            raise ValueError(f"GraphAttentionV2: adjacency {adj.m}x{adj.n} needs x_src with {adj.n} rows and x_dst with {adj.m}, "
+                             f"got {tuple(x_src.shape)} and {tuple(x_dst.shape)}")
+        h_src = torch.mm(x_src, self.weight_src)        # (bf16 under a bf16 autocast region, like any matmul)
+        if x_dst is x_src and self.weight_dst is None:
+            h_dst = h_src
+        else:
+            h_dst = torch.mm(x_dst, self.weight_src if self.weight_dst is None else self.weight_dst)
+        with torch.autocast("cuda", enabled=False):
+            h_src, h_dst = h_src.float(), h_dst.float()
+            s = gatv2_scores(adj, h_dst, h_src, self.att.float(), self.negative_slope)
+            out = spmm_heads(adj, h_src, edge_softmax(adj, s))
+            if not self.concat and self.heads > 1:
+                out = out.view(out.shape[0], self.heads, self.out_features).mean(1)
+            return out + self.bias.float() if self.bias is not None else out
+
+    def __repr__(self):
+        return (f"GraphAttentionV2 ({self.in_features} -> {self.out_features}, heads={self.heads}, "
+                f"{'concat' if self.concat else 'mean'}{', shared weights' if self.share_weights else ''})")
 
 
 class SAGEConv(nn.Module):

@@ -349,6 +349,33 @@ int gcn_spmm_heads_csr_f32(const int32_t* rowptr_dev, const int32_t* idx_dev, co
 int gcn_sddmm_heads_csr_f32(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz, int32_t heads, int32_t k,
                             const float* a, const float* b, float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* GATv2 attention scores (multihead.hip), in the layouts and under the argument rules of the head-batched family above:
+ *   out[e, h] = sum over j < F of att[h, j] * leaky_relu(h_dst[row(e), hF + j] + h_src[col[e], hF + j], negative_slope)
+ * h_dst [m, k], h_src with a row for every value of col, att [H, F] row-major (its flat index is the node column), out
+ * [nnz, H].  Per element t = h_dst + h_src rounded to fp32, then t > 0 ? t : negative_slope * t, then one fma with att; at
+ * t == 0 the value is negative_slope * 0 and the derivative below is the slope.  The summation order of an (entry, head)
+ * is the one of gcn_sddmm_heads_csr_f32: a function of F and of the aligned / element form only (the aligned form: h_dst,
+ * h_src and att 16-byte aligned and F % 4 == 0).  A NaN in t makes that (entry, head) NaN and no other.
+ * ws: at least the bytes gcn_gatv2_ws_bytes reports — 16 + 2 * 8 * k * ceil(nnz / 4096), the flag and the long rows' chunk
+ * partials of the backward's two sums — 16-byte aligned; the three calls on a pattern and its transpose share it. */
+int gcn_gatv2_ws_bytes(int32_t m, int32_t nnz, int32_t heads, int32_t k, size_t* bytes);
+int gcn_gatv2_scores_csr_f32(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz, int32_t heads, int32_t k,
+                             const float* h_dst, const float* h_src, const float* att, float negative_slope, float* out,
+                             void* ws, size_t ws_bytes, void* stream);
+/* The backward on one side, a row walk like gcn_spmm_heads_csr_f32 over (rowptr, idx, perm).  With
+ * t = own[r, j] + other[idx[e], j] and D = t > 0 ? 1 : negative_slope, over the entries e of row r and h the head of j:
+ *   grad_own[r, j] = att[j] * sum of g[perm ? perm[e] : e, h] * D                  (multiplied once, after the sum)
+ *   act_sums[r, j] =          sum of g[perm ? perm[e] : e, h] * (t * D)            (where act_sums is not NULL)
+ * grad_h_dst and act_sums: own = h_dst, other = h_src, idx = col, perm = NULL; grad_att[h, j] is the sum over r of
+ * act_sums[r, hF + j].  grad_h_src: the transposed pattern (rowptr = trowptr, idx = the source row of each entry, perm = the
+ * entry's index in the forward's order), own = h_src, other = h_dst, act_sums = NULL.  g [nnz, H]; own, grad_own and
+ * act_sums [rows, k]; an empty row gets zeros.  Fixed order: a sum is carried in SLOTS interleaved fma chains merged by an xor
+ * butterfly, rows of more than 4096 entries as chunk partials merged in chunk order.  A NaN in t or g stays in its (row, j). */
+int gcn_gatv2_scores_backward_csr_f32(const int32_t* rowptr_dev, const int32_t* idx_dev, const int32_t* perm_dev, int32_t rows,
+                                      int32_t nnz, int32_t heads, int32_t k, const float* own, const float* other,
+                                      const float* att, float negative_slope, const float* g, float* grad_own, float* act_sums,
+                                      void* ws, size_t ws_bytes, void* stream);
+
 /* Uniform neighbour sampling without replacement from the rows of a CSR matrix (GraphSAGE's mini-batch sampler).  Plan-free
  * like the aggregation family: the caller's CSR, one memset node and kernels, no allocation, no host read of device data, no
  * global atomics; every output element has one writer, so a call gives the same bits every time.  The stored values are
