@@ -98,6 +98,7 @@ class _SelectFunction(torch.autograd.Function):
         return out, arg
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g, _g_arg):
         if not ctx.needs_input_grad[1]:
             return None, None, None

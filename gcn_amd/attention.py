@@ -160,6 +160,7 @@ class _EdgeSoftmaxFunction(torch.autograd.Function):
         return p
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         (p,) = ctx.saved_tensors
         adj = ctx.adj
@@ -214,6 +215,7 @@ class _GatEdgeSoftmaxFunction(torch.autograd.Function):
         return p
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         ad, asrc, p = ctx.saved_tensors
         adj = ctx.adj
@@ -303,6 +305,7 @@ class _SpmmHeadsFunction(torch.autograd.Function):
         return out
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         xd, v = ctx.saved_tensors
         adj = ctx.adj
@@ -328,6 +331,7 @@ class _SddmmHeadsFunction(torch.autograd.Function):
         return _sddmm_heads_raw(adj, ad, bd, heads)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         ad, bd = ctx.saved_tensors
         adj = ctx.adj
@@ -432,6 +436,7 @@ class _Gatv2ScoresFunction(torch.autograd.Function):
         return out
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         hd, hs, a = ctx.saved_tensors
         adj = ctx.adj

@@ -27,7 +27,7 @@ from . import preprocess, reorder, timers
 from .aggregate import aggregate
 from .attention import edge_softmax, gat_edge_softmax, gatv2_scores, spmm_heads
 from .spgemm import HypergraphLaplacian
-from .spmm import CsrAdjacency, _SpmmFunction, dropout_rows, gather_rows, spmm
+from .spmm import CsrAdjacency, _SpmmFunction, _check_values_version, _values_version, dropout_rows, gather_rows, spmm
 
 
 def _spmm_operand(x):
@@ -47,10 +47,12 @@ class _FusedSpmmBiasRelu(torch.autograd.Function):
     def forward(ctx, adj, x, bias, relu, dropout=None):
         out = adj.matmul_raw(x, bias=bias, relu=relu, dropout=dropout)
         ctx.adj, ctx.relu, ctx.has_bias, ctx.dropout = adj, relu, bias is not None, dropout
+        ctx.values_version = _values_version(adj)
         ctx.save_for_backward(out)
         return out
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         (out,) = ctx.saved_tensors
         if ctx.dropout is not None and ctx.dropout[0] > 0:
@@ -58,6 +60,8 @@ class _FusedSpmmBiasRelu(torch.autograd.Function):
         if ctx.relu:
             g = g * (out > 0)                          # (dropped elements are 0 in `out`, and their gradient is 0 already)
         g = g.contiguous()
+        if ctx.needs_input_grad[1]:
+            _check_values_version(ctx.adj, ctx.values_version, "fused SpMM epilogue")
         gx = ctx.adj.transpose().matmul_raw(g) if ctx.needs_input_grad[1] else None
         gb = g.float().sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None     # (fp32 bias, bf16 activations too)
         return None, gx, gb, None, None

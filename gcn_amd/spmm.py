@@ -68,6 +68,7 @@ class CsrAdjacency:
         self._transpose = None
         self._tperm = None           # mutable transpose: its values are self.val[_tperm]
         self._tstale = False         # ... once refreshed: update_values has changed self.val since
+        self.values_version = 0      # counts update_values calls: a backward that reads the values checks it has not moved
         self.device = self.val.device
 
     # -- constructors ---------------------------------------------------------
@@ -338,7 +339,8 @@ class CsrAdjacency:
         """New values (nnz entries, CSR order) for a mutable adjacency: re-laid into the plan in place
         (gcn_spmm_plan_update_values: no allocation, no synchronisation — legal inside a graph capture) and copied
         into self.val (the adjacency's own copy: `val` itself is only read).  The transpose, if one exists, is refreshed
-        from them at its next use.  GcnAmdError on an adjacency not made mutable (nothing changes then)."""
+        from them at its next use.  GcnAmdError on an adjacency not made mutable (nothing changes then).
+        Increments ``values_version``: the backward of a plain ``spmm(adj, x)`` whose forward saw other values raises."""
         v = self._device_values(val, "update_values")
         with torch.cuda.device(self.device):
             st = _lib.load().gcn_spmm_plan_update_values(self.plan, _ptr(v), _stream_ptr(self.device))
@@ -346,6 +348,7 @@ class CsrAdjacency:
         if v.data_ptr() != self.val.data_ptr():
             self.val.copy_(v)
         self._tstale = self._transpose is not None
+        self.values_version += 1
         return self
 
     def sddmm(self, A, B, out=None):
@@ -475,6 +478,19 @@ class CsrAdjacency:
         return out
 
 
+def _values_version(adj):
+    """what a forward that reads adj's own values records: the version of a mutable adjacency's values, None for fixed ones"""
+    return adj.values_version if adj.mutable_values else None
+
+
+def _check_values_version(adj, seen, what):
+    """host-side, no copy and no synchronisation (under a graph capture it runs at capture time, like the rest of a
+    backward's host code): the backward would multiply by Âᵀ of values the forward never saw"""
+    if seen is not None and adj.values_version != seen:
+        raise RuntimeError(f"{what}: update_values changed the adjacency's values between this forward and its backward; "
+                           "the gradient of the forward's values is gone (use spmm(adj, x, values=...), which keeps them)")
+
+
 def _destroy_plan(handle):
     try:
         _lib.load().gcn_spmm_plan_destroy(handle)
@@ -488,13 +504,15 @@ class _SpmmFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, adj, dense):
-        ctx.adj = adj
+        ctx.adj, ctx.values_version = adj, _values_version(adj)
         return adj.matmul_raw(dense)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         if not ctx.needs_input_grad[1]:                # (a constant operand, e.g. the input features: no Âᵀ·grad to compute)
             return None, None
+        _check_values_version(ctx.adj, ctx.values_version, "spmm")
         return None, ctx.adj.transpose().matmul_raw(grad_out.contiguous())
 
 
@@ -510,6 +528,7 @@ class _SpmmValuesFunction(torch.autograd.Function):
         return adj.matmul_raw(dense)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         dense, values = ctx.saved_tensors
         adj = ctx.adj
@@ -528,7 +547,8 @@ def spmm(adj, dense, values=None):
     (COO/CSR) fp32 tensor on the GPU (converted and cached per tensor object).
     values: nnz fp32 values in adj's CSR order that replace adj's own (and may require grad): adj must have been made
     with mutable_values=True; they are re-laid into its plan at every call, so values changed in place between two
-    calls (an optimizer step) are picked up."""
+    calls (an optimizer step) are picked up.
+    Without `values`, the backward multiplies by the adjacency's own Âᵀ: RuntimeError if update_values ran since the forward."""
     if not isinstance(adj, CsrAdjacency):
         adj = _cached_csr(adj)
     if values is None:
@@ -606,7 +626,9 @@ class _SparseMmGrad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, b, adj):
-        vals = a._values().detach()
+        # a copy: the values of a sparse tensor share the storage of the tensor it was made from but not its version
+        # counter, so autograd's check would miss an in-place change of that tensor between forward and backward
+        vals = a._values().detach().clone()
         ctx.adj = adj
         ctx.a_indices, ctx.a_shape = a._indices(), a.shape
         ctx.save_for_backward(b, vals)
@@ -614,6 +636,7 @@ class _SparseMmGrad(torch.autograd.Function):
         return adj.matmul_raw(b)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         b, vals = ctx.saved_tensors
         adj = ctx.adj

@@ -334,6 +334,39 @@ def test_sparse_mm_routing_leaves_values_unchanged():
     assert (w1.grad.double() - gref).abs().max().item() <= 1e-5 * max(1.0, gref.abs().max().item())
 
 
+def test_sparse_mm_backward_keeps_the_forwards_values_when_their_tensor_changes_in_place():
+    """the COO tensor's values share the storage of the tensor it was made from, but not its version counter: the backward
+    must either refuse or give the gradient of the values the forward saw (tests/test_autograd_forms_gpu.py, form 6)"""
+    rp, ci, va, m, n = sddmm_graph("rect")
+    rows = np.repeat(np.arange(m), np.diff(rp))
+    key = rows.astype(np.int64) * n + ci
+    keep = np.concatenate([[True], key[1:] != key[:-1]])
+    idx = torch.tensor(np.stack([rows[keep], ci[keep]]), device=DEV)
+    rng = np.random.default_rng(9)
+    w0 = _t(rng.integers(1, 5, int(keep.sum())).astype(np.float32))
+    x0 = _t(rng.integers(-8, 9, (n, 8)).astype(np.float32))
+    g = _t(rng.integers(-8, 9, (m, 8)).astype(np.float32))
+
+    def run(change):
+        w, x = w0.clone().requires_grad_(True), x0.clone().requires_grad_(True)
+        y = torch.sparse.mm(torch.sparse_coo_tensor(idx, w, (m, n), is_coalesced=True), x)
+        if change:
+            with torch.no_grad():
+                w.neg_()
+        try:
+            y.backward(g)
+        except RuntimeError:
+            return None
+        return x.grad, w.grad
+
+    try:
+        gcn_amd.install(sparse_grad=True)
+        want, got = run(False), run(True)
+    finally:
+        gcn_amd.uninstall()
+    assert got is None or (torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]))
+
+
 @pytest.mark.parametrize("slices", [0, 4])
 def test_plain_backward_after_update_values_uses_new_values(slices):
     """update_values(w2), then the values-free spmm: x.grad = Â(w2)ᵀ·g, against fp64 — also on
