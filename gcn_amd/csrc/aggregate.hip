@@ -17,14 +17,8 @@
 // xor-shuffles.  Operands that are not 16-byte aligned, or k not a multiple of the vector, take the same kernels with one
 // element per lane (16 columns per tile).
 //
-// Dispatch by row length happens in the kernel (the host never reads a row length):
-//   * a wave owns 8 consecutive rows and takes them one after the other; 8 empty rows cost one row-pointer load and the
-//     stores of their zeros;
-//   * a row of more than kAggChunk entries is left alone and a flag in the workspace is raised.  The chunk kernels (a
-//     fixed grid of waves walking chunks of kAggChunk entries; they return at once while the flag is down) find the at most
-//     two long rows that meet a chunk — the rows of its first and last entry, a 64-ary search of rowptr — and write one
-//     partial state per (chunk, row, column) to the workspace; the finish kernel merges a row's partials in chunk order
-//     (the wave whose chunk holds the row's first entry does) and writes the row.  A hub row is spread over the chip.
+// Dispatch by row length happens in the kernels (the host never reads a row length) and is gather_rows.h's: 8 rows a
+// wave, rows of more than kAggChunk entries by chunk partials (here a (value, entry) pair) merged in chunk order.
 //
 // Selection rule (numpy's argmax / argmin): the first entry in CSR order among equals, -0.0 == +0.0; a NaN beats every
 // number and the first NaN wins; +-inf are ordinary values.  No arithmetic touches a value: the bits stored are the
@@ -34,16 +28,12 @@
 #include <climits>
 #include <cmath>
 
-#include "long_chunks.h"
+#include "gather_rows.h"
 #include "spmm_kernels.h"
 
 namespace gcn {
 namespace {
 
-constexpr int kRowsPerWave = 8;
-constexpr int kChunk = kAggChunk;                      // entries per chunk of the long-row kernels
-constexpr int kLongRow = kAggChunk;                    // rows longer than this are split over waves (>= kChunk: long_segment)
-constexpr int kLongWaves = 8192;                       // waves of the long-row kernels (they loop over the chunks)
 constexpr int kNone = INT_MAX;                         // "no entry yet" (a stored entry index is below nnz <= INT_MAX)
 
 using bf16_t = unsigned short;
@@ -61,17 +51,9 @@ __device__ __forceinline__ void put_rounded(bf16_t* p, float v) {
   *p = (bf16_t)(u >> 16);
 }
 
-// VEC consecutive elements at p as floats: one 16-byte load (fp32 x 4, bf16 x 8) or one element
-template <int VEC>
-__device__ __forceinline__ void load_row(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-    static_assert(VEC == 1);
-    v[0] = p[0];
-  }
-}
+// VEC consecutive elements at p as floats: one 16-byte load (fp32 x 4: gather_rows.h, bf16 x 8) or one element
+using gcn::load_row;                                   // (the overloads below would hide them)
+using gcn::store_row;
 template <int VEC>
 __device__ __forceinline__ void load_row(const bf16_t* p, float (&v)[VEC]) {
   if constexpr (VEC == 8) {
@@ -102,15 +84,6 @@ __device__ __forceinline__ void load_ints(const int* p, int (&v)[VEC]) {
 
 // VEC consecutive elements at p (a 16-byte boundary when VEC > 1) from floats: exact (the floats came from T) or rounded
 template <int VEC, bool ROUND>
-__device__ __forceinline__ void store_row(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    static_assert(VEC == 1);
-    p[0] = v[0];
-  }
-}
-template <int VEC, bool ROUND>
 __device__ __forceinline__ void store_row(bf16_t* p, const float (&v)[VEC]) {
   bf16_t h[VEC];
 #pragma unroll
@@ -140,7 +113,7 @@ struct State {
   float v[VEC];                                        // the best value so far / the running sum
   int e[VEC];                                          // its entry index, kNone before the first / unused
 };
-struct Partial { float v; int e; };                    // one column of a State in the workspace
+struct Pair { float v; int e; };                       // one column of a State in the workspace
 
 // is (av, ae) the better candidate than (bv, be)?  A total order (kNone, "no entry", below everything): usable in any
 // merge order.
@@ -196,7 +169,7 @@ struct SelectOp {                                      // the forward
       s.e[i] = take ? o.e[i] : s.e[i];
     }
   }
-  static __device__ void merge_next(Partial& s, Partial o) {
+  static __device__ void merge_next(Pair& s, Pair o) {
     if (better<MAX>(o.v, o.e, s.v, s.e)) s = o;
   }
   __device__ void store(int r, int j, const State<VEC>& s) const {    // columns j .. j + VEC of row r
@@ -211,7 +184,7 @@ struct SelectOp {                                      // the forward
     store_row<VEC, false>(out + at, v);
     store_ints<VEC>(arg + at, e);
   }
-  __device__ void store_one(int r, int j, Partial p) const {          // (kNone: the row has no entry)
+  __device__ void store_one(int r, int j, int, Pair p) const {        // (kNone: the row has no entry)
     const size_t at = (size_t)r * k + j;
     put_exact(out + at, p.e == kNone ? 0.f : p.v);
     arg[at] = p.e == kNone ? -1 : p.e;
@@ -251,20 +224,17 @@ struct ScatterOp {                                     // the backward, on the t
 #pragma unroll
     for (int i = 0; i < VEC; ++i) s.v[i] += o.v[i];
   }
-  static __device__ void merge_next(Partial& s, Partial o) { s.v += o.v; }
+  static __device__ void merge_next(Pair& s, Pair o) { s.v += o.v; }
   __device__ void store(int c, int j, const State<VEC>& s) const { store_row<VEC, true>(gx + (size_t)c * k + j, s.v); }
-  __device__ void store_one(int c, int j, Partial p) const { put_rounded(gx + (size_t)c * k + j, p.v); }
+  __device__ void store_one(int c, int j, int, Pair p) const { put_rounded(gx + (size_t)c * k + j, p.v); }
 };
-
-template <class Op>
-constexpr int tile_width() { return 16 * Op::VEC; }   // columns per wave: 16 lanes x VEC
 
 // ---- entries [b, b + n) on one wave: the lane's columns are j .. j + VEC (jok: they exist) ----------------------------------
 template <class Op>
 __device__ __forceinline__ void walk(const Op& op, int b, int n, int lane, int j, bool jok, State<Op::VEC>& s) {
   const int slot = lane >> 4;
   const int jl = jok ? j : 0;                          // (lanes past k gather column 0 and fold nothing)
-  for (int off = 0; off < n; off += 64) {              // (n <= kChunk: no overflow)
+  for (int off = 0; off < n; off += 64) {              // (n <= kAggChunk: no overflow)
     const int cnt = n - off < 64 ? n - off : 64;
     const typename Op::Index mine = op.index(b + (lane < cnt ? off + lane : 0));   // (past the end: the first entry again)
     for (int i0 = 0; i0 < cnt; i0 += 16) {
@@ -299,95 +269,27 @@ __device__ __forceinline__ void merge_slots(State<Op::VEC>& s) {
   }
 }
 
+// what gather_rows.h asks of an operation: 16 lanes a slot, one state per column, nothing fixed per lane
 template <class Op>
-__global__ void __launch_bounds__(256) agg_rows_kernel(Op op, const int* __restrict__ rowptr, int rows, int* __restrict__ long_flag) {
-  const int lane = threadIdx.x & 63;
-  const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
-  if (wave * kRowsPerWave >= rows) return;             // (whole waves leave: the shuffles below see full waves)
-  const int r0 = (int)wave * kRowsPerWave;
-  const int ri = r0 + lane < rows ? r0 + lane : rows;
-  const int rp = rowptr[ri];                           // lanes 0..8: the 9 row bounds (later lanes repeat rowptr[rows])
-  const int j = (blockIdx.y * 16 + (lane & 15)) * Op::VEC;
-  const bool jok = j < op.k;
-  for (int q = 0; q < kRowsPerWave && r0 + q < rows; ++q) {
-    const int b = __shfl(rp, q), e = __shfl(rp, q + 1);
-    const int n = e - b;
-    if (n > kLongRow) {
-      if (lane == 0) *long_flag = 1;                   // (every writer writes the same word)
-      continue;
-    }
-    State<Op::VEC> s;
+struct RowsOp : Op {
+  static constexpr int LPS = 16, NS = 1;
+  using Acc = State<Op::VEC>;
+  using Partial = Pair;
+  struct Lane {};
+  struct Row {};
+  __device__ Lane lane_ctx(int, bool) const { return {}; }
+  __device__ void reduce(int, int b, int n, int lane, int j, bool jok, Lane, Row&, Acc& s) const {
     Op::init(s);
-    walk(op, b, n, lane, j, jok, s);
+    walk<Op>(*this, b, n, lane, j, jok, s);
     merge_slots<Op>(s);
-    if (lane < 16 && jok) op.store(r0 + q, j, s);
   }
-}
-
-// ---- long rows (find_row, Segment and long_segment: long_chunks.h) --------------------------------------------------------
-template <class Op>
-__global__ void __launch_bounds__(256) agg_long_partial_kernel(Op op, const int* __restrict__ rowptr, int rows, int nnz, int nchunks,
-                                                               const int* __restrict__ long_flag, Partial* __restrict__ part) {
-  if (*long_flag == 0) return;
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = gridDim.x * 4;
-  const int j = (blockIdx.y * 16 + (lane & 15)) * Op::VEC;
-  const bool jok = j < op.k;
-  for_long_segments<kChunk, kLongRow>(rowptr, rows, nnz, nchunks, wave, nwaves, lane, [&](int c, int slot, const Segment& sg) {
-    State<Op::VEC> s;
-    Op::init(s);
-    walk(op, sg.sb, sg.se - sg.sb, lane, j, jok, s);
-    merge_slots<Op>(s);
-    if (lane < 16 && jok) {
-      Partial* p = part + (2 * (size_t)c + slot) * op.k + j;
-#pragma unroll
-      for (int i = 0; i < Op::VEC; ++i) p[i] = Partial{s.v[i], s.e[i]};
-    }
-  });
-}
-
-template <class Op>
-__global__ void __launch_bounds__(256) agg_long_finish_kernel(Op op, const int* __restrict__ rowptr, int rows, int nnz, int nchunks,
-                                                              const int* __restrict__ long_flag, const Partial* __restrict__ part) {
-  if (*long_flag == 0) return;
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = gridDim.x * 4;
-  const int j0 = blockIdx.y * tile_width<Op>();
-  const int j1 = j0 + tile_width<Op>() < op.k ? j0 + tile_width<Op>() : op.k;
-  for_long_segments<kChunk, kLongRow>(rowptr, rows, nnz, nchunks, wave, nwaves, lane, [&](int c, int slot, const Segment& sg) {
-    // the row's partials: chunks c_first..c_last, the first in slot 1 unless the row starts on the chunk's first entry.
-    // One writer per row: the wave whose chunk holds the row's first entry merges them, in chunk order, a column per lane.
-    const int c_first = sg.rb / kChunk, c_last = (sg.re - 1) / kChunk;
-    if (c != c_first) return;
-    const int first_slot = sg.rb > c_first * kChunk ? 1 : 0;
-    for (int j = j0 + lane; j < j1; j += 64) {
-      Partial acc = part[(2 * (size_t)c_first + first_slot) * op.k + j];
-      for (int cc = c_first + 1; cc <= c_last; ++cc) Op::merge_next(acc, part[2 * (size_t)cc * op.k + j]);
-      op.store_one(sg.r, j, acc);
-    }
-  });
-}
+  static __device__ Pair partial(const Acc& s, int, int v) { return Pair{s.v[v], s.e[v]}; }
+};
 
 template <class Op>
 hipError_t run(const Op& op, const int* rowptr, int rows, int nnz, void* ws, hipStream_t st) {
-  int* flag = static_cast<int*>(ws);
-  Partial* part = reinterpret_cast<Partial*>(static_cast<char*>(ws) + 16);
-  const unsigned tiles = (unsigned)((op.k + tile_width<Op>() - 1) / tile_width<Op>());
-  if (hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), st); e != hipSuccess) return e;
-  const long long waves = ((long long)rows + kRowsPerWave - 1) / kRowsPerWave;
-  agg_rows_kernel<Op><<<dim3((unsigned)((waves + 3) / 4), tiles), 256, 0, st>>>(op, rowptr, rows, flag);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  if (nnz <= kLongRow) return hipSuccess;              // (no row can be long)
-  const int nchunks = (int)(((long long)nnz + kChunk - 1) / kChunk);
-  const int nw = nchunks < kLongWaves ? nchunks : kLongWaves;
-  const dim3 grid((unsigned)((nw + 3) / 4), tiles);
-  agg_long_partial_kernel<Op><<<grid, 256, 0, st>>>(op, rowptr, rows, nnz, nchunks, flag, part);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  agg_long_finish_kernel<Op><<<grid, 256, 0, st>>>(op, rowptr, rows, nnz, nchunks, flag, part);
-  return hipGetLastError();
+  return run_gather(RowsOp<Op>{op}, rowptr, rows, nnz, ws, st);
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <class T, int VEC>
 hipError_t run_select(const int* rowptr, const int* col, int m, int nnz, const T* x, int k, int op, T* out, int* arg, void* ws,
@@ -399,7 +301,7 @@ hipError_t run_select(const int* rowptr, const int* col, int m, int nnz, const T
 }  // namespace
 
 size_t aggregate_workspace_bytes(int nnz, int k) {
-  return 16 + 16 * (size_t)k * (size_t)(((long long)nnz + kChunk - 1) / kChunk);
+  return 16 + 16 * (size_t)k * (size_t)(((long long)nnz + kGatherChunk - 1) / kGatherChunk);
 }
 
 // the 16-byte paths need every gathered or stored row to start on a 16-byte boundary: the base pointers and the row

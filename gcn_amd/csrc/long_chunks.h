@@ -2,8 +2,9 @@
 // at most two long rows that meet a chunk of consecutive entries, and the walk over the chunks that the wave-per-chunk
 // kernels make (edge_softmax.hip's block-per-chunk kernels write the same loop out: through the helper one of them comes
 // out with other registers and another occupancy).  The partials and what a kernel does with a segment are
-// each unit's own.  Device code only; the chunk length and the long-row threshold are the caller's (CHUNK and LONG_ROW,
-// at least the chunk length).
+// each unit's own (gather_rows.h: the engine of aggregate.hip and multihead.hip).  Also the other half of the dispatch by
+// row length, the rows a wave takes whole (for_wave_rows).  Device code only; the chunk length and the long-row threshold
+// are the caller's (CHUNK and LONG_ROW, at least the chunk length).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,6 +53,28 @@ __device__ __forceinline__ void for_long_segments(const int* __restrict__ rowptr
       Segment s;
       if (long_segment<LONG_ROW>(rowptr, slot, rh, rt, e0, e1, s)) f(c, slot, s);
     }
+  }
+}
+
+// the short rows: the wave of a 256-thread block owns ROWS (<= 63) consecutive rows and takes them one after the other,
+// f(r, b, n) for row r with the entries [b, b + n).  One load brings the ROWS + 1 row bounds (ROWS empty rows cost that
+// load and whatever f stores for them); a row of more than LONG_ROW entries is left to the chunk kernels and the flag is
+// raised.  f is wave-uniform: waves past the last row leave whole, so the shuffles here and in f see full waves.
+template <int ROWS, int LONG_ROW, class F>
+__device__ __forceinline__ void for_wave_rows(const int* __restrict__ rowptr, int rows, int lane, int* __restrict__ long_flag, F f) {
+  const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+  if (wave * ROWS >= rows) return;
+  const int r0 = (int)wave * ROWS;
+  const int ri = r0 + lane < rows ? r0 + lane : rows;
+  const int rp = rowptr[ri];                           // lanes 0..ROWS: the row bounds (later lanes repeat rowptr[rows])
+  for (int q = 0; q < ROWS && r0 + q < rows; ++q) {
+    const int b = __shfl(rp, q), e = __shfl(rp, q + 1);
+    const int n = e - b;
+    if (n > LONG_ROW) {
+      if (lane == 0) *long_flag = 1;                   // (every writer writes the same word)
+      continue;
+    }
+    f(r0 + q, b, n);
   }
 }
 

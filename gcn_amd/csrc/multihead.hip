@@ -12,9 +12,9 @@
 //    heads and a gather brings the whole k-wide row; wider k tiles 256 columns over blockIdx.y.  VEC = 4 (one 16-byte load;
 //    F % 4 == 0 keeps a lane's four columns in one head) or 1 (an operand that is not 16-byte aligned, or F % 4 != 0).  The
 //    wave loads 64 indices (and permutation entries) with one coalesced load each and hands them out with ds_bpermute; each
-//    slot has 4 gathers and their 4 one-word value loads vals[e * H + head] in flight before the first fma.  Rows of
-//    more than kAggChunk entries: chunk partials per (chunk, row, column), merged in chunk order by the wave whose chunk
-//    holds the row's first entry.
+//    slot has 4 gathers and their 4 one-word value loads vals[e * H + head] in flight before the first fma.  The
+//    dispatch by row length is gather_rows.h's: 8 rows a wave, rows of more than kAggChunk entries by chunk partials
+//    per (chunk, row, column), merged in chunk order by the wave whose chunk holds the row's first entry.
 //    Fixed order: slot s adds the entries s, s + SLOTS, ... in ascending order (fma), the slots are merged by the xor
 //    butterfly LPS .. 32, chunk partials in chunk order.
 //
@@ -41,37 +41,13 @@
 
 #include <cstdint>
 
-#include "long_chunks.h"
+#include "gather_rows.h"
 #include "spmm_kernels.h"
 
 namespace gcn {
 namespace {
 
-constexpr int kRowsPerWave = 8;
-constexpr int kGChunk = kAggChunk;                     // entries per chunk of the long-row route
-constexpr int kGLong = kAggChunk;                      // rows longer than this are split over waves
-constexpr int kGLongWaves = 8192;
 constexpr int kMaxFastHeads = 16;
-
-template <int VEC>
-__device__ __forceinline__ void load_row(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-    static_assert(VEC == 1);
-    v[0] = p[0];
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void store_row(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    static_assert(VEC == 1);
-    p[0] = v[0];
-  }
-}
 
 struct HeadsSpmmArgs {
   const int *idx, *perm;
@@ -142,7 +118,7 @@ struct Gatv2BackwardOp {
   }
 };
 
-// entries [b, b + n) of one row (n <= kGChunk) on a wave; the lane's columns are j .. j + VEC of head `head` (jok: they exist)
+// entries [b, b + n) of one row (n <= kGatherChunk) on a wave; the lane's columns are j .. j + VEC of head `head` (jok: they exist)
 template <int VEC, int LPS, class Op>
 __device__ __forceinline__ void spmm_walk(const HeadsSpmmArgs& a, const Op& op, int b, int n, int lane, int j, bool jok, int head,
                                           const typename Op::template Row<VEC>& row, float (&acc)[Op::NS * VEC]) {
@@ -186,109 +162,33 @@ __device__ __forceinline__ void merge_slots(float (&acc)[VEC]) {
   }
 }
 
-template <int VEC, int LPS, class Op>
-__global__ void __launch_bounds__(256) spmm_heads_rows_kernel(HeadsSpmmArgs a, Op op, const int* __restrict__ rowptr, int rows,
-                                                              int* __restrict__ long_flag) {
-  const int lane = threadIdx.x & 63;
-  const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
-  if (wave * kRowsPerWave >= rows) return;
-  const int r0 = (int)wave * kRowsPerWave;
-  const int ri = r0 + lane < rows ? r0 + lane : rows;
-  const int rp = rowptr[ri];
-  const int j = (blockIdx.y * LPS + (lane % LPS)) * VEC;
-  const bool jok = j < a.k;
-  const int head = jok ? j / a.F : 0;
-  for (int q = 0; q < kRowsPerWave && r0 + q < rows; ++q) {
-    const int b = __shfl(rp, q), e = __shfl(rp, q + 1);
-    const int n = e - b;
-    if (n > kGLong) {
-      if (lane == 0) *long_flag = 1;
-      continue;
-    }
-    typename Op::template Row<VEC> row;
-    float acc[Op::NS * VEC];
+// what gather_rows.h asks of a walk, over the args and the per-element op E: Acc stays the bare array of the walk, and the
+// head of a lane's columns (the one division) is found once a kernel
+template <int VEC_, int LPS_, class E>
+struct HeadsRowsOp : HeadsSpmmArgs {
+  static constexpr int VEC = VEC_, LPS = LPS_, NS = E::NS;
+  E e;
+  using Acc = float[NS * VEC];
+  using Partial = float;
+  using Lane = int;
+  using Row = typename E::template Row<VEC>;
+  __device__ __forceinline__ int lane_ctx(int j, bool jok) const { return jok ? j / F : 0; }
+  __device__ __forceinline__ void reduce(int r, int b, int n, int lane, int j, bool jok, int head, Row& row, Acc& acc) const {
 #pragma unroll
-    for (int v = 0; v < Op::NS * VEC; ++v) acc[v] = 0.f;
-    op.begin(a, r0 + q, jok ? j : 0, row);
-    spmm_walk<VEC, LPS>(a, op, b, n, lane, j, jok, head, row, acc);
-    merge_slots<Op::NS * VEC, LPS>(acc);
-    if (lane < LPS && jok) op.template store<VEC>(a, r0 + q, j, acc);
+    for (int v = 0; v < NS * VEC; ++v) acc[v] = 0.f;
+    e.begin(*this, r, jok ? j : 0, row);
+    spmm_walk<VEC, LPS>(*this, e, b, n, lane, j, jok, head, row, acc);
+    merge_slots<NS * VEC, LPS>(acc);
   }
-}
+  __device__ __forceinline__ void store(int r, int j, const Acc& acc) const { e.template store<VEC>(*this, r, j, acc); }
+  static __device__ __forceinline__ float partial(const Acc& acc, int t, int v) { return acc[t * VEC + v]; }
+  static __device__ __forceinline__ void merge_next(float& s, float o) { s += o; }
+  __device__ __forceinline__ void store_one(int r, int j, int t, float v) const { e.store_one(*this, r, j, t, v); }
+};
 
-template <int VEC, int LPS, class Op>
-__global__ void __launch_bounds__(256) spmm_heads_long_partial_kernel(HeadsSpmmArgs a, Op op, const int* __restrict__ rowptr, int rows, int nnz,
-                                                                      int nchunks, const int* __restrict__ long_flag,
-                                                                      float* __restrict__ part) {
-  if (*long_flag == 0) return;
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = gridDim.x * 4;
-  const int j = (blockIdx.y * LPS + (lane % LPS)) * VEC;
-  const bool jok = j < a.k;
-  const int head = jok ? j / a.F : 0;
-  for_long_segments<kGChunk, kGLong>(rowptr, rows, nnz, nchunks, wave, nwaves, lane, [&](int c, int slot, const Segment& sg) {
-    typename Op::template Row<VEC> row;
-    float acc[Op::NS * VEC];
-#pragma unroll
-    for (int v = 0; v < Op::NS * VEC; ++v) acc[v] = 0.f;
-    op.begin(a, sg.r, jok ? j : 0, row);
-    spmm_walk<VEC, LPS>(a, op, sg.sb, sg.se - sg.sb, lane, j, jok, head, row, acc);
-    merge_slots<Op::NS * VEC, LPS>(acc);
-    if (lane < LPS && jok) {
-#pragma unroll
-      for (int t = 0; t < Op::NS; ++t) {               // (sum t's partials: the t-th set of 2 nchunks rows)
-        float* p = part + ((size_t)t * 2 * nchunks + 2 * (size_t)c + slot) * a.k + j;
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) p[v] = acc[t * VEC + v];
-      }
-    }
-  });
-}
-
-template <int VEC, int LPS, class Op>
-__global__ void __launch_bounds__(256) spmm_heads_long_finish_kernel(HeadsSpmmArgs a, Op op, const int* __restrict__ rowptr, int rows, int nnz,
-                                                                     int nchunks, const int* __restrict__ long_flag,
-                                                                     const float* __restrict__ part) {
-  if (*long_flag == 0) return;
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = gridDim.x * 4;
-  const int j0 = blockIdx.y * LPS * VEC;
-  const int j1 = j0 + LPS * VEC < a.k ? j0 + LPS * VEC : a.k;
-  for_long_segments<kGChunk, kGLong>(rowptr, rows, nnz, nchunks, wave, nwaves, lane, [&](int c, int slot, const Segment& sg) {
-    // one writer per row: the wave whose chunk holds the row's first entry merges the partials, in chunk order
-    const int c_first = sg.rb / kGChunk, c_last = (sg.re - 1) / kGChunk;
-    if (c != c_first) return;
-    const int first_slot = sg.rb > c_first * kGChunk ? 1 : 0;
-    for (int j = j0 + lane; j < j1; j += 64) {
-#pragma unroll
-      for (int t = 0; t < Op::NS; ++t) {
-        const float* pt = part + (size_t)t * 2 * nchunks * a.k;
-        float acc = pt[(2 * (size_t)c_first + first_slot) * a.k + j];
-        for (int cc = c_first + 1; cc <= c_last; ++cc) acc += pt[2 * (size_t)cc * a.k + j];
-        op.store_one(a, sg.r, j, t, acc);
-      }
-    }
-  });
-}
-
-template <int VEC, int LPS, class Op>
-hipError_t run_spmm(const HeadsSpmmArgs& a, const Op& op, const int* rowptr, int rows, int nnz, void* ws, hipStream_t st) {
-  int* flag = static_cast<int*>(ws);
-  float* part = reinterpret_cast<float*>(static_cast<char*>(ws) + 16);
-  const long long tiles = ((long long)a.k + LPS * VEC - 1) / (LPS * VEC);
-  if (tiles > 65535) return hipErrorInvalidValue;
-  if (hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), st); e != hipSuccess) return e;
-  const long long waves = ((long long)rows + kRowsPerWave - 1) / kRowsPerWave;
-  spmm_heads_rows_kernel<VEC, LPS, Op><<<dim3((unsigned)((waves + 3) / 4), (unsigned)tiles), 256, 0, st>>>(a, op, rowptr, rows, flag);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  if (nnz <= kGLong) return hipSuccess;
-  const int nchunks = (int)(((long long)nnz + kGChunk - 1) / kGChunk);
-  const int nw = nchunks < kGLongWaves ? nchunks : kGLongWaves;
-  const dim3 grid((unsigned)((nw + 3) / 4), (unsigned)tiles);
-  spmm_heads_long_partial_kernel<VEC, LPS, Op><<<grid, 256, 0, st>>>(a, op, rowptr, rows, nnz, nchunks, flag, part);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  spmm_heads_long_finish_kernel<VEC, LPS, Op><<<grid, 256, 0, st>>>(a, op, rowptr, rows, nnz, nchunks, flag, part);
-  return hipGetLastError();
+template <int VEC, int LPS, class E>
+hipError_t run_spmm(const HeadsSpmmArgs& a, const E& op, const int* rowptr, int rows, int nnz, void* ws, hipStream_t st) {
+  return run_gather(HeadsRowsOp<VEC, LPS, E>{a, op}, rowptr, rows, nnz, ws, st);
 }
 
 template <int VEC, class Op>
@@ -343,7 +243,7 @@ __device__ __forceinline__ float merge_parts(float s, int pshift) {
   return s;
 }
 
-// entries [b0, b0 + n) of row r (0 < n <= kGChunk) on a wave
+// entries [b0, b0 + n) of row r (0 < n <= kGatherChunk) on a wave
 template <int VEC, class Op>
 __device__ __forceinline__ void sddmm_entries(const SddmmHeadsArgs& s, const Op& op, int r, int b0, int n, int lane) {
   const float* arow = s.a + (size_t)r * s.k;
@@ -412,20 +312,9 @@ template <int VEC, class Op>
 __global__ void __launch_bounds__(256) sddmm_heads_rows_kernel(SddmmHeadsArgs s, Op op, const int* __restrict__ rowptr, int m,
                                                                int* __restrict__ long_flag) {
   const int lane = threadIdx.x & 63;
-  const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
-  if (wave * kRowsPerWave >= m) return;
-  const int r0 = (int)wave * kRowsPerWave;
-  const int ri = r0 + lane < m ? r0 + lane : m;
-  const int rp = rowptr[ri];
-  for (int q = 0; q < kRowsPerWave && r0 + q < m; ++q) {
-    const int b = __shfl(rp, q), e = __shfl(rp, q + 1);
-    const int n = e - b;
-    if (n > kGLong) {
-      if (lane == 0) *long_flag = 1;
-      continue;
-    }
-    if (n > 0) sddmm_entries<VEC>(s, op, r0 + q, b, n, lane);
-  }
+  for_wave_rows<kRowsPerWave, kGatherLong>(rowptr, m, lane, long_flag, [&](int r, int b, int n) {
+    if (n > 0) sddmm_entries<VEC>(s, op, r, b, n, lane);
+  });
 }
 
 template <int VEC, class Op>
@@ -434,7 +323,7 @@ __global__ void __launch_bounds__(256) sddmm_heads_long_kernel(SddmmHeadsArgs s,
   if (*long_flag == 0) return;
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = gridDim.x * 4;
-  for_long_segments<kGChunk, kGLong>(rowptr, m, nnz, nchunks, wave, nwaves, lane, [&](int c, int slot, const Segment& sg) {
+  for_long_segments<kGatherChunk, kGatherLong>(rowptr, m, nnz, nchunks, wave, nwaves, lane, [&](int c, int slot, const Segment& sg) {
     sddmm_entries<VEC>(s, op, sg.r, sg.sb, sg.se - sg.sb, lane);
   });
 }
@@ -449,14 +338,12 @@ hipError_t run_sddmm(SddmmHeadsArgs s, const Op& op, const int* rowptr, int m, i
   const long long waves = ((long long)m + kRowsPerWave - 1) / kRowsPerWave;
   sddmm_heads_rows_kernel<VEC, Op><<<(unsigned)((waves + 3) / 4), 256, 0, st>>>(s, op, rowptr, m, flag);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  if (nnz <= kGLong) return hipSuccess;
-  const int nchunks = (int)(((long long)nnz + kGChunk - 1) / kGChunk);
-  const int nw = nchunks < kGLongWaves ? nchunks : kGLongWaves;
+  if (nnz <= kGatherLong) return hipSuccess;
+  const int nchunks = (int)(((long long)nnz + kGatherChunk - 1) / kGatherChunk);
+  const int nw = nchunks < kGatherLongWaves ? nchunks : kGatherLongWaves;
   sddmm_heads_long_kernel<VEC, Op><<<(unsigned)((nw + 3) / 4), 256, 0, st>>>(s, op, rowptr, m, nnz, nchunks, flag);
   return hipGetLastError();
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // log2 H where the entry walk has its fast route (H a power of two <= kMaxFastHeads), -1 otherwise
 int fast_hshift(int H) {
@@ -469,7 +356,7 @@ int fast_hshift(int H) {
 }  // namespace
 
 size_t heads_spmm_workspace_bytes(int nnz, int k) {
-  return 16 + 8 * (size_t)k * (size_t)(((long long)nnz + kGChunk - 1) / kGChunk);
+  return 16 + 8 * (size_t)k * (size_t)(((long long)nnz + kGatherChunk - 1) / kGatherChunk);
 }
 
 // the 16-byte form needs every gathered or stored row to start on a 16-byte boundary (the base pointers and the row stride)
@@ -491,7 +378,7 @@ hipError_t launch_sddmm_heads(const int* rowptr, const int* col, int m, int nnz,
 }
 
 size_t gatv2_workspace_bytes(int nnz, int k) {
-  return 16 + 2 * 8 * (size_t)k * (size_t)(((long long)nnz + kGChunk - 1) / kGChunk);
+  return 16 + 2 * 8 * (size_t)k * (size_t)(((long long)nnz + kGatherChunk - 1) / kGatherChunk);
 }
 
 hipError_t launch_gatv2_scores(const int* rowptr, const int* col, int m, int nnz, int H, int k, const float* h_dst, const float* h_src,

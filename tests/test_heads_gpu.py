@@ -481,6 +481,24 @@ def test_gather_kernels_shifted_keep_the_standing_bound(H, F):
         assert r <= 1.0, (op, r)
 
 
+@pytest.mark.parametrize("H,F", [(8, 40), (3, 25)])
+def test_spmm_heads_second_column_tile_with_long_rows(H, F):
+    """chunk partials in a column tile past the first (gather_rows.h: plane t, row 2 c + slot, column j of the tile
+    blockIdx.y): k = 320 is a quarter of a second 256-column tile at VEC = 4 (five 64-column tiles once shifted), k = 75
+    puts 11 columns into a second 64-column tile; rows on both sides of the chunk and of one, two and three chunks"""
+    rowptr, col, n = _csr_from_lens(np.array([0, 1, 4095, 4096, 4097, 8193, 12289, 3], np.int64), 50000, 6)
+    rng = np.random.default_rng(H + F)
+    k = H * F
+    x = dev(rng.integers(-3, 4, (n, k)).astype(np.float32))
+    a = dev(rng.integers(-3, 4, (len(rowptr) - 1, k)).astype(np.float32))
+    vals = dev((rng.integers(0, 8, (len(col), H)) / 8.0).astype(np.float32))
+    for by in (0, 1):
+        P = RawProblem(rowptr, col, n, by=by)
+        P.exact(H, F, seed=5 * H + F, what="second column tile")
+        assert torch.equal(P.spmm(vals, x, H), P.spmm(vals, x, H)), f"two calls, shifted by {by}"
+        assert torch.equal(P.spmm(vals, a, H, transposed=True), P.spmm(vals, a, H, transposed=True)), f"two calls (T), shifted by {by}"
+
+
 @pytest.mark.parametrize("H", [8, 3])
 def test_softmax_family_with_every_operand_shifted_by_one_element(H):
     """these kernels use element accesses only: a shifted operand must give the bits of the aligned call, whose bounds the
