@@ -6,6 +6,8 @@ non-zero status, a GcnAmdError is raised.
 import ctypes
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (GCN_AMD_LIB: load a private copy — long-running host tools that must survive a rebuild of the in-tree library)
 LIB_PATH = os.environ.get("GCN_AMD_LIB") or os.path.join(_HERE, "lib", "libgcnspmm.so")
@@ -249,3 +251,39 @@ def check(status, what):
         err = GcnAmdError(f"{what}: {msg} (status {status})")
         err.status = int(status)
         raise err
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _stream_ptr(device):
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+_Tensor = torch.Tensor
+_calls = {}                  # name -> (function, number of arguments): resolved once per name
+
+
+def call(name, *args, device=None):
+    """One call of the status-returning C-ABI function `name`: a torch.Tensor argument goes as its address, None as a null
+    pointer, everything else as it is.  With `device` the call runs under ``torch.cuda.device(device)`` and that device's
+    current stream is appended as the last argument.  A non-zero status raises GcnAmdError under `name`, `.status` set.
+    Nothing else: no ``.contiguous()``, no dtype or shape checks.  TypeError for a wrong number of arguments (before the
+    library is entered: ctypes lets surplus arguments through), GcnAmdError for a name include/gcn_spmm.h does not declare."""
+    try:
+        fn, nargs = _calls[name]
+    except KeyError:
+        if name not in SIGNATURES:
+            raise GcnAmdError(f"`{name}` is not a function declared in include/gcn_spmm.h") from None
+        fn, nargs = _calls[name] = getattr(load(), name), len(SIGNATURES[name][1])
+    if len(args) + (device is not None) != nargs:
+        raise TypeError(f"{name} takes {nargs} arguments ({len(args) + (device is not None)} given)")
+    args = [a.data_ptr() if isinstance(a, _Tensor) else a for a in args]    # (an int under a void* argtype is the address)
+    if device is None:
+        status = fn(*args)
+    else:
+        with torch.cuda.device(device):
+            status = fn(*args, torch.cuda.current_stream(device).cuda_stream)
+    if status != 0:
+        check(status, name)

@@ -15,7 +15,8 @@ inside a captured step.  There is no CPU path: CPU tensors raise.
 import torch
 
 from . import _lib
-from .spmm import CsrAdjacency, _ptr, _stream_ptr, spmm
+from ._lib import call
+from .spmm import CsrAdjacency, spmm
 
 _CHUNK = 4096                # entries per workspace partial: GCN_AGGREGATE_WS_BYTES in include/gcn_spmm.h
 _REDUCE = {"max": _lib.REDUCE_MAX, "min": _lib.REDUCE_MIN}
@@ -26,38 +27,11 @@ def _ws_bytes(nnz, k):
     return 16 + 16 * int(k) * ((int(nnz) + _CHUNK - 1) // _CHUNK)
 
 
-def _workspace(adj, k, device):
-    """the scratch of the kernels (a flag and the partials of rows longer than 4096 entries), kept on the adjacency and
-    shared by its calls, which one stream orders.  Its size grows with k, so a wider call than any before allocates a
-    larger one (a first call of a width must therefore come before a capture of it, as everywhere here).  The smaller
-    buffers it replaces are kept alive on the adjacency, never handed back: a captured step recorded their addresses
-    and goes on writing its flag and partials there at every replay."""
-    need = _ws_bytes(adj.nnz, k)
-    ws = getattr(adj, "_agg_ws", None)
-    if ws is None or ws.numel() < need or ws.device != device:
-        if ws is not None:
-            adj._agg_ws_retired = getattr(adj, "_agg_ws_retired", []) + [ws]
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
-        adj._agg_ws = ws
-    return ws
-
-
-def _transpose_pattern(adj):
-    """(rowptr, row of each entry, int32 permutation) of the transposed pattern, duplicates kept as separate entries;
-    entry t of the transpose is entry perm[t] of adj.  A mutable adjacency has all three already (its transpose and
-    ``_tperm``); otherwise they are built once by the same construction (``CsrAdjacency._transposed_pattern``) — not
-    by ``transpose()``, which keeps no permutation."""
-    if adj.mutable_values:
-        t = adj._mutable_transpose()
-        perm = getattr(adj, "_tperm32", None)
-        if perm is None:
-            perm = adj._tperm32 = adj._tperm.to(torch.int32)
-        return t.rowptr, t.col, perm
-    cached = getattr(adj, "_agg_transpose", None)
-    if cached is None:
-        trp, trow, perm = adj._transposed_pattern()
-        cached = adj._agg_transpose = (trp, trow, perm.to(torch.int32))
-    return cached
+def _scratch(adj, k, device):
+    """the "aggregate" buffer of the adjacency (a flag and the partials of rows longer than 4096 entries), shared by its
+    calls, which one stream orders; None for a pattern without entries.  Its size grows with k, so a first call of a width
+    must come before a capture of it, as everywhere here (the buffer it replaces stays allocated: spmm.Scratch)"""
+    return adj._scratch.get("aggregate", _ws_bytes(adj.nnz, k), device) if adj.nnz else None
 
 
 def _pattern_twin(adj, reduce):
@@ -86,12 +60,9 @@ class _SelectFunction(torch.autograd.Function):
         k = int(x.shape[1])
         out = torch.empty((adj.m, k), dtype=x.dtype, device=x.device)
         arg = torch.empty((adj.m, k), dtype=torch.int32, device=x.device)
-        ws = _workspace(adj, k, x.device) if adj.nnz else None
-        with torch.cuda.device(x.device):
-            st = _lib.load().gcn_aggregate_csr(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.n, adj.nnz, _ptr(x), _DTYPE[x.dtype], k,
-                                               _REDUCE[reduce], _ptr(out), _ptr(arg), _ptr(ws) if ws is not None else None,
-                                               ws.numel() if ws is not None else 0, _stream_ptr(x.device))
-        _lib.check(st, "gcn_aggregate_csr")
+        ws = _scratch(adj, k, x.device)
+        call("gcn_aggregate_csr", adj.rowptr, adj.col, adj.m, adj.n, adj.nnz, x, _DTYPE[x.dtype], k, _REDUCE[reduce], out, arg,
+             ws, ws.numel() if ws is not None else 0, device=x.device)
         ctx.adj = adj
         ctx.save_for_backward(arg)
         ctx.mark_non_differentiable(arg)
@@ -107,14 +78,10 @@ class _SelectFunction(torch.autograd.Function):
         g = g.contiguous()
         k = int(g.shape[1])
         gx = torch.empty((adj.n, k), dtype=g.dtype, device=g.device)
-        trowptr, trow, tperm = _transpose_pattern(adj)
-        ws = _workspace(adj, k, g.device) if adj.nnz else None
-        with torch.cuda.device(g.device):
-            st = _lib.load().gcn_aggregate_backward_csr(_ptr(trowptr), _ptr(trow), _ptr(tperm), adj.n, adj.m, adj.nnz, _ptr(g),
-                                                        _DTYPE[g.dtype], _ptr(arg), k, _ptr(gx),
-                                                        _ptr(ws) if ws is not None else None,
-                                                        ws.numel() if ws is not None else 0, _stream_ptr(g.device))
-        _lib.check(st, "gcn_aggregate_backward_csr")
+        trowptr, trow, tperm = adj.tpattern()
+        ws = _scratch(adj, k, g.device)
+        call("gcn_aggregate_backward_csr", trowptr, trow, tperm, adj.n, adj.m, adj.nnz, g, _DTYPE[g.dtype], arg, k, gx,
+             ws, ws.numel() if ws is not None else 0, device=g.device)
         return None, gx, None
 
 

@@ -24,26 +24,30 @@ import functools
 import torch
 
 from . import _lib
-from .spmm import CsrAdjacency, _ptr, _stream_ptr
+from ._lib import call
+from .spmm import CsrAdjacency, Scratch
 
 
 @functools.lru_cache(maxsize=None)
-def _ws_need(nnz, heads, k):
+def _ws_need(query, nnz, heads, k):
+    """bytes of scratch the library's `query` (gcn_heads_ws_bytes, gcn_gatv2_ws_bytes) asks for: a flag and the chunk
+    partials of long rows"""
     need = ctypes.c_size_t(0)
-    _lib.check(_lib.load().gcn_heads_ws_bytes(0, nnz, heads, k, ctypes.byref(need)), "gcn_heads_ws_bytes")
+    call(query, 0, nnz, heads, k, ctypes.byref(need))
     return need.value
 
 
 def _workspace(owner, nnz, device, heads=1, k=1):
-    """the scratch the kernels want (gcn_heads_ws_bytes: a flag and the chunk partials of long rows), kept on the adjacency:
-    allocated at the first call — so before a capture, with the plans and the transposed pattern — grown when a call needs
-    more, and shared by its calls, which one stream orders"""
-    need = _ws_need(int(nnz), int(heads), int(k))
-    ws = getattr(owner, "_edge_ws", None)
-    if ws is None or ws.numel() < need or ws.device != device:
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
-        owner._edge_ws = ws
-    return ws
+    """the scratch the kernels want (gcn_heads_ws_bytes: a flag and the chunk partials of long rows): the "edge" buffer of
+    the owner's Scratch — an adjacency's, or the Scratch itself for a segment_sum without one — shared by the owner's
+    softmax, segment-sum and heads calls, which one stream orders.  Only the size rule lives here; the keeping is Scratch's"""
+    keeper = owner._scratch if isinstance(owner, CsrAdjacency) else owner
+    return keeper.get("edge", _ws_need("gcn_heads_ws_bytes", int(nnz), int(heads), int(k)), device)
+
+
+def _check_adj(adj, what):
+    if not isinstance(adj, CsrAdjacency):
+        raise TypeError(f"{what}: adj must be a CsrAdjacency")
 
 
 def _fp32_tensors(items):
@@ -66,58 +70,27 @@ def _heads_of(t):
     return int(t.shape[1]) if t.dim() == 2 else 1
 
 
-def _heads_tpattern(adj):
-    """(rowptr int32 [n + 1], source row of each entry int32 [nnz], its index in adj's order int32 [nnz]) of the transposed
-    pattern, built once per adjacency (on the device) and kept on it"""
-    tp = getattr(adj, "_heads_tp", None)
-    if tp is None:
-        trp, trow, perm = adj._transposed_pattern()
-        tp = adj._heads_tp = (trp.contiguous(), trow.contiguous(), perm.to(torch.int32).contiguous())
-    return tp
-
-
-def _column_sums_pattern(adj):
-    """(rowptr int32 [n + 1], permutation int32 [nnz]) of the transposed pattern for sums by column: a mutable adjacency's
-    own (its mutable transpose is built from the same _transposed_pattern, so it is the same pattern and is never built
-    twice), _heads_tpattern otherwise"""
-    if not adj.mutable_values:
-        trp, _trow, tperm = _heads_tpattern(adj)
-        return trp, tperm
-    t = adj._mutable_transpose()                         # (its pattern and permutation; its values are not touched)
-    perm = getattr(adj, "_tperm32", None)
-    if perm is None:
-        perm = adj._tperm32 = adj._tperm.to(torch.int32)
-    return t.rowptr, perm
-
-
 def _segment_sum_raw(owner, rowptr, rows, x, perm, out):
     """out [rows] or [rows, H] = the row sums over rowptr of x [nnz] or [nnz, H] (read through perm)"""
     nnz, heads = int(x.shape[0]), _heads_of(x)
     if rows == 0 or nnz == 0:
         return out.zero_()
     ws = _workspace(owner, nnz, x.device, heads, heads)
-    with torch.cuda.device(x.device):
-        st = _lib.load().gcn_segment_sum_heads_csr_f32(_ptr(rowptr), rows, nnz, heads, _ptr(x),
-                                                       _ptr(perm) if perm is not None else None, _ptr(out), _ptr(ws),
-                                                       ws.numel(), _stream_ptr(x.device))
-    _lib.check(st, "gcn_segment_sum_heads_csr_f32")
+    call("gcn_segment_sum_heads_csr_f32", rowptr, rows, nnz, heads, x, perm, out, ws, ws.numel(), device=x.device)
     return out
 
 
-class _SegmentSumHolder:
-    """keeps the workspace of segment_sum calls that have no adjacency to keep it on"""
+_loose = {}                  # (device index, stream handle) -> Scratch of the segment_sum calls that have no adjacency to keep
+                             # it on: calls on different streams never share a workspace
 
 
-_loose = {}                  # (device index, stream handle) -> holder: calls on different streams never share a workspace
-
-
-def _loose_holder(device):
+def _loose_scratch(device):
     key = (device.index if device.index is not None else torch.cuda.current_device(),
            torch.cuda.current_stream(device).cuda_stream)
-    holder = _loose.get(key)
-    if holder is None:
-        holder = _loose[key] = _SegmentSumHolder()
-    return holder
+    scratch = _loose.get(key)
+    if scratch is None:
+        scratch = _loose[key] = Scratch()
+    return scratch
 
 
 def segment_sum(rowptr, x, perm=None):
@@ -137,7 +110,7 @@ def segment_sum(rowptr, x, perm=None):
         raise _lib.GcnAmdError("segment_sum: x must be fp32, rowptr and perm int32")
     m = int(rowptr.numel()) - 1
     out = torch.empty((m,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
-    return _segment_sum_raw(_loose_holder(x.device), rowptr.contiguous(), m, x.detach().contiguous(),
+    return _segment_sum_raw(_loose_scratch(x.device), rowptr.contiguous(), m, x.detach().contiguous(),
                             perm.contiguous() if perm is not None else None, out)
 
 
@@ -151,10 +124,7 @@ class _EdgeSoftmaxFunction(torch.autograd.Function):
         heads = _heads_of(s)
         if adj.m and adj.nnz:
             ws = _workspace(adj, adj.nnz, s.device, heads, heads)
-            with torch.cuda.device(s.device):
-                st = _lib.load().gcn_edge_softmax_heads_csr_f32(_ptr(adj.rowptr), adj.m, adj.nnz, heads, _ptr(s), _ptr(p),
-                                                                _ptr(ws), ws.numel(), _stream_ptr(s.device))
-            _lib.check(st, "gcn_edge_softmax_heads_csr_f32")
+            call("gcn_edge_softmax_heads_csr_f32", adj.rowptr, adj.m, adj.nnz, heads, s, p, ws, ws.numel(), device=s.device)
         ctx.adj = adj
         ctx.save_for_backward(p)
         return p
@@ -169,11 +139,8 @@ class _EdgeSoftmaxFunction(torch.autograd.Function):
         heads = _heads_of(p)
         if adj.m and adj.nnz:
             ws = _workspace(adj, adj.nnz, p.device, heads, heads)
-            with torch.cuda.device(p.device):
-                st = _lib.load().gcn_edge_softmax_heads_backward_csr_f32(_ptr(adj.rowptr), adj.m, adj.nnz, heads, _ptr(p),
-                                                                         _ptr(g), _ptr(ds), _ptr(ws), ws.numel(),
-                                                                         _stream_ptr(p.device))
-            _lib.check(st, "gcn_edge_softmax_heads_backward_csr_f32")
+            call("gcn_edge_softmax_heads_backward_csr_f32", adj.rowptr, adj.m, adj.nnz, heads, p, g, ds, ws, ws.numel(),
+                 device=p.device)
         return None, ds
 
 
@@ -183,8 +150,7 @@ def edge_softmax(adj, scores):
     in adj's CSR order; differentiable.  Empty rows have no entries; an all -inf row gets zeros (torch.softmax: NaN); a NaN
     stays in its row.  `scores` may be 2-D [nnz, H]: the softmax is taken per head, all heads in one pass (p is [nnz, H]).
     ValueError for a wrong shape, GcnAmdError for a CPU tensor or a dtype other than fp32."""
-    if not isinstance(adj, CsrAdjacency):
-        raise TypeError("edge_softmax: adj must be a CsrAdjacency")
+    _check_adj(adj, "edge_softmax")
     if isinstance(scores, torch.Tensor) and scores.dim() == 2:           # [nnz, H]: all heads in one pass
         _fp32_tensors([(scores, (adj.nnz, None), "edge_softmax: scores", f"a 2-D tensor [nnz = {adj.nnz}, H] in CSR order")])
     else:
@@ -205,11 +171,8 @@ class _GatEdgeSoftmaxFunction(torch.autograd.Function):
         p = torch.empty((adj.nnz,) + tuple(ad.shape[1:]), dtype=torch.float32, device=ad.device)
         if adj.m and adj.nnz:
             ws = _workspace(adj, adj.nnz, ad.device, heads, heads)
-            with torch.cuda.device(ad.device):
-                st = _lib.load().gcn_gat_edge_softmax_heads_csr_f32(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, heads,
-                                                                    _ptr(ad), _ptr(asrc), slope, _ptr(p), _ptr(ws), ws.numel(),
-                                                                    _stream_ptr(ad.device))
-            _lib.check(st, "gcn_gat_edge_softmax_heads_csr_f32")
+            call("gcn_gat_edge_softmax_heads_csr_f32", adj.rowptr, adj.col, adj.m, adj.nnz, heads, ad, asrc, slope, p, ws,
+                 ws.numel(), device=ad.device)
         ctx.adj, ctx.slope = adj, slope
         ctx.save_for_backward(ad, asrc, p)
         return p
@@ -228,13 +191,10 @@ class _GatEdgeSoftmaxFunction(torch.autograd.Function):
         if not (adj.m and adj.nnz):
             return None, g_dst.zero_(), g_src.zero_(), None
         ws = _workspace(adj, adj.nnz, dev, heads, heads)
-        with torch.cuda.device(dev):
-            st = _lib.load().gcn_gat_edge_softmax_heads_backward_csr_f32(
-                _ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, heads, _ptr(ad), _ptr(asrc), ctx.slope, _ptr(p), _ptr(g),
-                _ptr(ds), _ptr(g_dst), _ptr(ws), ws.numel(), _stream_ptr(dev))
-        _lib.check(st, "gcn_gat_edge_softmax_heads_backward_csr_f32")
+        call("gcn_gat_edge_softmax_heads_backward_csr_f32", adj.rowptr, adj.col, adj.m, adj.nnz, heads, ad, asrc, ctx.slope, p,
+             g, ds, g_dst, ws, ws.numel(), device=dev)
         if ctx.needs_input_grad[2]:
-            trp, tperm = _column_sums_pattern(adj)
+            trp, _trow, tperm = adj.tpattern()
             _segment_sum_raw(adj, trp, adj.n, ds, tperm, g_src)
         else:
             g_src = None
@@ -247,8 +207,7 @@ def gat_edge_softmax(adj, a_dst, a_src, negative_slope=0.2):
     `adj` must have been made with mutable_values=True — only because grad_a_src sums ds by column through the transpose
     permutation such an adjacency keeps (and the result is meant for spmm(adj, h, values=p), which needs it anyway).
     With a_dst [m, H] and a_src [n, H] all heads run in one pass, p is [nnz, H] (for spmm_heads) and any adjacency will do."""
-    if not isinstance(adj, CsrAdjacency):
-        raise TypeError("gat_edge_softmax: adj must be a CsrAdjacency")
+    _check_adj(adj, "gat_edge_softmax")
     if isinstance(a_dst, torch.Tensor) and isinstance(a_src, torch.Tensor) and (a_dst.dim() == 2 or a_src.dim() == 2):
         heads = int(a_dst.shape[-1])                     # a_dst [m, H], a_src [n, H]: all heads in one pass, any adjacency
         _fp32_tensors([(a_dst, (adj.m, heads), "gat_edge_softmax: a_dst", f"a 2-D tensor [{adj.m}, {heads}]"),
@@ -270,11 +229,7 @@ def _spmm_heads_raw(adj, rowptr, idx, perm, rows, vals, x, heads):
     if rows == 0 or adj.nnz == 0:
         return out.zero_()
     ws = _workspace(adj, adj.nnz, x.device, heads, k)
-    with torch.cuda.device(x.device):
-        st = _lib.load().gcn_spmm_heads_csr_f32(_ptr(rowptr), _ptr(idx), _ptr(perm) if perm is not None else None, rows,
-                                                adj.nnz, heads, k, _ptr(vals), _ptr(x), _ptr(out), _ptr(ws), ws.numel(),
-                                                _stream_ptr(x.device))
-    _lib.check(st, "gcn_spmm_heads_csr_f32")
+    call("gcn_spmm_heads_csr_f32", rowptr, idx, perm, rows, adj.nnz, heads, k, vals, x, out, ws, ws.numel(), device=x.device)
     return out
 
 
@@ -284,10 +239,7 @@ def _sddmm_heads_raw(adj, a, b, heads):
     if adj.m == 0 or adj.nnz == 0:
         return out
     ws = _workspace(adj, adj.nnz, a.device, heads, k)
-    with torch.cuda.device(a.device):
-        st = _lib.load().gcn_sddmm_heads_csr_f32(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, heads, k, _ptr(a), _ptr(b),
-                                                 _ptr(out), _ptr(ws), ws.numel(), _stream_ptr(a.device))
-    _lib.check(st, "gcn_sddmm_heads_csr_f32")
+    call("gcn_sddmm_heads_csr_f32", adj.rowptr, adj.col, adj.m, adj.nnz, heads, k, a, b, out, ws, ws.numel(), device=a.device)
     return out
 
 
@@ -312,7 +264,7 @@ class _SpmmHeadsFunction(torch.autograd.Function):
         g = g.contiguous()
         gx = gv = None
         if ctx.needs_input_grad[1]:
-            trp, trow, tperm = _heads_tpattern(adj)
+            trp, trow, tperm = adj.tpattern()
             gx = _spmm_heads_raw(adj, trp, trow, tperm, adj.n, v, g, ctx.heads)
         if ctx.needs_input_grad[2]:
             gv = _sddmm_heads_raw(adj, g, xd, ctx.heads)
@@ -340,7 +292,7 @@ class _SddmmHeadsFunction(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             ga = _spmm_heads_raw(adj, adj.rowptr, adj.col, None, adj.m, g, bd, ctx.heads)
         if ctx.needs_input_grad[2]:
-            trp, trow, tperm = _heads_tpattern(adj)
+            trp, trow, tperm = adj.tpattern()
             gb = _spmm_heads_raw(adj, trp, trow, tperm, adj.n, g, ad, ctx.heads)
         return None, ga, gb, None
 
@@ -350,8 +302,7 @@ def spmm_heads(adj, x, values):
     heads in one walk of the adjacency (gcn_spmm_heads_csr_f32).  x: [n, H*F] fp32, head h in columns hF .. hF + F - 1;
     values: [nnz, H] fp32 in adj's CSR order (adj's own values are ignored; any CsrAdjacency, no plan is used).
     Differentiable in x (the same kernel on the transposed pattern) and in values (sddmm_heads)."""
-    if not isinstance(adj, CsrAdjacency):
-        raise TypeError("spmm_heads: adj must be a CsrAdjacency")
+    _check_adj(adj, "spmm_heads")
     if not isinstance(values, torch.Tensor) or values.dim() != 2 or values.shape[0] != adj.nnz or values.shape[1] < 1:
         raise ValueError(f"spmm_heads: values must be a 2-D tensor [nnz = {adj.nnz}, H] in CSR order")
     heads = int(values.shape[1])
@@ -366,8 +317,7 @@ def sddmm_heads(adj, a, b, heads):
     """s[e, h] = sum over j < F of a[row(e), hF + j] * b[col[e], hF + j] for every stored entry e of adj: per-head dot-product
     scores (gcn_sddmm_heads_csr_f32).  a: [m, H*F], b: [n, H*F] fp32; returns [nnz, H] in adj's CSR order.  Differentiable in
     a and b (spmm_heads on the pattern and on its transpose)."""
-    if not isinstance(adj, CsrAdjacency):
-        raise TypeError("sddmm_heads: adj must be a CsrAdjacency")
+    _check_adj(adj, "sddmm_heads")
     heads = int(heads)
     if heads < 1:
         raise ValueError("sddmm_heads: heads must be at least 1")
@@ -380,22 +330,10 @@ def sddmm_heads(adj, a, b, heads):
 
 
 # ---- GATv2 scores (gcn_amd/csrc/multihead.hip) -------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _gatv2_ws_need(nnz, heads, k):
-    need = ctypes.c_size_t(0)
-    _lib.check(_lib.load().gcn_gatv2_ws_bytes(0, nnz, heads, k, ctypes.byref(need)), "gcn_gatv2_ws_bytes")
-    return need.value
-
-
-def _gatv2_workspace(adj, device, heads, k):
-    """the scratch of the three GATv2 calls (gcn_gatv2_ws_bytes: a flag and the chunk partials of the backward's two sums),
-    kept on the adjacency like _workspace's and allocated at the first forward, so before a capture"""
-    need = _gatv2_ws_need(int(adj.nnz), int(heads), int(k))
-    ws = getattr(adj, "_gatv2_ws", None)
-    if ws is None or ws.numel() < need or ws.device != device:
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
-        adj._gatv2_ws = ws
-    return ws
+def _gatv2_scratch(adj, device, heads, k):
+    """the "gatv2" buffer of the adjacency, for the three GATv2 calls (gcn_gatv2_ws_bytes: a flag and the chunk partials of
+    the backward's two sums): allocated at the first forward, so before a capture"""
+    return adj._scratch.get("gatv2", _ws_need("gcn_gatv2_ws_bytes", int(adj.nnz), int(heads), int(k)), device)
 
 
 def _gatv2_backward_raw(adj, rowptr, idx, perm, rows, own, other, att, slope, g, want_act):
@@ -405,13 +343,9 @@ def _gatv2_backward_raw(adj, rowptr, idx, perm, rows, own, other, att, slope, g,
     act = torch.empty(rows, k, dtype=torch.float32, device=own.device) if want_act else None
     if rows == 0 or adj.nnz == 0:
         return grad.zero_(), (act.zero_() if want_act else None)
-    ws = _gatv2_workspace(adj, own.device, heads, k)
-    with torch.cuda.device(own.device):
-        st = _lib.load().gcn_gatv2_scores_backward_csr_f32(
-            _ptr(rowptr), _ptr(idx), _ptr(perm) if perm is not None else None, rows, adj.nnz, heads, k, _ptr(own), _ptr(other),
-            _ptr(att), slope, _ptr(g), _ptr(grad), _ptr(act) if want_act else None, _ptr(ws), ws.numel(),
-            _stream_ptr(own.device))
-    _lib.check(st, "gcn_gatv2_scores_backward_csr_f32")
+    ws = _gatv2_scratch(adj, own.device, heads, k)
+    call("gcn_gatv2_scores_backward_csr_f32", rowptr, idx, perm, rows, adj.nnz, heads, k, own, other, att, slope, g, grad, act,
+         ws, ws.numel(), device=own.device)
     return grad, act
 
 
@@ -425,12 +359,9 @@ class _Gatv2ScoresFunction(torch.autograd.Function):
         heads, k = int(a.shape[0]), int(hd.shape[1])
         out = torch.empty(adj.nnz, heads, dtype=torch.float32, device=hd.device)
         if adj.m and adj.nnz:
-            ws = _gatv2_workspace(adj, hd.device, heads, k)
-            with torch.cuda.device(hd.device):
-                st = _lib.load().gcn_gatv2_scores_csr_f32(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, heads, k, _ptr(hd),
-                                                          _ptr(hs), _ptr(a), slope, _ptr(out), _ptr(ws), ws.numel(),
-                                                          _stream_ptr(hd.device))
-            _lib.check(st, "gcn_gatv2_scores_csr_f32")
+            ws = _gatv2_scratch(adj, hd.device, heads, k)
+            call("gcn_gatv2_scores_csr_f32", adj.rowptr, adj.col, adj.m, adj.nnz, heads, k, hd, hs, a, slope, out, ws, ws.numel(),
+                 device=hd.device)
         ctx.adj, ctx.slope = adj, slope
         ctx.save_for_backward(hd, hs, a)
         return out
@@ -450,7 +381,7 @@ class _Gatv2ScoresFunction(torch.autograd.Function):
             if not need_dst:
                 g_dst = None
         if need_src:
-            trp, trow, tperm = _heads_tpattern(adj)
+            trp, trow, tperm = adj.tpattern()
             g_src, _ = _gatv2_backward_raw(adj, trp, trow, tperm, adj.n, hs, hd, a, ctx.slope, g, False)
         return None, g_dst, g_src, g_att, None
 
@@ -463,8 +394,7 @@ def gatv2_scores(adj, h_dst, h_src, att, negative_slope=0.2):
     square or rectangular; its values are ignored.  Differentiable in all three operands (two row walks, on the pattern and
     on its transpose, and one [m, H*F] column sum); the same tensor may be passed as h_dst and h_src.  The derivative of
     leaky_relu at 0 is the slope."""
-    if not isinstance(adj, CsrAdjacency):
-        raise TypeError("gatv2_scores: adj must be a CsrAdjacency")
+    _check_adj(adj, "gatv2_scores")
     if not isinstance(att, torch.Tensor) or att.dim() != 2 or att.shape[0] < 1 or att.shape[1] < 1:
         raise ValueError("gatv2_scores: att must be a 2-D tensor [H, F]")
     heads, k = int(att.shape[0]), int(att.shape[0]) * int(att.shape[1])

@@ -15,7 +15,8 @@ import torch
 
 from . import _lib
 from .construct import _bucket, _check_ids, _check_size, _transpose_arrays
-from .spmm import CsrAdjacency, _ptr, _stream_ptr
+from ._lib import call
+from .spmm import CsrAdjacency
 
 REDUCE = {"sum": _lib.COALESCE_SUM, "max": _lib.COALESCE_MAX, "min": _lib.COALESCE_MIN, "first": _lib.COALESCE_FIRST}
 DIAGONAL = {"keep": _lib.DIAG_KEEP, "drop": _lib.DIAG_DROP, "fill": _lib.DIAG_FILL, "add": _lib.DIAG_ADD}
@@ -41,26 +42,20 @@ def _coalesce(rowptr, col, val, m, n, reduce, diagonal, diag_value, want_seg=Tru
     nnz = int(col.numel())
     if nnz + min(m, n) >= 2 ** 31:
         raise ValueError("coalesce: the merged matrix must hold fewer than 2^31 entries")
-    lib = _lib.load()
     ws = torch.empty(_lib.COALESCE_WS_BYTES, dtype=torch.uint8, device=dev)
     out_rowptr = torch.zeros(m + 1, dtype=torch.int32, device=dev)
     if m > 0:
-        with torch.cuda.device(dev):
-            st = lib.gcn_csr_coalesce_count(_ptr(rowptr), _ptr(col) if nnz else None, m, n, nnz, diagonal, _ptr(out_rowptr[1:]),
-                                            _ptr(ws), ws.numel(), _stream_ptr(dev))
-        _lib.check(st, "gcn_csr_coalesce_count")
+        call("gcn_csr_coalesce_count", rowptr, col if nnz else None, m, n, nnz, diagonal, out_rowptr[1:], ws, ws.numel(),
+             device=dev)
         out_rowptr.cumsum_(0)                              # (the total is below 2^31: int32 holds every partial sum)
     total = int(out_rowptr[-1])                            # the one synchronisation
     out_col = torch.empty(total, dtype=torch.int32, device=dev)
     out_val = torch.empty(total, dtype=torch.float32, device=dev) if val is not None else None
     seg = torch.full((nnz,), -1, dtype=torch.int32, device=dev) if want_seg else None
     if total > 0:
-        with torch.cuda.device(dev):
-            st = lib.gcn_csr_coalesce_fill(_ptr(rowptr), _ptr(col) if nnz else None, _ptr(val) if val is not None and nnz else None,
-                                           m, n, nnz, reduce, diagonal, float(diag_value), _ptr(out_rowptr), _ptr(out_col),
-                                           _ptr(out_val) if val is not None and nnz else None, None,
-                                           _ptr(seg) if want_seg and nnz else None, _ptr(ws), ws.numel(), _stream_ptr(dev))
-        _lib.check(st, "gcn_csr_coalesce_fill")
+        call("gcn_csr_coalesce_fill", rowptr, col if nnz else None, val if nnz else None, m, n, nnz, reduce, diagonal,
+             float(diag_value), out_rowptr, out_col, out_val if nnz else None, None, seg if nnz else None, ws, ws.numel(),
+             device=dev)
         if val is not None and nnz == 0:                   # (only inserted diagonals: no input values to hand to the call)
             out_val.fill_(float(diag_value))
     return out_rowptr, out_col, out_val, seg
@@ -153,16 +148,11 @@ def _normalized_values(rowptr, col, val, m, n, mode):
     """fp32 [nnz]: the degrees (fp64 row sums of val, row lengths for val None) and the scaled values, two calls"""
     dev = rowptr.device
     nnz = int(col.numel())
-    lib = _lib.load()
     deg = torch.zeros(m, dtype=torch.float64, device=dev)
     out = torch.empty(nnz, dtype=torch.float32, device=dev)
     if m > 0 and nnz > 0:
-        with torch.cuda.device(dev):
-            st = lib.gcn_csr_degree_f64(_ptr(rowptr), _ptr(val) if val is not None else None, m, nnz, _ptr(deg), _stream_ptr(dev))
-            _lib.check(st, "gcn_csr_degree_f64")
-            st = lib.gcn_csr_normalize_f32(_ptr(rowptr), _ptr(col), _ptr(val) if val is not None else None, m, n, nnz, _ptr(deg),
-                                           mode, _ptr(out), _stream_ptr(dev))
-            _lib.check(st, "gcn_csr_normalize_f32")
+        call("gcn_csr_degree_f64", rowptr, val, m, nnz, deg, device=dev)
+        call("gcn_csr_normalize_f32", rowptr, col, val, m, n, nnz, deg, mode, out, device=dev)
     return out
 
 

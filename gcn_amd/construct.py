@@ -12,7 +12,8 @@ CPU path: CPU tensors raise.
 import torch
 
 from . import _lib
-from .spmm import CsrAdjacency, _ptr, _stream_ptr
+from ._lib import call
+from .spmm import CsrAdjacency
 
 
 def _check_ids(ids, name, what):
@@ -32,17 +33,11 @@ def _bucket(keys32, nbuckets):
     count = int(keys32.numel())
     offsets = torch.empty(nbuckets + 1, dtype=torch.int32, device=dev)
     perm = torch.empty(count, dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = lib.gcn_bucket_count_i32(_ptr(keys32), count, nbuckets, _ptr(offsets), _stream_ptr(dev))
-    _lib.check(st, "gcn_bucket_count_i32")
+    call("gcn_bucket_count_i32", keys32, count, nbuckets, offsets, device=dev)
     offsets.cumsum_(0)                                     # (the total is count < 2^31: int32 holds every partial sum)
     if count > 0 and nbuckets > 0:
         ws = torch.empty(_lib.bucket_ws_bytes(count, nbuckets), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            st = lib.gcn_bucket_fill_i32(_ptr(keys32), count, nbuckets, _ptr(offsets), _ptr(perm), _ptr(ws), ws.numel(),
-                                         _stream_ptr(dev))
-        _lib.check(st, "gcn_bucket_fill_i32")
+        call("gcn_bucket_fill_i32", keys32, count, nbuckets, offsets, perm, ws, ws.numel(), device=dev)
     return offsets, perm
 
 
@@ -76,11 +71,8 @@ def _transpose_arrays(adj, with_values=True):
     trow = torch.empty(adj.nnz, dtype=torch.int32, device=dev)
     tval = torch.empty(adj.nnz, dtype=torch.float32, device=dev) if with_values else None
     if adj.nnz > 0:
-        with torch.cuda.device(dev):
-            st = _lib.load().gcn_csr_transpose_gather(_ptr(adj.rowptr), adj.m, adj.nnz, _ptr(eid),
-                                                      _ptr(adj.val) if with_values else None, _ptr(trow),
-                                                      _ptr(tval) if with_values else None, _stream_ptr(dev))
-        _lib.check(st, "gcn_csr_transpose_gather")
+        call("gcn_csr_transpose_gather", adj.rowptr, adj.m, adj.nnz, eid, adj.val if with_values else None, trow, tval,
+             device=dev)
     return trp, trow, tval, eid
 
 

@@ -14,7 +14,8 @@ import torch
 
 from . import _lib
 from .construct import transpose_csr
-from .spmm import CsrAdjacency, _ptr, _stream_ptr
+from ._lib import call
+from .spmm import CsrAdjacency
 
 KNN_K_MAX = _lib.KNN_K_MAX
 
@@ -37,15 +38,11 @@ def _knn(x, y, k, self_offset, splits, want_dist2=True, want_sum=False):
         return idx, dist2, rsum
     x, ldx = _rows(x.detach(), d)
     y, ldy = _rows(y.detach(), d)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.gcn_knn_ws_bytes(q, n, k, splits, ctypes.byref(nbytes)), "gcn_knn_ws_bytes")
-        ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
-        st = lib.gcn_knn_f32(_ptr(x), ldx, _ptr(y), ldy, q, n, d, k, self_offset, splits, _ptr(idx),
-                             _ptr(dist2) if want_dist2 else None, _ptr(rsum) if want_sum else None, _ptr(ws), ws.numel(),
-                             _stream_ptr(dev))
-    _lib.check(st, "gcn_knn_f32")
+    nbytes = ctypes.c_size_t(0)
+    with torch.cuda.device(dev):                           # (the rule counts the CUs of the current device)
+        call("gcn_knn_ws_bytes", q, n, k, splits, ctypes.byref(nbytes))
+    ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+    call("gcn_knn_f32", x, ldx, y, ldy, q, n, d, k, self_offset, splits, idx, dist2, rsum, ws, ws.numel(), device=dev)
     return idx, dist2, rsum
 
 

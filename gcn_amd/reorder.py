@@ -103,10 +103,8 @@ def order_deg_device(rowptr, col, which="total", desc=True):
     if rowptr.is_cuda:                      # the library's device kernels (reorder_device.hip)
         rp, ci = rowptr.to(torch.int32).contiguous(), col.to(torch.int32).contiguous()
         rank = torch.empty(n, dtype=torch.int32, device=rowptr.device)
-        _lib.check(_lib.load().gcn_order_deg_device(
-            ctypes.c_void_p(rp.data_ptr()), ctypes.c_void_p(ci.data_ptr()), n, int(ci.numel()),
-            {"total": 0, "out": 1, "in": 2}[which], int(bool(desc)), ctypes.c_void_p(rank.data_ptr()),
-            ctypes.c_void_p(torch.cuda.current_stream(rowptr.device).cuda_stream)), "gcn_order_deg_device")
+        _lib.call("gcn_order_deg_device", rp, ci, n, int(ci.numel()), {"total": 0, "out": 1, "in": 2}[which], int(bool(desc)),
+                  rank, device=rowptr.device)
         return rank.to(torch.int64)
     out_deg = (rowptr[1:] - rowptr[:-1]).to(torch.int64)
     in_deg = torch.bincount(col.to(torch.int64), minlength=n)
@@ -130,10 +128,8 @@ def order_rcm_device(rowptr, col, return_levels=False):
     rp, ci = rowptr.to(torch.int32).contiguous(), col.to(torch.int32).contiguous()
     rank = torch.empty(n, dtype=torch.int32, device=rowptr.device)
     levels = ctypes.c_int32(0)
-    _lib.check(_lib.load().gcn_order_rcm_device(
-        ctypes.c_void_p(rp.data_ptr()), ctypes.c_void_p(ci.data_ptr()), n, int(ci.numel()),
-        ctypes.c_void_p(rank.data_ptr()), ctypes.cast(ctypes.byref(levels), ctypes.c_void_p),
-        ctypes.c_void_p(torch.cuda.current_stream(rowptr.device).cuda_stream)), "gcn_order_rcm_device")
+    _lib.call("gcn_order_rcm_device", rp, ci, n, int(ci.numel()), rank, ctypes.cast(ctypes.byref(levels), ctypes.c_void_p),
+              device=rowptr.device)
     rank = rank.to(torch.int64)
     return (rank, int(levels.value)) if return_levels else rank
 
@@ -157,10 +153,7 @@ def apply_rank_device(rowptr, col, vals, rank):
     o_ci = torch.empty(nnz, dtype=torch.int32, device=d)
     o_va = torch.empty(nnz, dtype=torch.float32, device=d)
     vomp = torch.empty(n, dtype=torch.int32, device=d)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    _lib.check(_lib.load().gcn_csr_apply_rank_device(p(rp), p(ci), p(va), p(rk), n, nnz, p(o_rp), p(o_ci), p(o_va),
-                                                     p(vomp), ctypes.c_void_p(torch.cuda.current_stream(d).cuda_stream)),
-               "gcn_csr_apply_rank_device")
+    _lib.call("gcn_csr_apply_rank_device", rp, ci, va, rk, n, nnz, o_rp, o_ci, o_va, vomp, device=d)
     return o_rp, o_ci, o_va, vomp
 
 
@@ -191,12 +184,8 @@ def order_rabbit_device(rowptr, col, return_communities=False, return_stats=Fals
     rank = torch.empty(n, dtype=torch.int32, device=rowptr.device)
     comm = torch.empty(n, dtype=torch.int32, device=rowptr.device) if return_communities else None
     stats = (ctypes.c_int64 * 8)()
-    with torch.cuda.device(rowptr.device):
-        _lib.check(_lib.load().gcn_order_rabbit_device(
-            ctypes.c_void_p(rp.data_ptr()), ctypes.c_void_p(ci.data_ptr()), n, int(ci.numel()),
-            ctypes.c_void_p(rank.data_ptr()), ctypes.c_void_p(comm.data_ptr()) if comm is not None else None,
-            ctypes.cast(stats, ctypes.c_void_p), ctypes.c_void_p(torch.cuda.current_stream(rowptr.device).cuda_stream)),
-            "gcn_order_rabbit_device")
+    _lib.call("gcn_order_rabbit_device", rp, ci, n, int(ci.numel()), rank, comm, ctypes.cast(stats, ctypes.c_void_p),
+              device=rowptr.device)
     out = [rank.to(torch.int64)]
     if return_communities:
         out.append(comm.to(torch.int64))

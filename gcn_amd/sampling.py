@@ -22,7 +22,8 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from .spmm import CsrAdjacency, _ptr, _stream_ptr
+from ._lib import call
+from .spmm import CsrAdjacency
 
 Block = namedtuple("Block", ["adj", "eid", "src_ids", "num_dst"])
 Block.__doc__ = """One hop of a sampled mini-batch, a bipartite graph from ``src_ids`` to its first ``num_dst`` vertices.
@@ -48,13 +49,6 @@ def _check_stream(seed, offset, what):
     for name, v in (("seed", seed), ("offset", offset)):
         if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 64:
             raise ValueError(f"{what}: {name} must be an int in [0, 2^64), not {v!r}")
-
-
-def _workspace(adj):
-    ws = getattr(adj, "_sample_ws", None)
-    if ws is None:
-        ws = adj._sample_ws = torch.empty(_lib.SAMPLE_WS_BYTES, dtype=torch.uint8, device=adj.device)
-    return ws
 
 
 def sample_neighbors(adj, seeds, fanout, seed=0, offset=0):
@@ -95,12 +89,9 @@ def sample_neighbors(adj, seeds, fanout, seed=0, offset=0):
     out_col = torch.empty(total, dtype=torch.int32, device=dev)
     out_eid = torch.empty(total, dtype=torch.int32, device=dev)
     s32 = seeds.to(torch.int32).contiguous()
-    ws = _workspace(adj)
-    with torch.cuda.device(dev):
-        st = _lib.load().gcn_sample_neighbors_csr(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, _ptr(s32), ns, int(fanout),
-                                                  int(seed), int(offset), _ptr(out_rowptr), _ptr(out_col), _ptr(out_eid),
-                                                  _ptr(ws), ws.numel(), _stream_ptr(dev))
-    _lib.check(st, "gcn_sample_neighbors_csr")
+    ws = adj._scratch.get("sample", _lib.SAMPLE_WS_BYTES, adj.device)
+    call("gcn_sample_neighbors_csr", adj.rowptr, adj.col, adj.m, adj.nnz, s32, ns, int(fanout), int(seed), int(offset),
+         out_rowptr, out_col, out_eid, ws, ws.numel(), device=dev)
     return out_rowptr, out_col, out_eid
 
 

@@ -17,12 +17,13 @@ import torch
 from . import _lib
 from .coalesce import _check_adj, _entry_rows, coalesce_csr
 from .construct import transpose_csr
-from .spmm import CsrAdjacency, _ptr, _stream_ptr
+from ._lib import call
+from .spmm import CsrAdjacency
 
 
-def _ws_bytes(lib, m, n):
+def _ws_bytes(m, n):
     out = ctypes.c_size_t(0)
-    _lib.check(lib.gcn_spgemm_ws_bytes(m, n, ctypes.byref(out)), "gcn_spgemm_ws_bytes")
+    call("gcn_spgemm_ws_bytes", m, n, ctypes.byref(out))
     return int(out.value)
 
 
@@ -32,15 +33,11 @@ def _spgemm(a, b, bad=None, refusal=None):
     read together with the total (no second synchronisation); ValueError(refusal) before the fill when it is not zero"""
     dev = a.device
     m, p, n = a.m, a.n, b.n
-    lib = _lib.load()
     out_len = torch.zeros(m, dtype=torch.int32, device=dev)
     ws = None
     if m > 0 and a.nnz > 0 and b.nnz > 0 and n > 0:
-        ws = torch.empty(_ws_bytes(lib, m, n), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            st = lib.gcn_spgemm_count_csr(_ptr(a.rowptr), _ptr(a.col), m, p, a.nnz, _ptr(b.rowptr), _ptr(b.col), n, b.nnz,
-                                          _ptr(out_len), _ptr(ws), ws.numel(), _stream_ptr(dev))
-        _lib.check(st, "gcn_spgemm_count_csr")
+        ws = torch.empty(_ws_bytes(m, n), dtype=torch.uint8, device=dev)
+        call("gcn_spgemm_count_csr", a.rowptr, a.col, m, p, a.nnz, b.rowptr, b.col, n, b.nnz, out_len, ws, ws.numel(), device=dev)
     scan = torch.zeros(m + 1, dtype=torch.int64, device=dev)
     scan[1:] = out_len.cumsum(0, dtype=torch.int64)
     if bad is None:
@@ -55,11 +52,8 @@ def _spgemm(a, b, bad=None, refusal=None):
     out_col = torch.empty(total, dtype=torch.int32, device=dev)
     out_val = torch.empty(total, dtype=torch.float32, device=dev)
     if total > 0:
-        with torch.cuda.device(dev):
-            st = lib.gcn_spgemm_fill_csr(_ptr(a.rowptr), _ptr(a.col), _ptr(a.val), m, p, a.nnz, _ptr(b.rowptr), _ptr(b.col),
-                                         _ptr(b.val), n, b.nnz, _ptr(out_rowptr), _ptr(out_col), _ptr(out_val), _ptr(ws),
-                                         ws.numel(), _stream_ptr(dev))
-        _lib.check(st, "gcn_spgemm_fill_csr")
+        call("gcn_spgemm_fill_csr", a.rowptr, a.col, a.val, m, p, a.nnz, b.rowptr, b.col, b.val, n, b.nnz, out_rowptr, out_col,
+             out_val, ws, ws.numel(), device=dev)
     return out_rowptr, out_col, out_val
 
 
@@ -101,9 +95,7 @@ def _degree(adj, val):
     """fp64 [adj.m]: the row sums of val (fp32 [nnz]) over adj's rows, in fp64 and in a fixed order"""
     deg = torch.zeros(adj.m, dtype=torch.float64, device=adj.device)
     if adj.m > 0 and adj.nnz > 0:
-        with torch.cuda.device(adj.device):
-            st = _lib.load().gcn_csr_degree_f64(_ptr(adj.rowptr), _ptr(val), adj.m, adj.nnz, _ptr(deg), _stream_ptr(adj.device))
-        _lib.check(st, "gcn_csr_degree_f64")
+        call("gcn_csr_degree_f64", adj.rowptr, val, adj.m, adj.nnz, deg, device=adj.device)
     return deg
 
 
@@ -167,13 +159,10 @@ def _sampled_dot(pattern, x, xv, y, yv, x_by_col):
     if pattern.m == 0 or pattern.nnz == 0:
         return out
     ws = torch.empty(_lib.SAMPLED_DOT_WS_BYTES, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.load().gcn_csr_sampled_dot_f32(
-            _ptr(pattern.rowptr), _ptr(pattern.col), pattern.m, pattern.n, pattern.nnz,
-            _ptr(x.rowptr), _ptr(x.col) if x.nnz else None, _ptr(xv) if xv is not None and x.nnz else None, x.nnz,
-            _ptr(y.rowptr), _ptr(y.col) if y.nnz else None, _ptr(yv) if yv is not None and y.nnz else None, y.nnz,
-            x.n, 1 if x_by_col else 0, _ptr(out), _ptr(ws), ws.numel(), _stream_ptr(dev))
-    _lib.check(st, "gcn_csr_sampled_dot_f32")
+    call("gcn_csr_sampled_dot_f32", pattern.rowptr, pattern.col, pattern.m, pattern.n, pattern.nnz,
+         x.rowptr, x.col if x.nnz else None, xv if x.nnz else None, x.nnz,
+         y.rowptr, y.col if y.nnz else None, yv if y.nnz else None, y.nnz,
+         x.n, 1 if x_by_col else 0, out, ws, ws.numel(), device=dev)
     return out
 
 

@@ -22,14 +22,25 @@ import weakref
 import torch
 
 from . import _lib
+from ._lib import _ptr, _stream_ptr, call  # noqa: F401  (the two pointer helpers: tools import them from here)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+class Scratch:
+    """Device scratch by kind: one uint8 buffer per kind, allocated at the first call that needs it (so before a capture),
+    replaced only when a call needs more bytes or another device, never shrunk.  A replaced buffer goes onto ``retired``
+    and stays allocated: a captured step recorded its address and goes on writing its flag and partials there at every
+    replay.  Kinds are separate buffers, so two units of one owner may run on two streams."""
 
+    def __init__(self):
+        self.buffers, self.retired = {}, []
 
-def _stream_ptr(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    def get(self, kind, nbytes, device):
+        ws = self.buffers.get(kind)
+        if ws is None or ws.numel() < nbytes or ws.device != device:
+            if ws is not None:
+                self.retired.append(ws)
+            ws = self.buffers[kind] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return ws
 
 
 class CsrAdjacency:
@@ -66,8 +77,9 @@ class CsrAdjacency:
             self.panels = 0
         self._plan = None
         self._transpose = None
-        self._tperm = None           # mutable transpose: its values are self.val[_tperm]
-        self._tstale = False         # ... once refreshed: update_values has changed self.val since
+        self._tstale = False         # the mutable transpose needs a refresh: update_values has changed self.val since
+        self._tpattern = None        # tpattern(): the one copy every backward walk and the mutable transpose read
+        self._scratch = Scratch()    # the workspaces of the plan-free units, by kind: edge, gatv2, aggregate, sample
         self.values_version = 0      # counts update_values calls: a backward that reads the values checks it has not moved
         self.device = self.val.device
 
@@ -97,19 +109,13 @@ class CsrAdjacency:
     @property
     def plan(self):
         if self._plan is None:
-            lib = _lib.load()
             handle = ctypes.c_void_p()
-            with torch.cuda.device(self.device):
-                st = lib.gcn_spmm_plan_create(ctypes.byref(handle), _ptr(self.rowptr), self.m, self.n,
-                                              self.nnz, self.chunk_nnz, _stream_ptr(self.device))
-            _lib.check(st, "gcn_spmm_plan_create")
+            call("gcn_spmm_plan_create", ctypes.byref(handle), self.rowptr, self.m, self.n, self.nnz, self.chunk_nnz,
+                 device=self.device)
             self._plan = handle
             weakref.finalize(self, _destroy_plan, handle)
             if self.mutable_values:                  # (before the slicing: it is built once, as a weighted plan)
-                with torch.cuda.device(self.device):
-                    st = lib.gcn_spmm_plan_set_values_mutable(handle, _ptr(self.rowptr), _ptr(self.col), _ptr(self.val),
-                                                              _stream_ptr(self.device))
-                _lib.check(st, "gcn_spmm_plan_set_values_mutable")
+                call("gcn_spmm_plan_set_values_mutable", handle, self.rowptr, self.col, self.val, device=self.device)
             if self.panels != 0:
                 self.enable_panels(self.panels)
             if self.slices not in (0, 1) and self.panel_rows == 0:
@@ -126,32 +132,24 @@ class CsrAdjacency:
 
     def set_tile_cols(self, cols):
         """Feature-column tile per kernel pass (0 auto, 64, 128, 256)."""
-        _lib.check(_lib.load().gcn_spmm_plan_set_tile_cols(self.plan, int(cols)), "gcn_spmm_plan_set_tile_cols")
+        call("gcn_spmm_plan_set_tile_cols", self.plan, int(cols))
 
     def set_gather_width(self, nz_per_gather):
         """Non-zeros per gather instruction of the 64-column kernel: 0 auto, 1 or 4."""
-        _lib.check(_lib.load().gcn_spmm_plan_set_gather_width(self.plan, int(nz_per_gather)),
-                   "gcn_spmm_plan_set_gather_width")
+        call("gcn_spmm_plan_set_gather_width", self.plan, int(nz_per_gather))
 
     def set_blocks_per_cu(self, blocks):
         """Main-kernel grid in blocks of 4 waves per CU (1..64, default 32 = oversubscribed); below the
         resident count (8, or 4 for the four-per-gather kernel) it leaves room for a concurrent kernel."""
-        _lib.check(_lib.load().gcn_spmm_plan_set_blocks_per_cu(self.plan, int(blocks)),
-                   "gcn_spmm_plan_set_blocks_per_cu")
+        call("gcn_spmm_plan_set_blocks_per_cu", self.plan, int(blocks))
 
     def prepare_width(self, k):
         """Build now whatever a k-wide call would build at first use (gcn_spmm_plan_prepare_width): e.g. before a capture."""
-        with torch.cuda.device(self.device):
-            st = _lib.load().gcn_spmm_plan_prepare_width(self.plan, _ptr(self.rowptr), _ptr(self.col), _ptr(self.val), int(k),
-                                                         _stream_ptr(self.device))
-        _lib.check(st, "gcn_spmm_plan_prepare_width")
+        call("gcn_spmm_plan_prepare_width", self.plan, self.rowptr, self.col, self.val, int(k), device=self.device)
 
     def enable_panels(self, mode):
         """LDS-staged row panels (gcn_spmm_plan_enable_panels): 0 off, 1 on, -1 automatic."""
-        with torch.cuda.device(self.device):
-            st = _lib.load().gcn_spmm_plan_enable_panels(self.plan, _ptr(self.rowptr), _ptr(self.col),
-                                                         _ptr(self.val), int(mode), _stream_ptr(self.device))
-        _lib.check(st, "gcn_spmm_plan_enable_panels")
+        call("gcn_spmm_plan_enable_panels", self.plan, self.rowptr, self.col, self.val, int(mode), device=self.device)
 
     @property
     def panel_rows(self):
@@ -168,27 +166,19 @@ class CsrAdjacency:
 
     def enable_slicing(self, slices):
         """XCD-aware column slicing (gcn_spmm_plan_enable_slicing): 0/1 off, -1 automatic."""
-        with torch.cuda.device(self.device):
-            st = _lib.load().gcn_spmm_plan_enable_slicing(self.plan, _ptr(self.rowptr), _ptr(self.col),
-                                                          _ptr(self.val), int(slices), _stream_ptr(self.device))
-        _lib.check(st, "gcn_spmm_plan_enable_slicing")
+        call("gcn_spmm_plan_enable_slicing", self.plan, self.rowptr, self.col, self.val, int(slices), device=self.device)
 
     def set_value_factors(self, u_row, u_col):
         """Declare val[r, c] == u_row[r] * u_col[c] (checked on the device; GcnAmdError if an entry does not
         factor): lets the sliced main pass run without its value stream.  Square normalised adjacencies
         are detected automatically; this is for row blocks / renumbered columns.  (None, None) forgets."""
         if u_row is None and u_col is None:
-            _lib.check(_lib.load().gcn_spmm_plan_set_value_factors(self.plan, None, None, None, None, None,
-                                                                   _stream_ptr(self.device)), "gcn_spmm_plan_set_value_factors")
-            return
+            return call("gcn_spmm_plan_set_value_factors", self.plan, None, None, None, None, None, device=self.device)
         ur = u_row.to(device=self.device, dtype=torch.float32).contiguous()
         uc = u_col.to(device=self.device, dtype=torch.float32).contiguous()
         if ur.numel() != self.m or uc.numel() != self.n:
             raise ValueError("u_row needs m entries and u_col n entries")
-        with torch.cuda.device(self.device):
-            st = _lib.load().gcn_spmm_plan_set_value_factors(self.plan, _ptr(self.rowptr), _ptr(self.col), _ptr(self.val),
-                                                             _ptr(ur), _ptr(uc), _stream_ptr(self.device))
-        _lib.check(st, "gcn_spmm_plan_set_value_factors")
+        call("gcn_spmm_plan_set_value_factors", self.plan, self.rowptr, self.col, self.val, ur, uc, device=self.device)
 
     @property
     def has_value_factors(self):
@@ -218,8 +208,9 @@ class CsrAdjacency:
         S, w, ld = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
         rows = ctypes.c_int64(0)
         vp = lambda x: ctypes.cast(ctypes.byref(x), ctypes.c_void_p)
-        st = _lib.load().gcn_spmm_plan_prelaid_layout(self.plan, int(k), vp(S), vp(w), vp(rows), vp(ld))
-        if st != 0:
+        try:
+            call("gcn_spmm_plan_prelaid_layout", self.plan, int(k), vp(S), vp(w), vp(rows), vp(ld))
+        except _lib.GcnAmdError:
             return None
         return dict(slices=S.value, slice_cols=w.value, table_rows=rows.value, ld=ld.value)
 
@@ -247,16 +238,11 @@ class CsrAdjacency:
         need = self.m + (self.m - 1) // out_gap if (out_gap and self.m) else self.m
         if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] >= need):
             raise ValueError("out must be a contiguous fp32 array with room for every (gapped) row")
-        sp = ctypes.c_void_p()
-        if out_scale is not None:
-            if not (out_scale.is_cuda and out_scale.dtype == torch.float32 and out_scale.is_contiguous()
-                    and out_scale.numel() == self.m):
-                raise ValueError("out_scale must be a contiguous fp32 device vector with m entries")
-            sp = _ptr(out_scale)
-        with torch.cuda.device(self.device):
-            st = _lib.load().gcn_spmm_csr_f32_prelaid(self.plan, _ptr(self.rowptr), _ptr(self.col), _ptr(self.val),
-                                                      _ptr(Bp), _ptr(out), sp, int(out_gap), k, _stream_ptr(self.device))
-        _lib.check(st, "gcn_spmm_csr_f32_prelaid")
+        if out_scale is not None and not (out_scale.is_cuda and out_scale.dtype == torch.float32 and out_scale.is_contiguous()
+                                          and out_scale.numel() == self.m):
+            raise ValueError("out_scale must be a contiguous fp32 device vector with m entries")
+        call("gcn_spmm_csr_f32_prelaid", self.plan, self.rowptr, self.col, self.val, Bp, out, out_scale, int(out_gap), k,
+             device=self.device)
         return out
 
     def autotune(self, k=128, reps=3, verbose=False):
@@ -306,21 +292,19 @@ class CsrAdjacency:
             raise _lib.GcnAmdError(f"no SpMM for {dtype} operands (fp32 and bf16 only)")
         fn = "gcn_spmm_plan_main_kernel_bf16" if dtype == torch.bfloat16 else "gcn_spmm_plan_main_kernel"
         buf = ctypes.create_string_buffer(128)
-        _lib.check(getattr(_lib.load(), fn)(self.plan, int(k), int(bool(epilogue)), buf, 128), fn)
+        call(fn, self.plan, int(k), int(bool(epilogue)), buf, 128)
         return buf.value.decode()
 
     def profile_begin(self, capacity):
         """Record HIP-event pairs around the main kernel of the next `capacity` launches."""
-        _lib.check(_lib.load().gcn_spmm_profile_begin(self.plan, int(capacity)), "gcn_spmm_profile_begin")
+        call("gcn_spmm_profile_begin", self.plan, int(capacity))
         self._prof_cap = int(capacity)
 
     def profile_end(self):
         """→ list of per-launch main-kernel durations in ms (synchronises)."""
         buf = (ctypes.c_float * self._prof_cap)()
         cnt = ctypes.c_int32(0)
-        _lib.check(_lib.load().gcn_spmm_profile_end(self.plan, ctypes.cast(buf, ctypes.c_void_p),
-                                                    ctypes.cast(ctypes.byref(cnt), ctypes.c_void_p)),
-                   "gcn_spmm_profile_end")
+        call("gcn_spmm_profile_end", self.plan, ctypes.cast(buf, ctypes.c_void_p), ctypes.cast(ctypes.byref(cnt), ctypes.c_void_p))
         return [float(buf[i]) for i in range(cnt.value)]
 
     @property
@@ -342,9 +326,7 @@ class CsrAdjacency:
         from them at its next use.  GcnAmdError on an adjacency not made mutable (nothing changes then).
         Increments ``values_version``: the backward of a plain ``spmm(adj, x)`` whose forward saw other values raises."""
         v = self._device_values(val, "update_values")
-        with torch.cuda.device(self.device):
-            st = _lib.load().gcn_spmm_plan_update_values(self.plan, _ptr(v), _stream_ptr(self.device))
-        _lib.check(st, "gcn_spmm_plan_update_values")
+        call("gcn_spmm_plan_update_values", self.plan, v, device=self.device)
         if v.data_ptr() != self.val.data_ptr():
             self.val.copy_(v)
         self._tstale = self._transpose is not None
@@ -369,23 +351,31 @@ class CsrAdjacency:
             out = torch.empty(self.nnz, dtype=torch.float32, device=self.device)
         elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == self.nnz):
             raise ValueError("sddmm: out must be a contiguous fp32 device tensor of nnz entries")
-        with torch.cuda.device(self.device):
-            st = _lib.load().gcn_sddmm_csr_f32(self.plan, _ptr(self.rowptr), _ptr(self.col), _ptr(A), _ptr(B), _ptr(out),
-                                               int(A.shape[1]), _stream_ptr(self.device))
-        _lib.check(st, "gcn_sddmm_csr_f32")
+        call("gcn_sddmm_csr_f32", self.plan, self.rowptr, self.col, A, B, out, int(A.shape[1]), device=self.device)
         return out
 
     def sddmm_kernel(self, k):
         """name of the kernel a k-wide sddmm on this plan launches (gcn_spmm_plan_sddmm_kernel)"""
         buf = ctypes.create_string_buffer(128)
-        _lib.check(_lib.load().gcn_spmm_plan_sddmm_kernel(self.plan, int(k), buf, 128), "gcn_spmm_plan_sddmm_kernel")
+        call("gcn_spmm_plan_sddmm_kernel", self.plan, int(k), buf, 128)
         return buf.value.decode()
 
     def _refresh_transpose(self, values):
-        """re-lay values (nnz, CSR order of this adjacency) into the mutable transpose: values[_tperm]"""
+        """re-lay values (nnz, CSR order of this adjacency) into the mutable transpose: values[tperm]"""
         t = self._mutable_transpose()
-        t.update_values(values.detach().index_select(0, self._tperm))
+        t.update_values(values.detach().index_select(0, self.tpattern()[2]))
         return t
+
+    def tpattern(self):
+        """(trowptr int32 [n+1], trow int32 [nnz], tperm int32 [nnz]) of the transposed pattern, contiguous, built once per
+        adjacency on the device (construct.py) and kept: entry t of the transpose is entry tperm[t] of this adjacency, in
+        row trow[t]; duplicates stay separate entries, in their CSR order.  The one copy the backward walks of aggregate,
+        spmm_heads, sddmm_heads, gatv2_scores and gat_edge_softmax read, and the mutable transpose is built from."""
+        if self._tpattern is None:
+            from .construct import _transpose_arrays
+            trp, trow, _, eid = _transpose_arrays(self, with_values=False)
+            self._tpattern = (trp, trow, eid)
+        return self._tpattern
 
     def _transposed_pattern(self):
         """(rowptr int32 [n+1], row of each entry int32 [nnz], perm int64 [nnz]) of the transposed pattern, built on the
@@ -397,13 +387,12 @@ class CsrAdjacency:
 
     def _mutable_transpose(self):
         """Âᵀ of a mutable adjacency: itself mutable, never Â (a symmetric pattern does not make learned values
-        symmetric); duplicates stay separate entries, so its values are exactly self.val[_tperm]."""
+        symmetric); duplicates stay separate entries, so its values are exactly self.val[tperm] of tpattern(), whose
+        first two arrays are its rowptr and col."""
         if self._transpose is None:
-            trp, trow, perm = self._transposed_pattern()
-            t = CsrAdjacency(trp, trow, self.val[perm], (self.n, self.m),
-                             symmetric=False, chunk_nnz=self.chunk_nnz, mutable_values=True)
-            self._tperm = perm
-            self._transpose = t
+            trp, trow, tperm = self.tpattern()
+            self._transpose = CsrAdjacency(trp, trow, self.val.index_select(0, tperm), (self.n, self.m),
+                                           symmetric=False, chunk_nnz=self.chunk_nnz, mutable_values=True)
         return self._transpose
 
     def transpose(self):
@@ -441,22 +430,16 @@ class CsrAdjacency:
             out = torch.empty((self.m, k), dtype=torch.float32, device=dense.device)
         elif not (out.is_contiguous() and out.shape == (self.m, k) and out.dtype == torch.float32):
             raise ValueError("out must be a contiguous fp32 [m x k] tensor")
-        lib = _lib.load()
-        with torch.cuda.device(self.device):
-            if dropout is not None and float(dropout[0]) > 0.0:
-                bp = _ptr(bias.contiguous()) if bias is not None else ctypes.c_void_p()
-                st = lib.gcn_spmm_csr_f32_epilogue(self.plan, _ptr(self.rowptr), _ptr(self.col), _ptr(self.val),
-                                                   _ptr(dense), _ptr(out), bp, 1 if relu else 0, float(dropout[0]),
-                                                   int(dropout[1]), int(dropout[2]), k, _stream_ptr(self.device))
-            elif bias is None and not relu:
-                st = lib.gcn_spmm_csr_f32(self.plan, _ptr(self.rowptr), _ptr(self.col), _ptr(self.val),
-                                          _ptr(dense), _ptr(out), k, _stream_ptr(self.device))
-            else:
-                bp = _ptr(bias.contiguous()) if bias is not None else ctypes.c_void_p()
-                st = lib.gcn_spmm_csr_f32_bias_relu(self.plan, _ptr(self.rowptr), _ptr(self.col),
-                                                    _ptr(self.val), _ptr(dense), _ptr(out), bp,
-                                                    1 if relu else 0, k, _stream_ptr(self.device))
-        _lib.check(st, "gcn_spmm_csr_f32")
+        if bias is not None:
+            bias = bias.contiguous()
+        if dropout is not None and float(dropout[0]) > 0.0:
+            call("gcn_spmm_csr_f32_epilogue", self.plan, self.rowptr, self.col, self.val, dense, out, bias, 1 if relu else 0,
+                 float(dropout[0]), int(dropout[1]), int(dropout[2]), k, device=self.device)
+        elif bias is None and not relu:
+            call("gcn_spmm_csr_f32", self.plan, self.rowptr, self.col, self.val, dense, out, k, device=self.device)
+        else:
+            call("gcn_spmm_csr_f32_bias_relu", self.plan, self.rowptr, self.col, self.val, dense, out, bias, 1 if relu else 0, k,
+                 device=self.device)
         return out
 
     def _matmul_raw_bf16(self, dense, out, bias, relu, dropout):
@@ -469,12 +452,8 @@ class CsrAdjacency:
             bias = bias.to(dtype=torch.float32).contiguous()       # (the epilogue runs in fp32)
         c_dtype = _lib.DTYPE_BF16 if out.dtype == torch.bfloat16 else _lib.DTYPE_F32
         p, seed, offset = (float(dropout[0]), int(dropout[1]), int(dropout[2])) if dropout is not None else (0.0, 0, 0)
-        bp = _ptr(bias) if bias is not None else ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            st = _lib.load().gcn_spmm_csr_bf16_epilogue(self.plan, _ptr(self.rowptr), _ptr(self.col), _ptr(self.val),
-                                                        _ptr(dense), _ptr(out), c_dtype, bp, 1 if relu else 0,
-                                                        p if p > 0.0 else 0.0, seed, offset, k, _stream_ptr(self.device))
-        _lib.check(st, "gcn_spmm_csr_bf16_epilogue")
+        call("gcn_spmm_csr_bf16_epilogue", self.plan, self.rowptr, self.col, self.val, dense, out, c_dtype, bias, 1 if relu else 0,
+             p if p > 0.0 else 0.0, seed, offset, k, device=self.device)
         return out
 
 
@@ -493,7 +472,7 @@ def _check_values_version(adj, seen, what):
 
 def _destroy_plan(handle):
     try:
-        _lib.load().gcn_spmm_plan_destroy(handle)
+        call("gcn_spmm_plan_destroy", handle)
     except Exception:  # interpreter shutdown
         pass
 
@@ -699,10 +678,7 @@ def gather_rows(src, idx, out=None):
     nrows, k = int(idx.numel()), int(src.shape[1])
     if out is None:
         out = torch.empty((nrows, k), dtype=torch.float32, device=src.device)
-    with torch.cuda.device(src.device):
-        st = _lib.load().gcn_gather_rows_f32(_ptr(out), _ptr(src), _ptr(idx), nrows, k,
-                                             _stream_ptr(src.device))
-    _lib.check(st, "gcn_gather_rows_f32")
+    call("gcn_gather_rows_f32", out, src, idx, nrows, k, device=src.device)
     return out
 
 
@@ -717,8 +693,5 @@ def dropout_rows(x, p, seed, offset, out=None):
     if out is None:
         out = torch.empty_like(x)
     fn = "gcn_dropout_bf16" if x.dtype == torch.bfloat16 else "gcn_dropout_f32"
-    with torch.cuda.device(x.device):
-        st = getattr(_lib.load(), fn)(_ptr(out), _ptr(x), int(x.numel()), float(p), int(seed), int(offset),
-                                      _stream_ptr(x.device))
-    _lib.check(st, fn)
+    call(fn, out, x, int(x.numel()), float(p), int(seed), int(offset), device=x.device)
     return out

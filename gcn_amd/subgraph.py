@@ -17,8 +17,9 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from .sampling import _check_stream, _vertex_map, _workspace
-from .spmm import CsrAdjacency, _ptr, _stream_ptr
+from ._lib import call
+from .sampling import _check_stream, _vertex_map
+from .spmm import CsrAdjacency
 
 Subgraph = namedtuple("Subgraph", ["adj", "eid", "node_ids"])
 Subgraph.__doc__ = """The subgraph a vertex set induces, a square graph over ``node_ids``.
@@ -29,7 +30,7 @@ in the parent's entry order, columns are positions in node_ids; symmetric iff th
 eid: int32, the parent's entry index of each entry.  node_ids: int64 vertex ids of the parent, in the caller's order."""
 
 VALUES = ("parent", "gcn", "pattern")
-assert _lib.SUBGRAPH_WS_BYTES <= _lib.SAMPLE_WS_BYTES      # (sampling.py's workspace on the adjacency serves both)
+assert _lib.SUBGRAPH_WS_BYTES <= _lib.SAMPLE_WS_BYTES      # (the adjacency's "sample" scratch serves both units)
 
 
 def _check_ids(ids, name, what):
@@ -86,10 +87,8 @@ def random_walk(adj, starts, length, seed=0, offset=0):
     if nw >= 2 ** 31:
         raise ValueError("random_walk: fewer than 2^31 walks per call (split the starts)")
     s32 = starts.to(torch.int32).contiguous()
-    with torch.cuda.device(dev):
-        st = _lib.load().gcn_random_walk_csr(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, _ptr(s32), nw, int(length),
-                                             int(seed), int(offset), _ptr(out), _stream_ptr(dev))
-    _lib.check(st, "gcn_random_walk_csr")
+    call("gcn_random_walk_csr", adj.rowptr, adj.col, adj.m, adj.nnz, s32, nw, int(length), int(seed), int(offset), out,
+         device=dev)
     return out.t()
 
 
@@ -125,17 +124,14 @@ def induced_subgraph(adj, nodes, values="parent"):
         raise ValueError(f"induced_subgraph: nodes must lie in [0, {adj.m}), found {lo if lo < 0 else hi}")
     n32 = nodes.to(torch.int32).contiguous()
     vmap = _vertex_map(adj)
-    ws = _workspace(adj)
-    lib = _lib.load()
+    ws = adj._scratch.get("sample", _lib.SAMPLE_WS_BYTES, adj.device)
     place = torch.arange(nn, dtype=torch.int32, device=dev)
     try:
         vmap[ids] = place
         repeated = (vmap[ids] != place).any()              # (a vertex named twice keeps one of its two positions)
         out_len = torch.zeros(nn, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            st = lib.gcn_induced_subgraph_count_csr(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, _ptr(n32), nn, _ptr(vmap),
-                                                    _ptr(out_len), _ptr(ws), ws.numel(), _stream_ptr(dev))
-        _lib.check(st, "gcn_induced_subgraph_count_csr")
+        call("gcn_induced_subgraph_count_csr", adj.rowptr, adj.col, adj.m, adj.nnz, n32, nn, vmap, out_len, ws, ws.numel(),
+             device=dev)
         ends = torch.cumsum(out_len.long(), 0)
         dup, total = torch.stack([repeated.long(), ends[-1]]).tolist()   # the second synchronisation
         if dup:
@@ -146,11 +142,8 @@ def induced_subgraph(adj, nodes, values="parent"):
         out_col = torch.empty(total, dtype=torch.int32, device=dev)
         out_eid = torch.empty(total, dtype=torch.int32, device=dev)
         if total > 0:                                      # (an empty tensor has no address, and the call refuses a null output)
-            with torch.cuda.device(dev):
-                st = lib.gcn_induced_subgraph_fill_csr(_ptr(adj.rowptr), _ptr(adj.col), adj.m, adj.nnz, _ptr(n32), nn, _ptr(vmap),
-                                                       _ptr(out_rowptr), _ptr(out_col), _ptr(out_eid), _ptr(ws), ws.numel(),
-                                                       _stream_ptr(dev))
-            _lib.check(st, "gcn_induced_subgraph_fill_csr")
+            call("gcn_induced_subgraph_fill_csr", adj.rowptr, adj.col, adj.m, adj.nnz, n32, nn, vmap, out_rowptr, out_col,
+                 out_eid, ws, ws.numel(), device=dev)
     finally:
         vmap[ids] = -1                                     # back to the cleared state (stream order: after the kernels)
     if values == "parent":

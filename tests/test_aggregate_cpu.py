@@ -96,7 +96,6 @@ class _FakeAdj(gcn_amd.CsrAdjacency):
         self.mutable_values = False
         self._plan = None
         self._transpose = None
-        self._tperm = None
 
 
 def test_aggregate_checks_its_arguments_in_order():

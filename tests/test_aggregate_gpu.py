@@ -379,8 +379,8 @@ def test_operands_one_element_off_the_grid(k, dtype):
     m, code = adj.m, _lib.DTYPE_BF16 if dtype == torch.bfloat16 else _lib.DTYPE_F32
     lib = gcn_amd.load_library()
     agg = __import__("importlib").import_module("gcn_amd.aggregate")
-    ws = agg._workspace(adj, k, torch.device(DEV))
-    trp, trow, tperm = agg._transpose_pattern(adj)
+    ws = agg._scratch(adj, k, torch.device(DEV))
+    trp, trow, tperm = adj.tpattern()
     x = torch.from_numpy(level_features(n, k, seed=k)).to(dtype)
     g = torch.from_numpy(int_grad(m, k, seed=k + 1, top=1)).to(dtype)
     p = lambda t: ctypes.c_void_p(t.data_ptr())
@@ -611,12 +611,14 @@ def test_a_wider_call_keeps_the_workspace_a_capture_may_hold():
     adj = make_adj("boundaries")
     x = torch.ones(adj.n, 64, device=DEV)
     gcn_amd.aggregate(adj, x[:, :4].contiguous(), "max")
-    small = adj._agg_ws
+    keeper = adj._scratch
+    small = keeper.buffers["aggregate"]
     gcn_amd.aggregate(adj, x, "max")
-    assert adj._agg_ws is not small and adj._agg_ws.numel() > small.numel()
-    assert any(w is small for w in adj._agg_ws_retired)   # still allocated: a captured step would go on writing there
+    wide = keeper.buffers["aggregate"]
+    assert wide is not small and wide.numel() > small.numel()
+    assert any(w is small for w in keeper.retired)         # still allocated: a captured step would go on writing there
     gcn_amd.aggregate(adj, x[:, :4].contiguous(), "max")
-    assert adj._agg_ws.numel() > small.numel() and len(adj._agg_ws_retired) == 1      # (never shrinks)
+    assert keeper.buffers["aggregate"] is wide and len(keeper.retired) == 1           # (never shrinks)
 
 
 # ---- 10. errors -------------------------------------------------------------------------------------------------------------

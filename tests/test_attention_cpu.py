@@ -68,7 +68,6 @@ class _FakeAdj(gcn_amd.CsrAdjacency):
         self.mutable_values = mutable
         self._plan = None
         self._transpose = None
-        self._tperm = None
 
 
 def test_cpu_tensors_raise():

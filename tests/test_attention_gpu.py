@@ -578,3 +578,80 @@ def test_forward_backward_captures_and_replays_bit_for_bit():
             p.grad = gsaved                            # (the graph writes into these tensors)
         for a, b in zip(got, want):
             assert torch.equal(a, b)
+
+
+# ---- 9. the adjacency's scratch keeper and its one transposed pattern -----------------------------------------------------------
+def _retire_rule(adj, kind, narrow, wide):
+    """the rule of spmm.Scratch for one kind: a wider call replaces the buffer and keeps the one it replaces (a captured step
+    recorded its address and goes on writing there), a narrow call after it neither shrinks nor retires.  Identity and sizes
+    only: nothing is captured"""
+    keeper = adj._scratch
+    narrow()
+    small = keeper.buffers[kind]
+    wide()
+    big = keeper.buffers[kind]
+    assert big is not small and big.numel() > small.numel()
+    assert any(w is small for w in keeper.retired)
+    retired = len(keeper.retired)
+    narrow()
+    assert keeper.buffers[kind] is big and len(keeper.retired) == retired
+
+
+def test_a_wider_heads_call_keeps_the_edge_scratch_a_capture_may_hold():
+    adj = make_adj("boundaries")
+    vals = torch.ones(adj.nnz, 2, device=DEV)
+    x = torch.ones(adj.n, 64, device=DEV)
+    _retire_rule(adj, "edge", lambda: gcn_amd.spmm_heads(adj, x[:, :4].contiguous(), vals), lambda: gcn_amd.spmm_heads(adj, x, vals))
+    assert len(adj._scratch.retired) == 1 and set(adj._scratch.buffers) == {"edge"}
+
+
+def test_a_wider_gatv2_call_keeps_the_gatv2_scratch_a_capture_may_hold():
+    adj = make_adj("boundaries")
+    hd, hs = torch.ones(adj.m, 64, device=DEV), torch.ones(adj.n, 64, device=DEV)
+    call = lambda f: gcn_amd.gatv2_scores(adj, hd[:, :2 * f].contiguous(), hs[:, :2 * f].contiguous(), torch.ones(2, f, device=DEV))
+    _retire_rule(adj, "gatv2", lambda: call(2), lambda: call(32))
+    assert len(adj._scratch.retired) == 1 and set(adj._scratch.buffers) == {"gatv2"}
+
+
+@pytest.mark.parametrize("mutable", [False, True])
+def test_every_backward_walk_reads_the_adjacencys_one_transposed_pattern(mutable, monkeypatch):
+    import sys
+    agg_mod, att_mod = sys.modules["gcn_amd.aggregate"], sys.modules["gcn_amd.attention"]   # (the package's names are functions)
+    adj = make_adj("boundaries", mutable=mutable)
+    passed = {}                                        # entry point -> the (trowptr, trow, tperm) it was handed (None: not passed)
+    where = {"gcn_aggregate_backward_csr": (0, 1, 2), "gcn_spmm_heads_csr_f32": (0, 1, 2), "gcn_segment_sum_heads_csr_f32": (0, None, 5)}
+
+    def recording(real):
+        def call(name, *args, **kw):
+            if name in where and args[where[name][2]] is not None:             # (perm None: a walk of the pattern itself)
+                passed[name] = tuple(args[i] if i is not None else None for i in where[name])
+            return real(name, *args, **kw)
+        return call
+
+    monkeypatch.setattr(agg_mod, "call", recording(agg_mod.call))
+    monkeypatch.setattr(att_mod, "call", recording(att_mod.call))
+    gen = torch.Generator().manual_seed(21)
+    x = torch.randn(adj.n, 4, generator=gen).to(DEV).requires_grad_(True)
+    gcn_amd.aggregate(adj, x, "max").sum().backward()
+    vals = torch.rand(adj.nnz, 2, generator=gen).to(DEV)
+    gcn_amd.spmm_heads(adj, x, vals).sum().backward()
+    a_dst = torch.randn(adj.m, 2, generator=gen).to(DEV).requires_grad_(True)
+    a_src = torch.randn(adj.n, 2, generator=gen).to(DEV).requires_grad_(True)
+    (gcn_amd.gat_edge_softmax(adj, a_dst, a_src) * vals).sum().backward()
+    torch.cuda.synchronize()
+    # exactly one pattern cache on the adjacency, and every unit was handed its arrays themselves
+    caches = [k for k, v in vars(adj).items() if isinstance(v, (tuple, list)) and any(isinstance(t, torch.Tensor) for t in v)]
+    assert caches == ["_tpattern"]
+    tp = adj.tpattern()
+    assert tp is adj._tpattern and len(tp) == 3
+    assert set(passed) == set(where)
+    for name, arrays in passed.items():
+        for got, cached in zip(arrays, tp):
+            assert got is None or got is cached, name
+    for t, count in zip(tp, (adj.n + 1, adj.nnz, adj.nnz)):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == count
+    assert torch.equal(tp[2].long(), adj._transposed_pattern()[2])
+    if mutable:
+        t = adj._mutable_transpose()
+        assert torch.equal(t.rowptr, tp[0]) and torch.equal(t.col, tp[1])
+        assert [k for k, v in vars(adj).items() if isinstance(v, (tuple, list))] == ["_tpattern"]

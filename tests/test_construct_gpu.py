@@ -180,7 +180,8 @@ def test_transposed_pattern_is_the_torch_formulation_it_replaces():
     assert [a.dtype for a in new] == [torch.int32, torch.int32, torch.int64]
     mut, va = make_adj(rp[:200], ci[:rp[199]], 199, n, mutable_values=True)
     t = mut.transpose()                                # the mutable transpose rides on the same pattern
-    assert torch.equal(t.val, mut.val[mut._tperm]) and torch.equal(mut._tperm, torch_transposed_pattern(mut)[2])
+    tperm = mut.tpattern()[2].long()
+    assert torch.equal(t.val, mut.val[tperm]) and torch.equal(tperm, torch_transposed_pattern(mut)[2])
 
 
 def test_transpose_of_a_duplicate_free_bipartite_matrix_is_the_coo_round_trip():

@@ -20,7 +20,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import gcn_amd                  # noqa: E402
-from gcn_amd import attention, graphgen    # noqa: E402
+from gcn_amd import graphgen    # noqa: E402
 
 
 def time_ms(fn, steps, warmup):
@@ -52,7 +52,7 @@ def one_shape(adj, madj, n, nnz, H, F, T, gen, dev):
     res["gat_heads_fwd_ms"] = T(lambda: gcn_amd.gat_edge_softmax(adj, a_dst.detach(), a_src.detach(), 0.2))
     pg = gcn_amd.gat_edge_softmax(adj, a_dst, a_src, 0.2)
     res["gat_heads_bwd_ms"] = T(lambda: torch.autograd.grad(pg, (a_dst, a_src), gp, retain_graph=True))
-    trp, _trow, tperm = attention._heads_tpattern(adj)      # (grad_a_src: the segment sum inside the line above)
+    trp, _trow, tperm = adj.tpattern()      # (grad_a_src: the segment sum inside the line above)
     res["segment_sum_heads_transposed_ms"] = T(lambda: gcn_amd.segment_sum(trp, gp, perm=tperm))
     res["segment_sum_heads_ms"] = T(lambda: gcn_amd.segment_sum(adj.rowptr, gp))
     pv = p.detach().clone().requires_grad_(True)

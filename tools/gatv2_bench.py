@@ -50,7 +50,7 @@ def one_shape(adj, n, nnz, H, F, T, rounds, gen, dev, with_torch):
     gout = torch.randn((n, k), generator=gen, device=dev)
     vals = torch.rand((nnz, H), generator=gen, device=dev)
     hd, hs, a = h_dst.detach(), h_src.detach(), att.detach()
-    trp, trow, tperm = attention._heads_tpattern(adj)
+    trp, trow, tperm = adj.tpattern()
     row = torch.repeat_interleave(torch.arange(n, device=dev), (adj.rowptr[1:] - adj.rowptr[:-1]).long())
     col = adj.col.long()
 

@@ -68,7 +68,7 @@ def main():
            "what": "ms per call, CUDA events around `steps` calls", "sddmm": [], "train": []}
     w = val.clone().requires_grad_(True)
     adjT = adj.transpose()
-    wT = w.detach().index_select(0, adj._tperm)
+    wT = w.detach().index_select(0, adj.tpattern()[2])
     res["update_values_ms"] = time_ms(lambda: adj.update_values(w), args.steps, args.warmup)
     res["update_values_transpose_ms"] = time_ms(lambda: adjT.update_values(wT), args.steps, args.warmup)
     ok = True
