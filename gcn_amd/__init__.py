@@ -15,6 +15,7 @@ from .sampling import Block, NeighborLoader, sample_blocks, sample_neighbors  # 
 from .subgraph import ClusterLoader, RandomWalkLoader, Subgraph, induced_subgraph, random_walk  # noqa: F401
 from .construct import bucket_by_key, csr_from_edges, transpose_csr  # noqa: F401
 from .coalesce import coalesce_csr, gcn_adjacency, normalize_csr, symmetrize  # noqa: F401
+from .linkpred import LinkNeighborLoader, edge_subgraph, find_edges, negative_sample, pair_scores, reverse_entries, split_edges  # noqa: F401
 from .spgemm import HypergraphLaplacian, SparseProduct, hypergraph_laplacian, sampled_dot, spgemm  # noqa: F401
 from .knn import KNN_K_MAX, knn, knn_graph, knn_hypergraph  # noqa: F401
 from . import reorder, dropin  # noqa: F401

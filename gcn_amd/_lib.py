@@ -160,6 +160,9 @@ SIGNATURES = {
                                                      ctypes.c_size_t, _c_p]),
     "gcn_random_walk_csr": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_i32, ctypes.c_uint64, ctypes.c_uint64, _c_p,
                                            _c_p]),
+    "gcn_csr_find_entries": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p, _c_i32, _c_p, _c_p]),
+    "gcn_negative_sample_csr": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_i32, _c_i32, _c_i32,
+                                               ctypes.c_uint64, ctypes.c_uint64, _c_p, _c_p]),
     "gcn_bucket_count_i32": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p]),
     "gcn_bucket_fill_i32": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_csr_transpose_gather": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p]),

@@ -441,6 +441,26 @@ int gcn_random_walk_csr(const int32_t* rowptr, const int32_t* col, int32_t m, in
              ? GCN_OK : GCN_ERR_HIP;
 }
 
+int gcn_csr_find_entries(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t nnz, const int32_t* q_rows,
+                         const int32_t* q_cols, int32_t n_queries, int32_t* out_eid, void* stream) {
+  if (m < 0 || nnz < 0 || n_queries < 0) return GCN_ERR_INVALID_ARG;
+  if (n_queries == 0) return GCN_OK;
+  if (!q_rows || !q_cols || !out_eid || (m > 0 && !rowptr) || (m > 0 && nnz > 0 && !col)) return GCN_ERR_INVALID_ARG;
+  return launch_find_entries(rowptr, col, m, nnz, q_rows, q_cols, n_queries, out_eid, (hipStream_t)stream) == hipSuccess
+             ? GCN_OK : GCN_ERR_HIP;
+}
+
+int gcn_negative_sample_csr(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t n, int32_t nnz, const int32_t* q_rows,
+                            int32_t n_queries, int32_t num_neg, int32_t max_tries, int32_t exclude_self, uint64_t seed,
+                            uint64_t offset, int32_t* out_cols, void* stream) {
+  if (m < 0 || n < 0 || nnz < 0 || n_queries < 0 || num_neg < 1 || max_tries < 1 || max_tries > 64) return GCN_ERR_INVALID_ARG;
+  if ((long long)n_queries * num_neg >= (1ll << 31)) return GCN_ERR_INVALID_ARG;
+  if (n_queries == 0) return GCN_OK;
+  if (n < 1 || !q_rows || !out_cols || (m > 0 && !rowptr) || (m > 0 && nnz > 0 && !col)) return GCN_ERR_INVALID_ARG;
+  return launch_negative_sample(rowptr, col, m, n, nnz, q_rows, n_queries * num_neg, num_neg, max_tries, exclude_self != 0, seed,
+                                offset, out_cols, (hipStream_t)stream) == hipSuccess ? GCN_OK : GCN_ERR_HIP;
+}
+
 static_assert(kBucketWaveMax == GCN_BUCKET_WAVE_MAX && kBucketBlockMax == GCN_BUCKET_BLOCK_MAX, "include/gcn_spmm.h");
 
 int gcn_bucket_count_i32(const int32_t* keys, int32_t count, int32_t nbuckets, int32_t* offsets, void* stream) {

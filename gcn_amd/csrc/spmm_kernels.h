@@ -246,6 +246,15 @@ hipError_t launch_induced_subgraph_fill(const int* rowptr, const int* col, int m
 hipError_t launch_random_walk(const int* rowptr, const int* col, int m, int nnz, const int* starts, int n_walks, int length,
                               unsigned long long seed, unsigned long long offset, int* out_walks, hipStream_t st);
 
+// lookup.hip — the entry index of (q_rows[i], q_cols[i]) in a CSR with column-sorted rows, or -1, and num_neg columns per
+// query row that the row does not store (a pure function of (seed, offset, slot); slots = n_queries * num_neg): one lane per
+// query / slot, no workspace, no atomics (see the file's header and include/gcn_spmm.h).
+hipError_t launch_find_entries(const int* rowptr, const int* col, int m, int nnz, const int* q_rows, const int* q_cols,
+                               int n_queries, int* out_eid, hipStream_t st);
+hipError_t launch_negative_sample(const int* rowptr, const int* col, int m, int n, int nnz, const int* q_rows, int slots,
+                                  int num_neg, int max_tries, int exclude_self, unsigned long long seed,
+                                  unsigned long long offset, int* out_cols, hipStream_t st);
+
 // construct.hip — stable bucketing of the indices 0 .. count - 1 by an int key in [0, nbuckets) (count, the caller's scan,
 // fill) and the gather that turns the bucketing of a CSR's entries by column into its transpose (see the file's header and
 // include/gcn_spmm.h).  A bucket of at most kBucketWaveMax entries is ordered by a wave, one of at most kBucketBlockMax by a

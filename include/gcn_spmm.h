@@ -461,6 +461,51 @@ int gcn_induced_subgraph_fill_csr(const int32_t* rowptr_dev, const int32_t* col_
 int gcn_random_walk_csr(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz, const int32_t* starts_dev,
                         int32_t n_walks, int32_t length, uint64_t seed, uint64_t offset, int32_t* out_walks_dev, void* stream);
 
+/* Edge lookup on a CSR pattern whose rows hold ASCENDING columns (DGL's has_edges_between / edge_ids): the entry index of
+ * each queried pair.  One kernel, one lane per query, no workspace, no allocation, no host read of device data, no atomics;
+ * every output element has one writer; the call only enqueues.  The stored values are not used; 4-byte accesses only: no
+ * pointer needs more than 4-byte alignment.  The contract (tests/linkpred_ref.py is the numpy twin):
+ *   out_eid_dev[i] = the LOWEST entry index e in [rowptr[r], rowptr[r + 1]) with col[e] == q_cols_dev[i], r = q_rows_dev[i]
+ *   (a row may repeat a column), or -1 when the pair is not stored, r is outside [0, m), or the row's pointers are outside
+ *   [0, nnz] or out of order.  A q_cols_dev[i] that is negative or beyond the last column is simply not found.
+ * The search is a lower bound over the row (about log2 of its length dependent probes).  On a row whose columns do NOT
+ * ascend it still terminates and reads nothing outside the row's entries, but the answer is unspecified: an entry index of
+ * that row holding the column, or -1 although the column is stored.  The caller sorts first (gcn_amd.csr_from_edges
+ * with sort_columns=True, gcn_amd.coalesce_csr).
+ * The launch shape depends on n_queries only; the host never reads a row length.
+ * Negative sizes or a null pointer: GCN_ERR_INVALID_ARG (rowptr_dev may be null when m == 0, col_dev when nnz == 0);
+ * n_queries == 0: GCN_OK, nothing written. */
+int gcn_csr_find_entries(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t nnz, const int32_t* q_rows_dev,
+                         const int32_t* q_cols_dev, int32_t n_queries, int32_t* out_eid_dev, void* stream);
+
+/* Negative sampling for link prediction: num_neg columns per queried row that the row does NOT store, by rejection, a pure
+ * function of (seed, offset, slot).  Same pattern (ascending columns within rows, same behaviour on a row that does not
+ * ascend: terminates in bounds, answer unspecified) and same rules as the lookup, whose row search it shares: one kernel,
+ * one lane per slot, no workspace, no allocation, no host read of device data, no atomics, one writer per output element,
+ * 4-byte accesses only.  The contract (tests/linkpred_ref.py is the numpy twin):
+ *   out_cols_dev is int32 [n_queries * num_neg]; slot p = i * num_neg + s (a 64-bit integer) belongs to row r = q_rows_dev[i].
+ *   Let T4 = 4 * ceil(max_tries / 4).  Try t = 0 .. max_tries - 1 of slot p uses j = p * T4 + t:
+ *     key = word (j & 3) of Philox4x32-10 with counter (lo32(j >> 2), hi32(j >> 2), lo32(offset), hi32(offset)) and key
+ *           (lo32(seed), hi32(seed)) — the word and counter convention of gcn_random_walk_csr;
+ *     c   = (key * n) >> 32, the high word of the 32 x 32-bit product, in [0, n).
+ *   out_cols_dev[p] = the first c, in ascending t, that is not stored in row r and, with exclude_self != 0, differs from r;
+ *   -1 when all max_tries candidates are refused, or the row is unusable (r outside [0, m), row pointers outside [0, nnz] or
+ *   out of order).
+ *   T4 is a multiple of 4, so the tries 4q .. 4q + 3 of a slot share the counter p * T4 / 4 + q: one Philox call serves
+ *   four consecutive tries, made when the first of the four is needed.
+ * Uniformity: key is a uniform 32-bit word, so c takes each value in [0, n) with probability floor or ceil of 2^32 / n over
+ * 2^32; over the columns that pass the two tests the accepted column is therefore uniform up to a relative bias below
+ * n / 2^32, e.g. 2^-14 for n = 2^18.  A slot is -1 with probability (refused columns / n)^max_tries.
+ * Independence: a slot depends on (seed, offset, p, max_tries — through T4 —, n, and the contents of its row) only, not on
+ * n_queries or the other queries of the call; successive batches must use different offsets.  The slots of one query are
+ * drawn independently of each other: two of them MAY hold the same column.
+ * 1 <= max_tries <= 64, num_neg >= 1, n_queries * num_neg < 2^31, n >= 1 when n_queries > 0; anything else, negative sizes
+ * or a null pointer: GCN_ERR_INVALID_ARG (rowptr_dev may be null when m == 0, col_dev when nnz == 0); n_queries == 0:
+ * GCN_OK, nothing written.  The launch shape depends on n_queries * num_neg only. */
+int gcn_negative_sample_csr(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t n, int32_t nnz,
+                            const int32_t* q_rows_dev, int32_t n_queries, int32_t num_neg, int32_t max_tries,
+                            int32_t exclude_self, uint64_t seed, uint64_t offset, int32_t* out_cols_dev, void* stream);
+
 /* Stable bucketing of the indices 0 .. count - 1 by an integer key: the primitive under the device CSR transpose and under
  * building a CSR from an edge list (gcn_amd/construct.py).  Two calls with the caller's prefix sum between them, as for the
  * induced subgraph, and plan-free under the same rules: the caller's arrays, memset / copy nodes and kernels, no allocation,
