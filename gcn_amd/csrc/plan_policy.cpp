@@ -266,7 +266,8 @@ PassKind pass_kind(const gcn_spmm_plan* p, int k, int ld, bool sliced, int tile_
   if (walks) { pk.valless = pk.group = true; return pk; }
   SpmmRoute r;                                         // without the group stream: the four-per-gather kernel, all 16 lanes
   r.family = SpmmFamily::sliced_quad; r.k_run = k; r.ldb = ld; r.copy = BCopy::row_padded; r.tile_cols = tile_cols;
-  pk.valless = spmm_will_use_quad(spmm_args(p, r, false)) && spmm_quad_lanes(k) == 16;
+  const ChunkChoice c = spmm_chunk_choice(spmm_args(p, r, false));
+  pk.valless = c.family == ChunkFamily::quad && c.lanes == 16;
   pk.group = pk.valless && p->group.ready();        // (a stream that exists is walked: the width it cannot serve is refused there)
   return pk;
 }
@@ -449,7 +450,7 @@ int gcn_spmm_plan_main_kernel(const gcn_spmm_plan_t* p, int32_t k, int32_t epilo
   if (r.family == SpmmFamily::panels) snprintf(buf, (size_t)buflen, "gcn::spmm_panel_in_kernel");
   else if (r.family == SpmmFamily::group)
     spmm_group_kernel_name(spmm_group_choice(group_shape(r.ss, r.weighted, 4, r.ldb, r.k_run)), buf, (size_t)buflen);
-  else describe_main_kernel(spmm_args(p, r, epilogue != 0), buf, (size_t)buflen);
+  else spmm_chunk_kernel_name(spmm_chunk_choice(spmm_args(p, r, epilogue != 0)), buf, (size_t)buflen);
   return GCN_OK;
 }
 

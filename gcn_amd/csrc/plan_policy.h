@@ -61,7 +61,7 @@ struct SpmmRoute {
 // `prelaid`: the caller hands B over in the plan's pre-laid layout (own slice set, rows already scaled, no detour).
 SpmmRoute spmm_route(gcn_spmm_plan* p, int k, bool build, const int32_t* rowptr, const int32_t* col, const float* val,
                      hipStream_t st, bool prelaid = false);
-// the launch of a non-group route without its pointers: what launch_spmm is handed and describe_main_kernel names
+// the launch of a non-group route without its pointers: what launch_spmm is handed and spmm_chunk_choice decides from
 SpmmArgs spmm_args(const gcn_spmm_plan* p, const SpmmRoute& r, bool epilogue);
 // the route of a call that hands B over pre-laid (k % 4 == 0), or GCN_ERR_INVALID_ARG: the plan has no such layout for k
 int spmm_route_prelaid(const gcn_spmm_plan* p, int k, SpmmRoute* r);

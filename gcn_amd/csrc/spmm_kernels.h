@@ -56,45 +56,39 @@ hipError_t launch_count_empty_rows(const int* rowptr, int m, int* count_dev, hip
 hipError_t launch_fill_empty_rows(const int* rowptr, float* C, const float* bias, int relu, int accumulate, int m, int k,
                                   hipStream_t s);
 
-// The main kernels' row walk has just stepped onto row r and found it empty (rowptr[r + 1] == pos): the first row
-// i > r that holds an entry (rowptr[i + 1] > pos), or m.  Gallop, then bisect — wave-uniform scalar loads, O(log run)
-// where the walk used to spend one dependent load and one store per empty row.
-template <class RowPtr>
-__device__ __forceinline__ int next_nonempty_row(RowPtr rowptr, int r, int m, int pos) {
-  int lo = r, hi = r + 1;                               // row lo is empty; is row hi?
-  unsigned step = 1;
-  while (hi < m && rowptr[hi + 1] == pos) {
-    lo = hi;
-    step <<= 1;
-    hi = (step >= (unsigned)(m - hi)) ? m : hi + (int)step;
-  }
-  while (hi - lo > 1) {                                 // row lo empty, row hi not (or hi == m)
-    const int mid = lo + ((hi - lo) >> 1);
-    if (rowptr[mid + 1] == pos) lo = mid; else hi = mid;
-  }
-  return hi;
-}
 hipError_t launch_spmm(const SpmmArgs& a, int cu_count, hipStream_t s);
 hipError_t launch_gather_rows(float* dst, const float* src, const int* idx, int nrows, int k,
                               hipStream_t s);
 // dst[r, 0:k] = src[r, 0:k], dst[r, k:ld] = 0 for r < rows (dst row stride ld >= k)
 hipError_t launch_pad_rows(float* dst, const float* src, long long rows, int k, int ld, hipStream_t s,
                            const float* rowscale = nullptr);   // dst[r, :] = rowscale[r] * src[r, :] when given
-// true when launch_spmm will run the four-per-gather kernel for these arguments
-bool spmm_will_use_quad(const SpmmArgs& a);
 // dst[r, 0:k] = act(src[r, 0:k] + bias), src row stride ld >= k
 hipError_t launch_unpad_rows(float* dst, const float* src, const float* bias, int relu, long long rows, int k,
                              int ld, hipStream_t s, const int* guard = nullptr);   // guard: skip when *guard == 0
 int pick_vec(int k, int tile_cols, const void* B, const void* C, const void* P);
-void describe_main_kernel(const SpmmArgs& a, char* buf, size_t len);
 
-// spmm_narrow.hip — k <= 32: several non-zeros per gather instruction
-hipError_t launch_spmm_narrow(const SpmmArgs& a, int nblocks, bool epi, hipStream_t s);
+// which main kernel a launch_spmm with these arguments runs (the one rule: the launch switches on it, the plan API's
+// reports ask it), and its name.  refused: what launch_spmm answers with hipErrorInvalidValue — a value-free or 16-bit
+// column stream handed to a kernel that is not built for it.
+enum class ChunkFamily { empty, quad, narrow, narrow16_dpp, chunk, refused };
+struct ChunkChoice {
+  ChunkFamily family;
+  int lanes;                             // lanes per non-zero: quad 4 / 16, narrow G = 4 / 8 / 16, chunk 64
+  int vec, U;                            // floats per lane and gather; gather instructions per batch
+  bool epi, buf, valless, col16;         // template flags: fused epilogue, buffer addressing, no values, 16-bit columns
+};
+ChunkChoice spmm_chunk_choice(const SpmmArgs& a);
+void spmm_chunk_kernel_name(const ChunkChoice& c, char* buf, size_t len);
+// the fifteen leading arguments of every chunk-schedule main kernel
+#define GCN_CHUNK_ARGS(a) (a).rowptr, (a).col, (a).val, (a).B, (a).C, (a).P, (a).chunk_row, (a).bias, (a).nnz_dev, \
+                          (a).relu, (a).nchunks, (a).T, (a).m, (a).nnz, (a).k
 
-// spmm_quad.hip — 64-column tile, four non-zeros per 16-byte-per-lane gather instruction
+// spmm_narrow.hip — k <= 16: several non-zeros per gather instruction (c: a narrow or narrow16_dpp choice)
+hipError_t launch_spmm_narrow(const SpmmArgs& a, const ChunkChoice& c, int nblocks, hipStream_t s);
+
+// spmm_quad.hip — 64-column tile, four non-zeros per 16-byte-per-lane gather instruction (c: a quad choice)
 bool spmm_quad_eligible(const SpmmArgs& a);
-int spmm_quad_lanes(int k);
-hipError_t launch_spmm_quad(const SpmmArgs& a, int nblocks, bool epi, hipStream_t s);
+hipError_t launch_spmm_quad(const SpmmArgs& a, const ChunkChoice& c, int nblocks, hipStream_t s);
 
 // spmm_group.hip — sliced main pass, four independent 16-lane row engines per wave (the walk itself: group_walk.h)
 struct GroupArgs {

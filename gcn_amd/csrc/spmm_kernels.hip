@@ -28,6 +28,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "spmm_kernels.h"
+#include "chunk_walk.h"
 
 namespace gcn {
 
@@ -54,8 +55,6 @@ __device__ __forceinline__ void store_vec(float* p, const float (&in)[VEC]) {
   for (int i = 0; i < VEC; ++i) f[i] = in[i];
   *reinterpret_cast<V*>(p) = v;
 }
-
-__device__ __forceinline__ int sgpr(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -112,11 +111,7 @@ spmm_chunk_kernel(const int* __restrict__ g_rowptr, const int* __restrict__ g_co
                   int relu, int nchunks, int T, int m, int nnz, int kk, int col_tile, int accumulate, int ldb) {
   // drop-in (flexspmm) mode: the host does not know nnz; it lives in rowptr[m] and
   // the values follow the column indices in one buffer (api_dropin.cpp, csr2tile layout)
-  if (g_nnz_dev) {
-    nnz = *g_nnz_dev;
-    nchunks = (int)(((long long)nnz + T - 1) / T);
-    g_val = reinterpret_cast<const float*>(g_col) + nnz;
-  }
+  dropin_shape(g_nnz_dev, T, nnz, nchunks, g_col, g_val);   // drop-in (flexspmm) mode: nnz lives on the device (chunk_walk.h)
   // plain-struct view of the arguments (all loads below are from __restrict__
   // const pointers, so row pointers / chunk rows come in through the scalar cache)
   const struct {
@@ -128,15 +123,7 @@ spmm_chunk_kernel(const int* __restrict__ g_rowptr, const int* __restrict__ g_co
   const int lane = threadIdx.x & 63;
   const int wib  = sgpr(threadIdx.x >> 6);
 
-  // XCD-aware chunk ranges: blocks b and b+8 share an XCD (round-robin dispatch),
-  // so XCD x walks the contiguous chunk range [x*N/8, (x+1)*N/8) — neighbouring
-  // rows (which share neighbours after RCM/Gorder) meet in one 4 MiB L2.
-  // Placement only affects speed, never the result.
-  const int xcd           = blockIdx.x & 7;
-  const int wave_in_xcd   = (blockIdx.x >> 3) * 4 + wib;
-  const int waves_per_xcd = (gridDim.x >> 3) * 4;
-  const int c_lo = (int)(((long long)a.nchunks * xcd) >> 3);
-  const int c_hi = (int)(((long long)a.nchunks * (xcd + 1)) >> 3);
+  const ChunkRange range(wib, a.nchunks);
 
   const int  fcol   = col_tile * (64 * VEC) + lane * VEC;   // first feature column of this lane
   const bool active = fcol < a.k;
@@ -165,15 +152,10 @@ spmm_chunk_kernel(const int* __restrict__ g_rowptr, const int* __restrict__ g_co
     }
   }
 
-  for (int c = c_lo + wave_in_xcd; c < c_hi; c += waves_per_xcd) {
+  for (int c = range.first; c < range.c_hi; c += range.stride) {
     const int start = c * a.T;
     const int end   = (int)min((long long)start + a.T, (long long)a.nnz);
-    int r = a.chunk_row[c];
-    int row_end    = a.rowptr[r + 1];
-    int row_end_nx = (r + 1 < a.m) ? a.rowptr[r + 2] : -1;
-    bool head = a.rowptr[r] < start;      // row r began in an earlier chunk
-    int pos = start;
-    int last_flush = start;
+    GCN_ROW_WALK_OPEN(a.rowptr, a.chunk_row, c, a.T, a.m);     // r, row_end, row_end_nx, head, pos, last_flush (chunk_walk.h)
 
     float acc[VEC];
 #pragma unroll
@@ -205,15 +187,7 @@ spmm_chunk_kernel(const int* __restrict__ g_rowptr, const int* __restrict__ g_co
       }
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
-      head = false;
-      last_flush = pos;
-      ++r;
-      row_end    = row_end_nx;
-      if (row_end == pos) {                 // row r is empty: on to the next row that holds an entry
-        r = next_nonempty_row(a.rowptr, r, a.m, pos);
-        row_end = (r < a.m) ? a.rowptr[r + 1] : -1;
-      }
-      row_end_nx = (r + 1 < a.m) ? a.rowptr[r + 2] : -1;
+      GCN_ROW_WALK_NEXT(a.rowptr, a.m)
     };
 
     while (pos == row_end) flush();        // leading empty rows (chunk 0 only)
@@ -292,7 +266,7 @@ spmm_fixup_kernel(const int* __restrict__ g_rowptr, const float* __restrict__ g_
                   float* __restrict__ g_C, const int* __restrict__ g_chunk_row,
                   const float* __restrict__ g_bias, const int* __restrict__ g_nnz_dev,
                   int relu, int nchunks, int T, int kk, int accumulate) {
-  if (g_nnz_dev) nchunks = (int)(((long long)(*g_nnz_dev) + T - 1) / T);
+  if (g_nnz_dev) nchunks = dropin_nchunks(*g_nnz_dev, T);
   const struct {
     const int* __restrict__ rowptr; const float* __restrict__ P; float* __restrict__ C;
     const int* __restrict__ chunk_row; const float* __restrict__ bias; int relu, nchunks, T, k;
@@ -432,31 +406,24 @@ hipError_t launch_plan_chunk_rows(const int* rowptr, int m, int T, int nchunks,
 }
 
 template <int VEC, int U>
-static hipError_t launch_main(const SpmmArgs& a, int nblocks, bool epi, hipStream_t s) {
+static hipError_t launch_main(const SpmmArgs& a, const ChunkChoice& c, int nblocks, hipStream_t s) {
   // One launch per 64*VEC-column tile, back to back on the stream: a pass only touches its
   // own column slice of B, so the gathered working set per pass is n*64*VEC*4 bytes — the
   // narrower the slice, the larger the share of it that stays in L2 / Infinity Cache.
   const int tiles = (a.k + 64 * VEC - 1) / (64 * VEC);
   dim3 grid(nblocks), block(256);
-#define GCN_MAIN_ARGS a.rowptr, a.col, a.val, a.B, a.C, a.P, a.chunk_row, a.bias, a.nnz_dev, \
-                      a.relu, a.nchunks, a.T, a.m, a.nnz, a.k, t, a.accumulate, ldb
   const int ldb = a.ldb > 0 ? a.ldb : a.k;
-  // buffer addressing needs every byte offset into B to fit 32 bits
-  const bool buf = VEC == 1 && (unsigned long long)a.n * (unsigned long long)ldb * 4ull < 0xFFFFFFF0ull;
   for (int t = 0; t < tiles; ++t) {
     if constexpr (VEC == 1) {
-      if (buf) {
-        if (epi) spmm_chunk_kernel<VEC, U, true, true><<<grid, block, 0, s>>>(GCN_MAIN_ARGS);
-        else     spmm_chunk_kernel<VEC, U, false, true><<<grid, block, 0, s>>>(GCN_MAIN_ARGS);
+      if (c.buf) {
+        if (c.epi) spmm_chunk_kernel<VEC, U, true, true><<<grid, block, 0, s>>>(GCN_CHUNK_ARGS(a), t, a.accumulate, ldb);
+        else       spmm_chunk_kernel<VEC, U, false, true><<<grid, block, 0, s>>>(GCN_CHUNK_ARGS(a), t, a.accumulate, ldb);
         continue;
       }
     }
-    {
-      if (epi) spmm_chunk_kernel<VEC, U, true, false><<<grid, block, 0, s>>>(GCN_MAIN_ARGS);
-      else     spmm_chunk_kernel<VEC, U, false, false><<<grid, block, 0, s>>>(GCN_MAIN_ARGS);
-    }
+    if (c.epi) spmm_chunk_kernel<VEC, U, true, false><<<grid, block, 0, s>>>(GCN_CHUNK_ARGS(a), t, a.accumulate, ldb);
+    else       spmm_chunk_kernel<VEC, U, false, false><<<grid, block, 0, s>>>(GCN_CHUNK_ARGS(a), t, a.accumulate, ldb);
   }
-#undef GCN_MAIN_ARGS
   return hipGetLastError();
 }
 
@@ -471,29 +438,86 @@ int pick_vec(int k, int tile_cols, const void* B, const void* C, const void* P) 
   return 1;
 }
 
-// the quad kernel (spmm_quad.hip) runs whenever its layout applies: k % 4 == 0, 16-byte aligned operands,
-// 32-bit byte offsets; for k > 32 only where the 64-column tile is the chosen tile width
 constexpr int kQuadMinRowLen = 48;
 
-static bool use_quad(const SpmmArgs& a) {
-  constexpr int min_k = 12;               // (below: the narrow kernels' 4-byte-per-lane gathers, spmm_narrow.hip)
-  if (a.gather_width == 1 || a.k < min_k || !spmm_quad_eligible(a)) return false;
+// Which main kernel runs for these arguments: the one place that decides.  launch_spmm switches on the answer, the
+// launchers of spmm_quad.hip / spmm_narrow.hip instantiate from it, spmm_chunk_kernel_name prints it, and plan_policy.cpp
+// asks it where the policy depends on the kernel.
+ChunkChoice spmm_chunk_choice(const SpmmArgs& a) {
+  ChunkChoice c{};
+  c.epi = (a.bias != nullptr) || a.relu;
+  c.valless = a.valless != 0;
+  c.col16 = a.col16 != 0;
+  if (a.nchunks_grid == 0) { c.family = ChunkFamily::empty; return c; }
+  const int ldb = a.ldb > 0 ? a.ldb : a.k;
+  // buffer addressing needs every byte offset into B to fit 32 bits
+  const bool buf32 = (unsigned long long)a.n * (unsigned long long)ldb * 4ull < 0xFFFFFFF0ull;
+  const int vec = pick_vec(a.k, a.tile_cols, a.B, a.C, a.P);
+
+  // The quad kernel (spmm_quad.hip) runs whenever its layout applies: k % 4 == 0, 16-byte aligned operands, 32-bit byte
+  // offsets; from k = 12 (below: the narrow kernels' 4-byte-per-lane gathers, spmm_narrow.hip); for k > 32 only where the
+  // 64-column tile is the chosen tile width.
   // Short rows: every finished row costs the quad layout a cross-lane reduction (8-16 shuffles) where
   // the one-per-gather kernel just stores.  R-MAT, n = 1 M, k = 64 (profiles/r01f_lowdeg_probe.log), one-
   // vs four-per-gather: mean degree 4.9: 0.229 vs 0.508 ms; 8.8: 0.33 vs 0.56; 16: 0.54 vs 0.64;
   // 31: 0.87 vs 0.89; 59: 1.573 vs 1.564 -> the quad kernel from ~48 non-zeros per (virtual) row up.
   const long long nnz = a.nnz_dev ? (long long)a.nchunks_grid * a.T : (long long)a.nnz;
-  if (a.gather_width != 4 && a.m > 0 && nnz / a.m < kQuadMinRowLen) return false;
-  return a.k <= 32 || pick_vec(a.k, a.tile_cols, a.B, a.C, a.P) == 1;
+  const bool short_rows = a.gather_width != 4 && a.m > 0 && nnz / a.m < kQuadMinRowLen;
+  if (a.gather_width != 1 && a.k >= 12 && spmm_quad_eligible(a) && !short_rows && (a.k <= 32 || vec == 1)) {
+    // 16-byte-per-lane gathers; lanes per non-zero: the narrowest layout whose tile (4 * lanes columns) covers k, so
+    // 4 (k > 16) or 16 (k <= 16) non-zeros per instruction
+    c.family = ChunkFamily::quad;
+    c.lanes = a.k <= 16 ? 4 : 16;
+    c.vec = 4; c.U = c.lanes;
+    // the value-free variants are only built for the sliced main pass (16 lanes, no epilogue), 16-bit columns only
+    // value-free: anything else is a caller bug — B was prepared for a kernel that is not there
+    if ((c.valless || c.col16) && !(c.lanes == 16 && c.valless && !c.epi)) c.family = ChunkFamily::refused;
+    return c;
+  }
+  if (c.valless) { c.family = ChunkFamily::refused; return c; }
+  if (a.k <= 16 && (a.ldb == 0 || a.ldb == a.k)) {
+    // k <= 16 without the alignment the quad kernel needs: several non-zeros per 4-byte-per-lane gather; U gather
+    // instructions per batch: one 64-entry (col, val) block
+    c.vec = 1; c.buf = buf32;
+    c.lanes = c.U = a.k <= 4 ? 4 : (a.k <= 8 ? 8 : 16);
+    // k in 9..16 with buffer addressing and n < 2^24: the cross-lane traffic on DPP, 24-bit offsets
+    c.family = (a.k > 8 && buf32 && a.n < (1 << 24)) ? ChunkFamily::narrow16_dpp : ChunkFamily::narrow;
+    return c;
+  }
+  // 32 gathers in flight per wave for the 64-column tile (measured on the sliced Reddit-shaped case, whole SpMM:
+  // U = 4 / 8 / 16 / 32 -> 5.16 / 4.33 / 4.18 / 4.09 ms; 52 VGPRs at U = 32, still 8 waves per SIMD)
+  c.family = ChunkFamily::chunk;
+  c.lanes = 64;
+  c.vec = vec; c.U = vec == 4 ? 4 : (vec == 2 ? 8 : 32);
+  c.buf = vec == 1 && buf32;             // (the 2- and 4-float tiles keep flat addressing: gather_row)
+  return c;
 }
 
-bool spmm_will_use_quad(const SpmmArgs& a) { return a.nchunks_grid > 0 && use_quad(a); }
+// Name (as rocprofv3 prints it) of the kernel a choice stands for: what gcn_spmm_plan_main_kernel reports, so that a
+// benchmark names the kernel that runs.
+void spmm_chunk_kernel_name(const ChunkChoice& c, char* buf, size_t len) {
+  const auto tf = [](bool b) { return b ? "true" : "false"; };
+  switch (c.family) {
+    case ChunkFamily::empty:   snprintf(buf, len, "gcn::spmm_empty_kernel"); break;
+    case ChunkFamily::quad:
+      snprintf(buf, len, "gcn::spmm_quad_kernel<%d, %s, %s, %s>", c.lanes, tf(c.epi), tf(c.valless), tf(c.col16));
+      break;
+    case ChunkFamily::narrow16_dpp: snprintf(buf, len, "gcn::spmm_narrow16_dpp_kernel<%s>", tf(c.epi)); break;
+    case ChunkFamily::narrow:
+      snprintf(buf, len, "gcn::spmm_narrow_kernel<%d, %d, %s, %s>", c.lanes, c.U, tf(c.epi), tf(c.buf));
+      break;
+    case ChunkFamily::chunk:
+      snprintf(buf, len, "gcn::spmm_chunk_kernel<%d, %d, %s, %s>", c.vec, c.U, tf(c.epi), tf(c.buf));
+      break;
+    case ChunkFamily::refused: snprintf(buf, len, "(none: launch_spmm refuses these arguments)"); break;
+  }
+}
 
 hipError_t launch_spmm(const SpmmArgs& a, int cu_count, hipStream_t s) {
-  const bool epi = (a.bias != nullptr) || a.relu;
   if (a.m <= 0 || a.k <= 0) return hipSuccess;
+  const ChunkChoice c = spmm_chunk_choice(a);
   const int ng = a.nchunks_grid;          // chunk count the grids are sized for (>= actual)
-  if (ng == 0) {
+  if (c.family == ChunkFamily::empty) {
     const long long total = (long long)a.m * a.k;
     int nb = (int)((total + 255) / 256);
     if (nb > 4096) nb = 4096;
@@ -510,59 +534,27 @@ hipError_t launch_spmm(const SpmmArgs& a, int cu_count, hipStream_t s) {
   // the empty rows first (the main kernels never write them), outside the timed interval of the main kernel
   if (a.empty_rows != 0 && (e = launch_fill_empty_rows(a.rowptr, a.C, a.bias, a.relu, a.accumulate, a.m, a.k, s)) != hipSuccess) return e;
   if (a.ev_start && (e = hipEventRecord(a.ev_start, s)) != hipSuccess) return e;
-  if (a.valless && !use_quad(a)) return hipErrorInvalidValue;
-  if (use_quad(a)) {
-    // 16-byte-per-lane gathers, 4 (k > 16) or 16 (k <= 16) non-zeros per instruction (spmm_quad.hip)
-    e = launch_spmm_quad(a, nblocks, epi, s);
-  } else if (a.k <= 16 && (a.ldb == 0 || a.ldb == a.k)) {
-    // k <= 16 without the alignment the quad kernel needs: several non-zeros per 4-byte-per-lane gather
-    e = launch_spmm_narrow(a, nblocks, epi, s);
-  } else switch (pick_vec(a.k, a.tile_cols, a.B, a.C, a.P)) {
-    case 4:  e = launch_main<4, 4>(a, nblocks, epi, s); break;
-    case 2:  e = launch_main<2, 8>(a, nblocks, epi, s); break;
-    default:
-      // 32 gathers in flight per wave for the 64-column tile (measured on the sliced Reddit-shaped case, whole SpMM:
-      // U = 4 / 8 / 16 / 32 -> 5.16 / 4.33 / 4.18 / 4.09 ms; 52 VGPRs at U = 32, still 8 waves per SIMD)
-      e = launch_main<1, 32>(a, nblocks, epi, s);
+  switch (c.family) {
+    case ChunkFamily::quad:         e = launch_spmm_quad(a, c, nblocks, s); break;
+    case ChunkFamily::narrow:
+    case ChunkFamily::narrow16_dpp: e = launch_spmm_narrow(a, c, nblocks, s); break;
+    case ChunkFamily::chunk:
+      e = c.vec == 4 ? launch_main<4, 4>(a, c, nblocks, s)
+        : c.vec == 2 ? launch_main<2, 8>(a, c, nblocks, s) : launch_main<1, 32>(a, c, nblocks, s);
       break;
+    default: return hipErrorInvalidValue;  // refused
   }
   if (e != hipSuccess) return e;
   if (a.ev_stop && (e = hipEventRecord(a.ev_stop, s)) != hipSuccess) return e;
   if (ng > 1) {
     const int nb = (ng - 1 + 3) / 4;
-    if (epi) spmm_fixup_kernel<true><<<nb, 256, 0, s>>>(a.rowptr, a.P, a.C, a.chunk_row, a.bias,
-                                                        a.nnz_dev, a.relu, a.nchunks, a.T, a.k, a.accumulate);
-    else     spmm_fixup_kernel<false><<<nb, 256, 0, s>>>(a.rowptr, a.P, a.C, a.chunk_row, a.bias,
-                                                         a.nnz_dev, a.relu, a.nchunks, a.T, a.k, a.accumulate);
+    if (c.epi) spmm_fixup_kernel<true><<<nb, 256, 0, s>>>(a.rowptr, a.P, a.C, a.chunk_row, a.bias,
+                                                          a.nnz_dev, a.relu, a.nchunks, a.T, a.k, a.accumulate);
+    else       spmm_fixup_kernel<false><<<nb, 256, 0, s>>>(a.rowptr, a.P, a.C, a.chunk_row, a.bias,
+                                                           a.nnz_dev, a.relu, a.nchunks, a.T, a.k, a.accumulate);
     e = hipGetLastError();
   }
   return e;
-}
-
-// Name (as rocprofv3 prints it) of the main kernel launch_spmm picks for these arguments; mirrors the
-// selection above.  Used by gcn_spmm_plan_main_kernel so that a benchmark reports the kernel that runs.
-void describe_main_kernel(const SpmmArgs& a, char* buf, size_t len) {
-  const bool epi = (a.bias != nullptr) || a.relu;
-  const char* e = epi ? "true" : "false";
-  const bool buf32 = (unsigned long long)a.n * (unsigned long long)(a.ldb > 0 ? a.ldb : a.k) * 4ull < 0xFFFFFFF0ull;
-  if (a.nchunks_grid == 0) { snprintf(buf, len, "gcn::spmm_empty_kernel"); return; }
-  if (use_quad(a)) {
-    snprintf(buf, len, "gcn::spmm_quad_kernel<%d, %s, %s, %s>", spmm_quad_lanes(a.k), e, a.valless ? "true" : "false",
-             a.col16 ? "true" : "false");
-    return;
-  }
-  if (a.k <= 16 && (a.ldb == 0 || a.ldb == a.k)) {
-    if (a.k > 8 && buf32 && a.n < (1 << 24)) snprintf(buf, len, "gcn::spmm_narrow16_dpp_kernel<%s>", e);
-    else {
-      const int g = a.k <= 4 ? 4 : (a.k <= 8 ? 8 : 16);
-      snprintf(buf, len, "gcn::spmm_narrow_kernel<%d, %d, %s, %s>", g, g, e, buf32 ? "true" : "false");
-    }
-    return;
-  }
-  const int vec = pick_vec(a.k, a.tile_cols, a.B, a.C, a.P);
-  if (vec == 4) { snprintf(buf, len, "gcn::spmm_chunk_kernel<4, 4, %s, false>", e); return; }
-  if (vec == 2) { snprintf(buf, len, "gcn::spmm_chunk_kernel<2, 8, %s, false>", e); return; }
-  snprintf(buf, len, "gcn::spmm_chunk_kernel<1, 32, %s, %s>", e, buf32 ? "true" : "false");
 }
 
 // dst[r, 0:k] = src[r, 0:k], dst[r, k:ld] = 0: feature rows re-laid on whole 128-byte lines

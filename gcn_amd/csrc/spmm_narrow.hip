@@ -1,10 +1,10 @@
-// spmm_narrow.hip — the SpMM kernel for narrow feature widths, k <= 32 (GCN hidden / class sizes;
+// spmm_narrow.hip — the SpMM kernel for narrow feature widths, k <= 16 (GCN hidden / class sizes;
 // the reference dedicates four of its five kernels to them: flexspmm.cu:17-422, k4/k8/k16/k32).
 //
-// With k <= 32 a gathered feature row is only 16..128 bytes, so the wide kernel's "one wave
+// With k <= 16 a gathered feature row is only 16..64 bytes, so the wide kernel's "one wave
 // instruction per non-zero" spends its time on instruction issue, not on bytes (measured: every
 // k <= 32 took the same 1.66 ms on the Reddit-shaped graph).  Here a wave instruction covers
-// NPI = 64/G non-zeros at once (G = 4/8/16/32 lanes per non-zero, the power of two >= k):
+// NPI = 64/G non-zeros at once (G = 4/8/16 lanes per non-zero, the power of two >= k):
 //
 //   lane = sub*G + f:  sub = which of the NPI non-zeros of this step, f = feature column.
 //   The column index and value of non-zero (j + sub) come from the coalesced 64-entry block by
@@ -13,16 +13,17 @@
 //   When a row ends — anywhere inside a step — the lanes that belong to it are reduced across
 //   `sub` (log2(NPI) xor-shuffles) and lanes sub == 0 store the k floats.
 //
-// Chunk schedule, partial slab and fix-up are those of spmm_kernels.hip (same plan), so results
+// Chunk schedule, partial slab and fix-up are those of spmm_kernels.hip (same plan; prologue, chunk range and row cursor
+// from chunk_walk.h), so results
 // are deterministic; the summation order inside a row differs from the wide kernel (a tree over
 // `sub` instead of a chain), within the 1e-5 contract.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "spmm_kernels.h"
+#include "chunk_walk.h"
 
 namespace gcn {
 
-__device__ __forceinline__ int nsgpr(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 template <int G, int U, bool EPI, bool BUF>
 __global__ void __launch_bounds__(256)
@@ -33,37 +34,24 @@ spmm_narrow_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                    const int* __restrict__ nnz_dev,
                    int relu, int nchunks, int T, int m, int nnz, int k) {
   constexpr int NPI = 64 / G;                       // non-zeros per gather instruction
-  if (nnz_dev) {                                    // drop-in (flexspmm) mode, see spmm_kernels.hip
-    nnz = *nnz_dev;
-    nchunks = (int)(((long long)nnz + T - 1) / T);
-    val = reinterpret_cast<const float*>(col) + nnz;
-  }
+  dropin_shape(nnz_dev, T, nnz, nchunks, col, val);
   const int lane = threadIdx.x & 63;
-  const int wib  = nsgpr(threadIdx.x >> 6);
+  const int wib  = sgpr(threadIdx.x >> 6);
   const int sub  = lane / G;
   const int f    = lane % G;
   const bool fok = f < k;
 
-  const int xcd           = blockIdx.x & 7;
-  const int wave_in_xcd   = (blockIdx.x >> 3) * 4 + wib;
-  const int waves_per_xcd = (gridDim.x >> 3) * 4;
-  const int c_lo = (int)(((long long)nchunks * xcd) >> 3);
-  const int c_hi = (int)(((long long)nchunks * (xcd + 1)) >> 3);
+  const ChunkRange range(wib, nchunks);
 
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(B), 0, 0xFFFFFFFFu, 0x00020000);
   const unsigned row_bytes = (unsigned)k * 4u;
   const float bias_f = (EPI && bias && fok) ? bias[f] : 0.f;
 
-  for (int c = c_lo + wave_in_xcd; c < c_hi; c += waves_per_xcd) {
+  for (int c = range.first; c < range.c_hi; c += range.stride) {
     const int start = c * T;
     const int end   = (int)min((long long)start + T, (long long)nnz);
-    int r = chunk_row[c];
-    int row_end    = rowptr[r + 1];
-    int row_end_nx = (r + 1 < m) ? rowptr[r + 2] : -1;
-    bool head = rowptr[r] < start;
-    int pos = start;                                // position of the first non-zero not yet summed
-    int last_flush = start;
+    GCN_ROW_WALK_OPEN(rowptr, chunk_row, c, T, m);     // r, row_end, row_end_nx, head, pos, last_flush (chunk_walk.h)
     float acc = 0.f;                                // this lane's (sub, f) partial of the current row
 
     // the current row is complete at `pos`: reduce over sub, write, step to the next row
@@ -81,15 +69,7 @@ spmm_narrow_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
         if (sub == 0 && fok) C[(size_t)r * k + f] = t;
       }
       acc = 0.f;
-      head = false;
-      last_flush = pos;
-      ++r;
-      row_end    = row_end_nx;
-      if (row_end == pos) {                         // row r is empty: jump over the whole run of empty rows
-        r = next_nonempty_row(rowptr, r, m, pos);
-        row_end = (r < m) ? rowptr[r + 1] : -1;
-      }
-      row_end_nx = (r + 1 < m) ? rowptr[r + 2] : -1;
+      GCN_ROW_WALK_NEXT(rowptr, m)
     };
 
     while (pos == row_end) flush();                 // leading empty rows (chunk 0 only)
@@ -166,11 +146,6 @@ spmm_narrow_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
 // gathers for.  Per-lane byte offsets use the 24-bit multiplier (needs n < 2^24 and buffer
 // addressing; otherwise the generic kernel above runs).
 // ---------------------------------------------------------------------------------------------
-template <int UU>
-__device__ __forceinline__ int dpp_row_bcast(int v) {
-  return __builtin_amdgcn_mov_dpp(v, 0x150 + UU, 0xf, 0xf, true);               // row_newbcast:UU
-}
-
 template <bool EPI>
 __global__ void __launch_bounds__(256)
 spmm_narrow16_dpp_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
@@ -180,23 +155,15 @@ spmm_narrow16_dpp_kernel(const int* __restrict__ rowptr, const int* __restrict__
                          const int* __restrict__ nnz_dev,
                          int relu, int nchunks, int T, int m, int nnz, int k) {
   constexpr int NPI = 4;
-  if (nnz_dev) {
-    nnz = *nnz_dev;
-    nchunks = (int)(((long long)nnz + T - 1) / T);
-    val = reinterpret_cast<const float*>(col) + nnz;
-  }
+  dropin_shape(nnz_dev, T, nnz, nchunks, col, val);
   const int lane = threadIdx.x & 63;
-  const int wib  = nsgpr(threadIdx.x >> 6);
+  const int wib  = sgpr(threadIdx.x >> 6);
   const int sub  = lane >> 4;
   const int f    = lane & 15;
   const bool fok = f < k;
   const int tl   = (lane & 15) * 4 + (lane >> 4);   // transposed position this lane loads
 
-  const int xcd           = blockIdx.x & 7;
-  const int wave_in_xcd   = (blockIdx.x >> 3) * 4 + wib;
-  const int waves_per_xcd = (gridDim.x >> 3) * 4;
-  const int c_lo = (int)(((long long)nchunks * xcd) >> 3);
-  const int c_hi = (int)(((long long)nchunks * (xcd + 1)) >> 3);
+  const ChunkRange range(wib, nchunks);
 
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(B), 0, 0xFFFFFFFFu, 0x00020000);
@@ -204,15 +171,10 @@ spmm_narrow16_dpp_kernel(const int* __restrict__ rowptr, const int* __restrict__
   const unsigned foff = (unsigned)f * 4u;
   const float bias_f = (EPI && bias && fok) ? bias[f] : 0.f;
 
-  for (int c = c_lo + wave_in_xcd; c < c_hi; c += waves_per_xcd) {
+  for (int c = range.first; c < range.c_hi; c += range.stride) {
     const int start = c * T;
     const int end   = (int)min((long long)start + T, (long long)nnz);
-    int r = chunk_row[c];
-    int row_end    = rowptr[r + 1];
-    int row_end_nx = (r + 1 < m) ? rowptr[r + 2] : -1;
-    bool head = rowptr[r] < start;
-    int pos = start;
-    int last_flush = start;
+    GCN_ROW_WALK_OPEN(rowptr, chunk_row, c, T, m);     // r, row_end, row_end_nx, head, pos, last_flush (chunk_walk.h)
     float acc = 0.f;
 
     auto flush = [&]() {
@@ -229,15 +191,7 @@ spmm_narrow16_dpp_kernel(const int* __restrict__ rowptr, const int* __restrict__
         if (sub == 0 && fok) C[(size_t)r * k + f] = t;
       }
       acc = 0.f;
-      head = false;
-      last_flush = pos;
-      ++r;
-      row_end    = row_end_nx;
-      if (row_end == pos) {                         // row r is empty: jump over the whole run of empty rows
-        r = next_nonempty_row(rowptr, r, m, pos);
-        row_end = (r < m) ? rowptr[r + 1] : -1;
-      }
-      row_end_nx = (r + 1 < m) ? rowptr[r + 2] : -1;
+      GCN_ROW_WALK_NEXT(rowptr, m)
     };
     // one step = the 4 non-zeros at [pos, pos + n_step)
     auto step = [&](float prod, int n_step) {
@@ -271,8 +225,8 @@ spmm_narrow16_dpp_kernel(const int* __restrict__ rowptr, const int* __restrict__
 
 #define GCN_N16_GATHER(UU)                                                                      \
       {                                                                                         \
-        const int cu = dpp_row_bcast<UU>(cj);                                                   \
-        const float vu = __builtin_bit_cast(float, dpp_row_bcast<UU>(vj));                      \
+        const int cu = quad_bcast<16, UU>(cj);                                                   \
+        const float vu = __builtin_bit_cast(float, quad_bcast<16, UU>(vj));                      \
         const bool ok = (UU * 4 + sub < cnt) && fok;                                            \
         float b = 0.f;                                                                          \
         if (ok) b = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(             \
@@ -304,40 +258,31 @@ spmm_narrow16_dpp_kernel(const int* __restrict__ rowptr, const int* __restrict__
   }
 }
 
-template <int G, int U>
-static hipError_t launch_g(const SpmmArgs& a, int nblocks, bool epi, bool buf, hipStream_t s) {
-#define GCN_NARROW_ARGS a.rowptr, a.col, a.val, a.B, a.C, a.P, a.chunk_row, a.bias, a.nnz_dev, \
-                        a.relu, a.nchunks, a.T, a.m, a.nnz, a.k
-  dim3 grid(nblocks), block(256);
-  if (buf) {
-    if (epi) spmm_narrow_kernel<G, U, true, true><<<grid, block, 0, s>>>(GCN_NARROW_ARGS);
-    else     spmm_narrow_kernel<G, U, false, true><<<grid, block, 0, s>>>(GCN_NARROW_ARGS);
+template <int G>
+static hipError_t launch_g(const SpmmArgs& a, const ChunkChoice& c, int nblocks, hipStream_t s) {
+  const dim3 grid(nblocks), block(256);
+  if (c.buf) {
+    if (c.epi) spmm_narrow_kernel<G, G, true, true><<<grid, block, 0, s>>>(GCN_CHUNK_ARGS(a));
+    else       spmm_narrow_kernel<G, G, false, true><<<grid, block, 0, s>>>(GCN_CHUNK_ARGS(a));
   } else {
-    if (epi) spmm_narrow_kernel<G, U, true, false><<<grid, block, 0, s>>>(GCN_NARROW_ARGS);
-    else     spmm_narrow_kernel<G, U, false, false><<<grid, block, 0, s>>>(GCN_NARROW_ARGS);
+    if (c.epi) spmm_narrow_kernel<G, G, true, false><<<grid, block, 0, s>>>(GCN_CHUNK_ARGS(a));
+    else       spmm_narrow_kernel<G, G, false, false><<<grid, block, 0, s>>>(GCN_CHUNK_ARGS(a));
   }
-#undef GCN_NARROW_ARGS
   return hipGetLastError();
 }
 
-// k <= 32 only
-hipError_t launch_spmm_narrow(const SpmmArgs& a, int nblocks, bool epi, hipStream_t s) {
-  const bool buf = (unsigned long long)a.n * (unsigned long long)a.k * 4ull < 0xFFFFFFF0ull;
-  // U gather instructions per batch: one 64-entry (col, val) block per batch where that fits
-  if (a.k <= 4)  return launch_g<4, 4>(a, nblocks, epi, buf, s);
-  if (a.k <= 8)  return launch_g<8, 8>(a, nblocks, epi, buf, s);
-  if (a.k <= 16) {
-    if (a.k > 8 && buf && a.n < (1 << 24) && a.k * 4 < (1 << 24)) {   // DPP + 24-bit offsets
-#define GCN_N16_ARGS a.rowptr, a.col, a.val, a.B, a.C, a.P, a.chunk_row, a.bias, a.nnz_dev, \
-                     a.relu, a.nchunks, a.T, a.m, a.nnz, a.k
-      if (epi) spmm_narrow16_dpp_kernel<true><<<dim3(nblocks), dim3(256), 0, s>>>(GCN_N16_ARGS);
-      else     spmm_narrow16_dpp_kernel<false><<<dim3(nblocks), dim3(256), 0, s>>>(GCN_N16_ARGS);
-#undef GCN_N16_ARGS
-      return hipGetLastError();
-    }
-    return launch_g<16, 16>(a, nblocks, epi, buf, s);
+// G lanes per non-zero and U = G gather instructions per batch: one 64-entry (col, val) block per batch
+hipError_t launch_spmm_narrow(const SpmmArgs& a, const ChunkChoice& c, int nblocks, hipStream_t s) {
+  if (c.family == ChunkFamily::narrow16_dpp) {
+    if (c.epi) spmm_narrow16_dpp_kernel<true><<<dim3(nblocks), dim3(256), 0, s>>>(GCN_CHUNK_ARGS(a));
+    else       spmm_narrow16_dpp_kernel<false><<<dim3(nblocks), dim3(256), 0, s>>>(GCN_CHUNK_ARGS(a));
+    return hipGetLastError();
   }
-  return launch_g<32, 16>(a, nblocks, epi, buf, s);
+  switch (c.lanes) {
+    case 4:  return launch_g<4>(a, c, nblocks, s);
+    case 8:  return launch_g<8>(a, c, nblocks, s);
+    default: return launch_g<16>(a, c, nblocks, s);
+  }
 }
 
 }  // namespace gcn

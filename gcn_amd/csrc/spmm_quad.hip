@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "spmm_kernels.h"
+#include "chunk_walk.h"
 
 namespace gcn {
 
@@ -35,21 +36,7 @@ typedef float f32x4_q __attribute__((ext_vector_type(4)));
 
 typedef const int __attribute__((address_space(4)))* const_int_ptr;
 
-__device__ __forceinline__ int qsgpr(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// The value held by the lane that loaded non-zero (step UU, this lane's sub) of the transposed block.
-//   LPE = 16: lane s*16+u holds entry 4u+s   -> DPP row_newbcast:UU (lane UU of every 16-lane row)
-//   LPE =  4: lane s*4+u  holds entry 16u+s  -> DPP quad_perm [UU,UU,UU,UU]
-// (every lane has a source lane, so bound_ctrl is irrelevant)
-template <int LPE, int UU>
-__device__ __forceinline__ int quad_bcast(int v) {
-  static_assert(LPE == 16 || LPE == 4, "layouts: 16 or 4 lanes per non-zero");
-  if constexpr (LPE == 16) {
-    return __builtin_amdgcn_mov_dpp(v, 0x150 + UU, 0xf, 0xf, true);
-  } else {
-    return __builtin_amdgcn_mov_dpp(v, UU | (UU << 2) | (UU << 4) | (UU << 6), 0xf, 0xf, true);
-  }
-}
+// (quad_bcast<LPE, UU>, the DPP broadcast of the transposed block's entries: chunk_walk.h)
 
 // sum over the subs (lane bits >= log2(LPE))
 template <int LPE>
@@ -90,11 +77,7 @@ spmm_quad_kernel(const int* __restrict__ g_rowptr, const int* __restrict__ g_col
   static_assert(!COL16 || VALLESS, "16-bit columns are only built for the value-free pass");
   const bool accumulate = flags & 1;                // C += ...
   const bool stream_rows = flags & 2;               // finished rows leave with non-temporal stores (SpmmArgs::stream_rows)
-  if (nnz_dev) {                                    // drop-in (flexspmm) mode, see spmm_kernels.hip
-    nnz = *nnz_dev;
-    nchunks = (int)(((long long)nnz + T - 1) / T);
-    g_val = reinterpret_cast<const float*>(g_col) + nnz;
-  }
+  dropin_shape(nnz_dev, T, nnz, nchunks, g_col, g_val);
   // Row pointers and chunk rows are read through the CONSTANT address space: wave-uniform loads
   // from it always go through the scalar cache (s_load_dword), which keeps row_end / pos in SGPRs.
   // (The kernel is too large for the compiler to prove by itself that its stores to C / P never
@@ -106,7 +89,7 @@ spmm_quad_kernel(const int* __restrict__ g_rowptr, const int* __restrict__ g_col
   } a = {(const_int_ptr)(uintptr_t)g_rowptr, g_col, g_val, g_B, g_C, g_P,
          (const_int_ptr)(uintptr_t)g_chunk_row, g_bias};
   const int lane = threadIdx.x & 63;
-  const int wib  = qsgpr(threadIdx.x >> 6);
+  const int wib  = sgpr(threadIdx.x >> 6);
   constexpr int EPS = 64 / LPE;                     // non-zeros per step (= per gather instruction)
   const int sub  = lane / LPE;
   const int f    = lane % LPE;
@@ -115,11 +98,7 @@ spmm_quad_kernel(const int* __restrict__ g_rowptr, const int* __restrict__ g_col
   const bool writer = fok && sub == 0;
   const int tl   = f * EPS + sub;                   // transposed position this lane loads
 
-  const int xcd           = blockIdx.x & 7;
-  const int wave_in_xcd   = (blockIdx.x >> 3) * 4 + wib;
-  const int waves_per_xcd = (gridDim.x >> 3) * 4;
-  const int c_lo = (int)(((long long)nchunks * xcd) >> 3);
-  const int c_hi = (int)(((long long)nchunks * (xcd + 1)) >> 3);
+  const ChunkRange range(wib, nchunks);
 
   const unsigned row_bytes = (unsigned)ldb * 4u;    // B row stride (>= k: rows may be padded to 128-byte lines)
   // lanes past k gather the tile's first four columns of the same rows (valid memory, a cache line
@@ -132,15 +111,10 @@ spmm_quad_kernel(const int* __restrict__ g_rowptr, const int* __restrict__ g_col
     if (a.bias && fok) bias4 = *reinterpret_cast<const float4*>(a.bias + fcol);
   }
 
-  for (int c = c_lo + wave_in_xcd; c < c_hi; c += waves_per_xcd) {
+  for (int c = range.first; c < range.c_hi; c += range.stride) {
     const int start = c * T;
     const int end   = (int)min((long long)start + T, (long long)nnz);
-    int r = a.chunk_row[c];
-    int row_end    = a.rowptr[r + 1];
-    int row_end_nx = (r + 1 < m) ? a.rowptr[r + 2] : -1;
-    bool head = a.rowptr[r] < start;
-    int pos = start;
-    int last_flush = start;
+    GCN_ROW_WALK_OPEN(a.rowptr, a.chunk_row, c, T, m);     // r, row_end, row_end_nx, head, pos, last_flush (chunk_walk.h)
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);   // this lane's (sub, f) partial of the current row
 
     auto flush = [&]() {
@@ -162,15 +136,7 @@ spmm_quad_kernel(const int* __restrict__ g_rowptr, const int* __restrict__ g_col
         }
       }
       acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      head = false;
-      last_flush = pos;
-      ++r;
-      row_end    = row_end_nx;
-      if (row_end == pos) {                         // row r is empty: jump over the whole run of empty rows
-        r = next_nonempty_row(a.rowptr, r, m, pos);
-        row_end = (r < m) ? a.rowptr[r + 1] : -1;
-      }
-      row_end_nx = (r + 1 < m) ? a.rowptr[r + 2] : -1;
+      GCN_ROW_WALK_NEXT(a.rowptr, m)
     };
     while (pos == row_end) flush();                 // leading empty rows (chunk 0 only)
 
@@ -263,39 +229,32 @@ bool spmm_quad_eligible(const SpmmArgs& a) {
 }
 
 template <int LPE>
-static hipError_t launch_quad(const SpmmArgs& a, int nblocks, bool epi, hipStream_t s) {
+static hipError_t launch_quad(const SpmmArgs& a, const ChunkChoice& c, int nblocks, hipStream_t s) {
   const int tiles = (a.k + 4 * LPE - 1) / (4 * LPE);
   QuadSlices sl{};
-  if (a.col16) {
+  if (c.col16) {
     sl.S = a.col16_S; sl.w = a.col16_w;
     for (int i = 0; i < 9; ++i) sl.start[i] = a.col16_start[i];
   }
+  const dim3 grid(nblocks), block(256);
   for (int t = 0; t < tiles; ++t) {
-#define GCN_QUAD_ARGS a.rowptr, a.col, a.val, a.B, a.C, a.P, a.chunk_row, a.bias, a.nnz_dev, \
-                      a.relu, a.nchunks, a.T, a.m, a.nnz, a.k, t, (a.accumulate ? 1 : 0) | (a.stream_rows ? 2 : 0), (a.ldb > 0 ? a.ldb : a.k), sl, a.n
-    if constexpr (LPE == 16) {
-      if (a.valless && !epi) {                       // (the value-free variants are only built for the sliced main pass)
-        if (a.col16) spmm_quad_kernel<LPE, false, true, true><<<dim3(nblocks), dim3(256), 0, s>>>(GCN_QUAD_ARGS);
-        else         spmm_quad_kernel<LPE, false, true, false><<<dim3(nblocks), dim3(256), 0, s>>>(GCN_QUAD_ARGS);
+#define GCN_QUAD_ARGS GCN_CHUNK_ARGS(a), t, (a.accumulate ? 1 : 0) | (a.stream_rows ? 2 : 0), (a.ldb > 0 ? a.ldb : a.k), sl, a.n
+    if constexpr (LPE == 16) {                       // (the value-free variants: spmm_chunk_choice refuses every other shape)
+      if (c.valless) {
+        if (c.col16) spmm_quad_kernel<LPE, false, true, true><<<grid, block, 0, s>>>(GCN_QUAD_ARGS);
+        else         spmm_quad_kernel<LPE, false, true, false><<<grid, block, 0, s>>>(GCN_QUAD_ARGS);
         continue;
       }
     }
-    if (a.valless || a.col16) return hipErrorInvalidValue;   // a caller bug: B was prepared for a kernel that is not there
-    if (epi) spmm_quad_kernel<LPE, true, false, false><<<dim3(nblocks), dim3(256), 0, s>>>(GCN_QUAD_ARGS);
-    else     spmm_quad_kernel<LPE, false, false, false><<<dim3(nblocks), dim3(256), 0, s>>>(GCN_QUAD_ARGS);
+    if (c.epi) spmm_quad_kernel<LPE, true, false, false><<<grid, block, 0, s>>>(GCN_QUAD_ARGS);
+    else       spmm_quad_kernel<LPE, false, false, false><<<grid, block, 0, s>>>(GCN_QUAD_ARGS);
 #undef GCN_QUAD_ARGS
   }
   return hipGetLastError();
 }
 
-// lanes per non-zero for a k-wide SpMM: the narrowest layout whose tile (4*LPE columns) covers k
-int spmm_quad_lanes(int k) { return k <= 16 ? 4 : 16; }
-
-hipError_t launch_spmm_quad(const SpmmArgs& a, int nblocks, bool epi, hipStream_t s) {
-  switch (spmm_quad_lanes(a.k)) {
-    case 4:  return launch_quad<4>(a, nblocks, epi, s);
-    default: return launch_quad<16>(a, nblocks, epi, s);
-  }
+hipError_t launch_spmm_quad(const SpmmArgs& a, const ChunkChoice& c, int nblocks, hipStream_t s) {
+  return c.lanes == 4 ? launch_quad<4>(a, c, nblocks, s) : launch_quad<16>(a, c, nblocks, s);
 }
 
 }  // namespace gcn

@@ -71,6 +71,15 @@ def _gather(width):
     return make
 
 
+def _tile(cols):
+    """one non-zero per gather on a 128- / 256-column tile: the 2- and 4-float-per-lane chunk kernels"""
+    def make():
+        adj = _gather(1)()
+        adj.set_tile_cols(cols)
+        return adj
+    return make
+
+
 def _c():
     adj = _adj(_graph("norm"), 17000, 17000)
     adj.prepare_width(16)                                # (one slice of 128-byte rows fits an L2: no narrow set to build)
@@ -141,6 +150,19 @@ def _unsliced(adj):
     _is(("spmm_chunk_kernel", "spmm_quad_kernel"))(adj)
 
 
+def _narrow_4_and_8(adj):
+    _unsliced(adj)
+    assert adj.main_kernel(3) == "gcn::spmm_narrow_kernel<4, 4, false, true>", adj.main_kernel(3)
+    assert adj.main_kernel(7) == "gcn::spmm_narrow_kernel<8, 8, false, true>", adj.main_kernel(7)
+
+
+def _chunk_tile(vec, u, k):
+    def check(adj):
+        assert adj.num_slices == 0 and adj.panel_rows == 0
+        assert adj.main_kernel(k) == f"gcn::spmm_chunk_kernel<{vec}, {u}, false, false>", adj.main_kernel(k)
+    return check
+
+
 def _group_free(adj):
     assert adj.num_slices >= 2 and adj.has_value_factors
     _is(("spmm_group",), weighted=False)(adj)
@@ -200,6 +222,10 @@ CONFIGS = {
     "h_mutable": (lambda: _adj(_graph("mid"), 6000, 6000, slices=3, mutable_values=True), _mutable, DIGEST_WIDTHS),
     "i_empty": (_empty, _nothing, DIGEST_WIDTHS),
     "i_no_rows": (_no_rows, _nothing, DIGEST_WIDTHS),
+    # (recorded at meta.commit_chunk_walk: widths below 8 and the 128- / 256-column tiles, which the rows above do not call)
+    "j_unsliced_narrow": (_a, _narrow_4_and_8, (1, 2, 3, 4, 5, 7), ()),
+    "k_gather1_tile128": (_tile(128), _chunk_tile(2, 8, 128), (128, 130, 256), ()),
+    "l_gather1_tile256": (_tile(256), _chunk_tile(4, 4, 256), (256, 260), ()),
 }
 
 
@@ -240,6 +266,11 @@ def record(name):
         rng = np.random.default_rng(77)
         features = torch.from_numpy(rng.standard_normal((adj.n, max(DIGEST_WIDTHS))).astype(np.float32)).to(_dev())
         bias = torch.from_numpy(rng.standard_normal(max(DIGEST_WIDTHS)).astype(np.float32)).to(_dev())
+        extra = max(widths + bf16_widths + (0,)) - max(DIGEST_WIDTHS)
+        if extra > 0:                                    # columns past the widest of DIGEST_WIDTHS: a stream of their own
+            more = np.random.default_rng(78)
+            features = torch.cat([features, torch.from_numpy(more.standard_normal((adj.n, extra)).astype(np.float32)).to(_dev())], 1)
+            bias = torch.cat([bias, torch.from_numpy(more.standard_normal(extra).astype(np.float32)).to(_dev())])
         results = {f"f32_{k}": _digests(adj, k, torch.float32, features, bias) for k in widths}
         results.update({f"bf16_{k}": _digests(adj, k, BF16, features, bias) for k in bf16_widths})
         after = [dict(k=k, main_kernel=adj.main_kernel(k), narrow_slices_for=adj.narrow_slices_for(k)) for k in (16, 32, 64)]
