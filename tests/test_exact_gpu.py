@@ -342,8 +342,9 @@ def test_exact_epilogue(case):
     (scale 2 exactly), offset 11, the mask of util.dropout_keep; C starts as NaN.  tests/test_exact_cpu.py proves on these very
     inputs that a result with one step missing or out of order is refused.  A bf16 result equals the reference converted once.
     An explicit slice count builds no narrow slice set, so the k <= 32 cases run on the plan's own slices (asserted).
-    Out of scope: OFF32 = false in the wide reduction (a plane of partial rows of 4 GiB), the pre-laid entry (it has no bias,
-    ReLU or mask argument) and GCN_AMD_GROUP_FUSED_FIXUP=0 (read once per process)."""
+    OFF32 = false in the wide reduction (a plane of partial rows of 4 GiB) runs in tests/test_large_operands_gpu.py, with and
+    without this epilogue.  Out of scope: the pre-laid entry (it has no bias, ReLU or mask argument) and
+    GCN_AMD_GROUP_FUSED_FIXUP=0 (read once per process)."""
     cid, carrier, pattern, kind, k, opt = case
     adj, ops = _epilogue_plan(carrier, pattern, kind, k, opt)
     m = ops["m"]

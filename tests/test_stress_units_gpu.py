@@ -6,7 +6,8 @@ workspace and its retired buffers, the edge workspace, the cached transposes and
 Every comparison is a helper of the unit's own test module with its own bound; an assertion carries the seed, the group, the
 step and the drawn parameters, and ``stress_units.case(seed, group)`` reproduces the inputs on the host.
 
-Not here: the long kernel's second screening window (test_row_dispatch_gpu.py), tables past 4 GiB, rabbit_device."""
+Not here: the long kernel's second screening window (test_row_dispatch_gpu.py), tables past 4 GiB
+(test_large_operands_gpu.py), rabbit_device."""
 import contextlib
 
 import numpy as np

@@ -196,6 +196,18 @@ def dropout_keep(count, p, seed, offset):
     return w >= np.uint64(dropout_threshold(p))
 
 
+def dropout_keep_at(indices, p, seed, offset):
+    """keep[i] of the same contract at the given flat indices (any shape, up to 2^64) without generating the stream before them"""
+    seed, offset = int(seed), int(offset)
+    i = np.asarray(indices).astype(np.uint64)
+    j = i >> np.uint64(2)
+    words = philox4x32_10((j & np.uint64(0xFFFFFFFF), j >> np.uint64(32), offset & 0xFFFFFFFF, offset >> 32),
+                          (seed & 0xFFFFFFFF, seed >> 32))
+    lane = i & np.uint64(3)
+    w = np.select([lane == 0, lane == 1, lane == 2], words[:3], words[3])
+    return w >= np.uint64(dropout_threshold(p))
+
+
 # ---- builders, references and bounds that more than one test module uses ----
 def banded_csr(n, half_band, extra, seed, hub=None):
     """near-diagonal matrix (what a renumbered community graph looks like) + a few far entries"""
