@@ -455,8 +455,11 @@ static void flexspmm_group(const int* seg_rowPtr, const float* segNzCV, const in
   ga.table_rows = table_rows;
   FLEX_TRY(gcn::launch_spmm_group(ga, st), "main kernel launch");
   FLEX_TRY(gcn::launch_group_fixup(seg_rowPtr + g.fix_off, g.nchunks_ub, scratch.ws, scratch.cv, kc, st, dyn), "fix-up launch");
-  float* Cc = kc != k ? scratch.cpad.get() : C;
-  FLEX_TRY(gcn::launch_slice_reduce(scratch.cv, Cc, nullptr, 0, m, g.S, kc, st, 0, u, gcn::DropoutSpec{}, dyn), "slice reduction launch");
+  gcn::SliceReduce red;
+  red.Cv = scratch.cv; red.C = kc != k ? scratch.cpad.get() : C;
+  red.m = m; red.S = g.S; red.k = kc;
+  red.rowscale = u; red.guard = dyn;
+  FLEX_TRY(gcn::launch_slice_reduce(red, st), "slice reduction launch");
   if (kc != k) FLEX_TRY(gcn::launch_unpad_rows(C, scratch.cpad, nullptr, 0, m, k, kc, st, dyn), "result compaction launch");
 }
 

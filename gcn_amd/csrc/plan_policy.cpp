@@ -400,25 +400,31 @@ SpmmArgs spmm_args(const gcn_spmm_plan* p, const SpmmRoute& r, bool epilogue) {
 // of 128-byte rows, built here at first use like the fp32 k <= 32 one; the five-engine kernel's 48-float rows are an fp32
 // matter only).  Rows of the bf16 table are padded to whole 128-byte lines.  Anything else — unsliced plans, panels,
 // narrow / odd widths — takes the fallback.
-Bf16Route bf16_route(gcn_spmm_plan* p, int k, bool build, const int32_t* rowptr, const int32_t* col, const float* val,
-                     hipStream_t st) {
-  Bf16Route r;
-  if (k < 64 || k % 8 != 0 || p->nnz <= 0 || p->panels.R != 0 || !p->group.ready()) return r;
+bool spmm_route_bf16(gcn_spmm_plan* p, int k, bool build, const int32_t* rowptr, const int32_t* col, const float* val,
+                     hipStream_t st, SpmmRoute* r) {
+  if (k < 64 || k % 8 != 0 || p->nnz <= 0 || p->panels.R != 0 || !p->group.ready()) return false;
   const int ldh = (k + 63) / 64 * 64;
   const int kw = k / 2, ldw = ldh / 2;                 // the fp32 width and stride with the same row bytes
   const PassKind pk = pass_kind(p, kw, ldw, sliced_for(p, kw, true), p->tile_cols ? p->tile_cols : 64);
-  if (!pk.group) return r;
+  if (!pk.group) return false;
   const SliceSet ss = pk.valless ? narrow_slice_set(p, kw, build, rowptr, col, val, st) : own_slice_set(p);
   const GroupStream* g = ss.g;
-  if (!g || !g->ready() || g->nchunks % 32 != 0 || g->T < 64 || g->T % 64 != 0) return r;
-  if (spmm_group_needs_big(ss.table_rows(), ldh * 2LL) && ldh * 2 >= (1 << 17)) return r;
-  r.group = true; r.weighted = pk.weighted; r.ss = ss; r.ldh = ldh;
-  return r;
+  if (!g || !g->ready() || g->nchunks % 32 != 0 || g->T < 64 || g->T % 64 != 0) return false;
+  if (spmm_group_needs_big(ss.table_rows(), ldh * 2LL) && ldh * 2 >= (1 << 17)) return false;
+  *r = SpmmRoute{};
+  r->family = SpmmFamily::group; r->k_run = k; r->elem_bytes = 2; r->ldb = ldh; r->copy = BCopy::group_layout_bf16;
+  r->valless = pk.valless; r->weighted = pk.weighted; r->ss = ss; r->S_run = ss.S; r->reduce_epilogue = true;
+  return true;
 }
 
 // the route as it stands: the reports build nothing
 static SpmmRoute report_route(const gcn_spmm_plan* p, int k, bool prelaid = false) {
   return spmm_route(const_cast<gcn_spmm_plan*>(p), k, /*build=*/false, nullptr, nullptr, nullptr, nullptr, prelaid);
+}
+
+// the kernel a group route's walk runs, fp32 or bf16: the shape run_group_walk (api_spmm.cpp) launches with
+static void group_route_kernel_name(const SpmmRoute& r, char* buf, int buflen) {
+  spmm_group_kernel_name(spmm_group_choice(group_shape(r.ss, r.weighted, r.elem_bytes, r.ldb, r.k_run)), buf, (size_t)buflen);
 }
 
 // only the value-free group pass gathers from a scaled, slice-by-slice copy of B; the layout is that of the plan's OWN
@@ -448,18 +454,17 @@ int gcn_spmm_plan_main_kernel(const gcn_spmm_plan_t* p, int32_t k, int32_t epilo
   if (!p || k <= 0 || !buf || buflen <= 0) return GCN_ERR_INVALID_ARG;
   const SpmmRoute r = report_route(p, k);
   if (r.family == SpmmFamily::panels) snprintf(buf, (size_t)buflen, "gcn::spmm_panel_in_kernel");
-  else if (r.family == SpmmFamily::group)
-    spmm_group_kernel_name(spmm_group_choice(group_shape(r.ss, r.weighted, 4, r.ldb, r.k_run)), buf, (size_t)buflen);
+  else if (r.family == SpmmFamily::group) group_route_kernel_name(r, buf, buflen);
   else spmm_chunk_kernel_name(spmm_chunk_choice(spmm_args(p, r, epilogue != 0)), buf, (size_t)buflen);
   return GCN_OK;
 }
 
 int gcn_spmm_plan_main_kernel_bf16(const gcn_spmm_plan_t* p, int32_t k, int32_t epilogue, char* buf, int32_t buflen) {
   if (!p || k <= 0 || !buf || buflen <= 0) return GCN_ERR_INVALID_ARG;
-  // (the slice set only as it exists: nothing is built here)
-  const Bf16Route r = bf16_route(const_cast<gcn_spmm_plan*>(p), k, /*build=*/false, nullptr, nullptr, nullptr, nullptr);
-  if (!r.group) return gcn_spmm_plan_main_kernel(p, k, epilogue, buf, buflen);    // the fallback runs the fp32 entry
-  spmm_group_kernel_name(spmm_group_choice(group_shape(r.ss, r.weighted, 2, r.ldh, k)), buf, (size_t)buflen);
+  SpmmRoute r;                                         // (the slice set only as it exists: nothing is built here)
+  if (!spmm_route_bf16(const_cast<gcn_spmm_plan*>(p), k, /*build=*/false, nullptr, nullptr, nullptr, nullptr, &r))
+    return gcn_spmm_plan_main_kernel(p, k, epilogue, buf, buflen);                 // the fallback runs the fp32 entry
+  group_route_kernel_name(r, buf, buflen);
   return GCN_OK;
 }
 

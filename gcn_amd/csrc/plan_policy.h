@@ -1,12 +1,18 @@
-// plan_policy.h — what the three translation units behind the native SpMM API share (internal):
+// plan_policy.h — what the translation units behind the native API share (internal):
 //   plan_policy.cpp  the dispatch policy: which kernel family, tile, slice count and slice set a k-wide call takes
 //   plan_build.cpp   plan construction: chunk table, column slicing, streams, value factors, panels
-//   api_spmm.cpp     the C entry points that launch
+//   api_spmm.cpp     the C entry points of the SpMM, the SDDMM and dropout: the ones that read a plan or the epilogue
+//   api_units.cpp    the C entry points of the plan-free units: argument checks in front of one launcher each
 // The public contract is include/gcn_spmm.h.
 #pragma once
 #include "plan.h"
 
 namespace gcn {
+
+inline int hip_status(hipError_t e) { return e == hipSuccess ? GCN_OK : GCN_ERR_HIP; }   // a launcher's error as a status
+// the dropout arguments of the four entry points that take them: the range each checks first (a NaN fails it), the kernels' spec
+inline bool dropout_p_ok(float p) { return p >= 0.f && p < 1.f; }
+inline DropoutSpec dropout_spec(float p, uint64_t seed, uint64_t offset) { return DropoutSpec{p, seed, offset}; }
 
 // thresholds of the policy (measured; the experiments behind them are cited where they are used)
 constexpr int kSliceMinK = 33;          // smallest k the sliced copy is used for on the four-per-gather kernel
@@ -41,15 +47,17 @@ bool group_plan(const gcn_spmm_plan* p);
 struct OddShape { int k4, ld; bool fits; };
 OddShape odd_width_shape(long long n, int k);
 
-// How ONE k-wide fp32 call runs: decided once (spmm_route), consumed by the launch (api_spmm.cpp) and printed by the
-// reports (gcn_spmm_plan_num_passes / _main_kernel / _prelaid_layout).  DESIGN.md §4.19 lists who reads what.
+// How ONE k-wide call runs, fp32 (spmm_route) or on the bf16 hot path (spmm_route_bf16): decided once, consumed by the
+// launch (api_spmm.cpp) and printed by the reports (gcn_spmm_plan_num_passes / _main_kernel / _main_kernel_bf16 /
+// _prelaid_layout).  DESIGN.md §4.19 lists who reads what.
 enum class SpmmFamily { panels, unsliced, sliced_quad, group };
-enum class BCopy { none, row_padded, group_layout };   // the copy of B the call lays out first
+enum class BCopy { none, row_padded, group_layout, group_layout_bf16 };   // the copy of B the call lays out first
 struct SpmmRoute {
   SpmmFamily family = SpmmFamily::unsliced;
   bool odd = false;                     // computed at k_run = ceil(k / 4) * 4 into a padded result, compacted afterwards
   int k_run = 0;
-  int ldb = 0;                          // row stride B is gathered with (k_run: the caller's own rows)
+  int elem_bytes = 4;                   // of the table the main kernels gather from: fp32, or 2 for a bf16 call's bf16 table
+  int ldb = 0;                          // row stride B is gathered with, in table elements (k_run: the caller's own rows)
   BCopy copy = BCopy::none;             // (a value-free route's copy has its rows multiplied by u_col)
   bool valless = false, weighted = false, col16 = false;
   SliceSet ss;                          // the slice set a group launch walks
@@ -66,16 +74,10 @@ SpmmArgs spmm_args(const gcn_spmm_plan* p, const SpmmRoute& r, bool epilogue);
 // the route of a call that hands B over pre-laid (k % 4 == 0), or GCN_ERR_INVALID_ARG: the plan has no such layout for k
 int spmm_route_prelaid(const gcn_spmm_plan* p, int k, SpmmRoute* r);
 
-// How a bf16 call at width k runs (api_spmm.cpp, gcn_spmm_csr_bf16_epilogue): on the bf16 group walk (group = true) —
-// value-free or weighted, on the slice set an fp32 call with the same table row BYTES would take (k / 2 columns), from a
-// bf16 table with rows of ldh columns — or, group = false, on the fallback (B widened to fp32, the fp32 entry, C narrowed).
-struct Bf16Route {
-  bool group = false, weighted = false;
-  SliceSet ss;
-  int ldh = 0;
-};
-Bf16Route bf16_route(gcn_spmm_plan* p, int k, bool build, const int32_t* rowptr, const int32_t* col, const float* val,
-                     hipStream_t st);
+// true, *r: the route of a bf16 call at width k on the bf16 group walk (the rule stands at the definition); false: the
+// fallback (B widened to fp32, the fp32 entry, C narrowed)
+bool spmm_route_bf16(gcn_spmm_plan* p, int k, bool build, const int32_t* rowptr, const int32_t* col, const float* val,
+                     hipStream_t st, SpmmRoute* r);
 
 // plan_build.cpp
 int count_empty(const int* rowptr, int m, int* out, hipStream_t st);

@@ -87,11 +87,11 @@ slice_scatter_kernel(const int* __restrict__ rowptr, const int* __restrict__ col
   }
 }
 
-// C[r, :] = act( [C[r, :] +] sum_s Cv[s*m + r, :] + bias ), partials added in slice order; wave per row
+// C[r, :] = act( sum_s Cv[s*m + r, :] + bias ), partials added in slice order; wave per row
 template <int VEC>
 __global__ void __launch_bounds__(256)
 slice_reduce_kernel(const float* __restrict__ Cv, float* __restrict__ C,
-                    const float* __restrict__ bias, int relu, int m, int S, int k, int accumulate,
+                    const float* __restrict__ bias, int relu, int m, int S, int k,
                     const float* __restrict__ rowscale, DropoutSpec drop, const int* __restrict__ guard,
                     const float* __restrict__ outscale, int gap_w, CutLists cuts) {
   if (guard && *guard == 0) return;
@@ -125,11 +125,6 @@ slice_reduce_kernel(const float* __restrict__ Cv, float* __restrict__ C,
       if (rowscale) {
 #pragma unroll
         for (int i = 0; i < VEC; ++i) acc[i] *= rs;
-      }
-      if (accumulate) {                             // C already holds another part of the product
-        const float* o = C + orow * (size_t)k + x;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] += o[i];
       }
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
@@ -172,7 +167,7 @@ typedef float slice_f32x4 __attribute__((ext_vector_type(4)));
 template <bool DROP, bool OFF32>
 __global__ void __launch_bounds__(256)
 slice_reduce_wide_kernel(const float* __restrict__ Cv, float* __restrict__ C,
-                         const float* __restrict__ bias, int relu, int m, int S, int k, int accumulate,
+                         const float* __restrict__ bias, int relu, int m, int S, int k,
                          const float* __restrict__ rowscale, DropoutSpec drop, const int* __restrict__ guard,
                          const float* __restrict__ outscale, int gap_w, CutLists cuts) {
   if (guard && *guard == 0) return;
@@ -230,10 +225,6 @@ slice_reduce_wide_kernel(const float* __restrict__ Cv, float* __restrict__ C,
     // (all-zero, never written) row behind every gap_w rows — already multiplied by the consumer's column factor
     const size_t orow = gap_w > 0 ? (size_t)r + (size_t)(r / gap_w) : (size_t)r;
     float* o = C + orow * (size_t)k + x;
-    if (accumulate) {                                 // C already holds another part of the product
-      const float4 c = *reinterpret_cast<const float4*>(o);
-      acc.x += c.x; acc.y += c.y; acc.z += c.z; acc.w += c.w;
-    }
     if (bias) {
       const float4 b = *reinterpret_cast<const float4*>(bias + x);
       acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w;
@@ -300,25 +291,35 @@ hipError_t build_sliced_csr(const int* rowptr, const int* col, const float* val,
   return hipSuccess;
 }
 
-hipError_t launch_slice_reduce(const float* Cv, float* C, const float* bias, int relu, int m, int S,
-                               int k, hipStream_t st, int accumulate, const float* rowscale, const DropoutSpec& drop,
-                               const int* guard, const float* outscale, int gap_w, const CutLists& cuts) {
+// The one kernel rule of the slice reduction (SliceReduce, spmm_kernels.h).  bf16 result: slice_reduce_bf16_kernel.  fp32: the
+// wide kernel for k % 4 == 0, k <= 256 and 16-byte aligned Cv | C | bias | cuts.P; beyond 256 columns <4>; anything else <1>.
+hipError_t launch_slice_reduce(const SliceReduce& r, hipStream_t st) {
+  const int m = r.m, k = r.k;
   if (m <= 0 || k <= 0) return hipSuccess;
+  if (r.c_dtype == kDtypeBf16) {
+    if (k % 4 != 0 || (((uintptr_t)r.Cv | (uintptr_t)r.cuts.P) & 15) != 0 || r.outscale || r.gap_w || r.guard)
+      return hipErrorInvalidValue;
+    const long long nb = ((long long)m * (k / 4) + 255) / 256;
+    return enqueue_slice_reduce_bf16(r, (int)(nb > 65536 ? 65536 : nb), /*vec_out=*/((uintptr_t)r.C & 7) == 0 ? 1 : 0, st);
+  }
+  float* const C = static_cast<float*>(r.C);
   int nb = (m + 3) / 4;
   if (nb > 8192) nb = 8192;
-  const uintptr_t al = (uintptr_t)Cv | (uintptr_t)C | (uintptr_t)bias | (uintptr_t)cuts.P;
+  const uintptr_t al = (uintptr_t)r.Cv | (uintptr_t)C | (uintptr_t)r.bias | (uintptr_t)r.cuts.P;
+#define GCN_REDUCE_ARGS r.Cv, C, r.bias, r.relu, m, r.S, k, r.rowscale, r.drop, r.guard, r.outscale, r.gap_w, r.cuts
   if (k % 4 == 0 && k <= 256 && (al & 15) == 0) {
     const long long steps = ((long long)m + 256 / k - 1) / (256 / k);   // wave steps of 256 / k rows (1 KiB when k divides 256)
     const int cap = 16384;
     const int nbw = (int)(steps / 4 + 1 < cap ? steps / 4 + 1 : cap);
     const bool off32 = (size_t)m * (size_t)k * 4 < (1ull << 32);   // a lane's byte offset inside a plane of partial rows
     // (62 VGPRs: eight waves per SIMD, and the kernel wants them all — 344 / 357 / 374 / 399 us at 8 / 7 / 5 / 4, profiles/r03am_*)
-#define GCN_RW(D, O) slice_reduce_wide_kernel<D, O><<<nbw, 256, 0, st>>>(Cv, C, bias, relu, m, S, k, accumulate, rowscale, drop, guard, outscale, gap_w, cuts)
-    if (drop.on()) { if (off32) GCN_RW(true, true); else GCN_RW(true, false); }
-    else           { if (off32) GCN_RW(false, true); else GCN_RW(false, false); }
+#define GCN_RW(D, O) slice_reduce_wide_kernel<D, O><<<nbw, 256, 0, st>>>(GCN_REDUCE_ARGS)
+    if (r.drop.on()) { if (off32) GCN_RW(true, true); else GCN_RW(true, false); }
+    else             { if (off32) GCN_RW(false, true); else GCN_RW(false, false); }
 #undef GCN_RW
-  } else if (k % 4 == 0 && (al & 15) == 0) slice_reduce_kernel<4><<<nb, 256, 0, st>>>(Cv, C, bias, relu, m, S, k, accumulate, rowscale, drop, guard, outscale, gap_w, cuts);
-  else                              slice_reduce_kernel<1><<<nb, 256, 0, st>>>(Cv, C, bias, relu, m, S, k, accumulate, rowscale, drop, guard, outscale, gap_w, cuts);
+  } else if (k % 4 == 0 && (al & 15) == 0) slice_reduce_kernel<4><<<nb, 256, 0, st>>>(GCN_REDUCE_ARGS);
+  else                                     slice_reduce_kernel<1><<<nb, 256, 0, st>>>(GCN_REDUCE_ARGS);
+#undef GCN_REDUCE_ARGS
   return hipGetLastError();
 }
 

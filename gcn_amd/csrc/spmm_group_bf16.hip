@@ -112,8 +112,8 @@ hipError_t launch_relay_bf16_sliced(unsigned short* dst, const unsigned short* s
   return hipGetLastError();
 }
 
-// ---- slice reduction with a bf16 result: the S partial rows in slice order, then the cut-row pieces in chunk order (the
-// order of slice_reduce_wide_kernel), row factor, bias, ReLU, the dropout mask of element r*k + x, one RNE rounding
+// ---- slice reduction with a bf16 result (launch_slice_reduce, slicing.hip): the S partial rows in slice order, then the cut-row
+// pieces in chunk order (as slice_reduce_wide_kernel), row factor, bias, ReLU, the dropout mask of element r*k + x, one RNE rounding
 template <bool DROP>
 __global__ void __launch_bounds__(256)
 slice_reduce_bf16_kernel(const float* __restrict__ Cv, unsigned short* __restrict__ C, const float* __restrict__ bias, int relu,
@@ -152,15 +152,10 @@ slice_reduce_bf16_kernel(const float* __restrict__ Cv, unsigned short* __restric
   }
 }
 
-hipError_t launch_slice_reduce_bf16(const float* Cv, unsigned short* C, const float* bias, int relu, int m, int S, int k,
-                                    const float* rowscale, const DropoutSpec& drop, const CutLists& cuts, hipStream_t st) {
-  if (m <= 0 || k <= 0) return hipSuccess;
-  if (k % 4 != 0 || (((uintptr_t)Cv | (uintptr_t)cuts.P) & 15) != 0) return hipErrorInvalidValue;
-  const int vec_out = ((uintptr_t)C & 7) == 0 ? 1 : 0;
-  long long nb = ((long long)m * (k / 4) + 255) / 256;
-  if (nb > 65536) nb = 65536;
-  if (drop.on()) slice_reduce_bf16_kernel<true><<<(int)nb, 256, 0, st>>>(Cv, C, bias, relu, m, S, k, rowscale, drop, cuts, vec_out);
-  else           slice_reduce_bf16_kernel<false><<<(int)nb, 256, 0, st>>>(Cv, C, bias, relu, m, S, k, rowscale, drop, cuts, vec_out);
+hipError_t enqueue_slice_reduce_bf16(const SliceReduce& r, int nblocks, int vec_out, hipStream_t st) {
+  unsigned short* const C = static_cast<unsigned short*>(r.C);
+  if (r.drop.on()) slice_reduce_bf16_kernel<true><<<nblocks, 256, 0, st>>>(r.Cv, C, r.bias, r.relu, r.m, r.S, r.k, r.rowscale, r.drop, r.cuts, vec_out);
+  else             slice_reduce_bf16_kernel<false><<<nblocks, 256, 0, st>>>(r.Cv, C, r.bias, r.relu, r.m, r.S, r.k, r.rowscale, r.drop, r.cuts, vec_out);
   return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
-// Internal interface between the C-ABI layer (plan_policy.cpp, plan_build.cpp, api_spmm.cpp, api_dropin.cpp) and the device code
-// (spmm_kernels.hip).  Not installed; the public contract is include/gcn_spmm.h.
+// Internal interface between the C-ABI layer (plan_policy.cpp, plan_build.cpp, api_spmm.cpp, api_units.cpp, api_dropin.cpp)
+// and the device code (spmm_kernels.hip).  Not installed; the public contract is include/gcn_spmm.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -380,15 +380,25 @@ struct CutLists {
   const int* chunk = nullptr;    // [ptr[m]]
   const float* P = nullptr;      // the piece slab of the launch (GroupArgs::P)
 };
-hipError_t launch_slice_reduce(const float* Cv, float* C, const float* bias, int relu, int m, int S,
-                               int k, hipStream_t st, int accumulate = 0, const float* rowscale = nullptr,
-                               const DropoutSpec& drop = DropoutSpec{}, const int* guard = nullptr,   // guard: skip when *guard == 0
-                               const float* outscale = nullptr, int gap_w = 0,    // pre-laid output: row r -> r + r / gap_w, times outscale[r]
-                               const CutLists& cuts = CutLists{});
-// launch_slice_reduce with a bf16 result (k % 4 == 0; no accumulate / pre-laid output): the same sums in the same order,
-// the same epilogue, one RNE rounding at the end
-hipError_t launch_slice_reduce_bf16(const float* Cv, unsigned short* C, const float* bias, int relu, int m, int S, int k,
-                                    const float* rowscale, const DropoutSpec& drop, const CutLists& cuts, hipStream_t st);
+// One slice reduction: C[r, :] = dropout(act(rowscale[r] * (sum_s Cv[s*m + r, :] + the row's cut pieces) + bias)), the
+// partial rows added in slice order, then the pieces in chunk order.
+constexpr int kDtypeF32 = 0, kDtypeBf16 = 1;          // GCN_DTYPE_F32 / GCN_DTYPE_BF16
+struct SliceReduce {
+  const float* Cv = nullptr;         // partial rows [S*m x k]
+  void* C = nullptr;                 // [m x k] of c_dtype; bf16: the same sums and epilogue, one RNE rounding at the end
+  int c_dtype = kDtypeF32;
+  const float* bias = nullptr;       // [k] or null
+  int relu = 0, m = 0, S = 0, k = 0;
+  const float* rowscale = nullptr;   // [m] or null: the row factor u_row of a value-free pass
+  DropoutSpec drop;
+  const int* guard = nullptr;        // device word; the kernel does nothing when *guard == 0 (drop-in flexspmm)
+  const float* outscale = nullptr; int gap_w = 0;   // pre-laid output: row r lands in row r + r / gap_w, times outscale[r]
+  CutLists cuts;
+};
+// the one kernel rule (slicing.hip).  A bf16 result needs k % 4 == 0, aligned Cv and cuts.P, no guard and no pre-laid output
+// (else hipErrorInvalidValue); its kernel is in spmm_group_bf16.hip, launched through enqueue_slice_reduce_bf16 once checked.
+hipError_t launch_slice_reduce(const SliceReduce& r, hipStream_t st);
+hipError_t enqueue_slice_reduce_bf16(const SliceReduce& r, int nblocks, int vec_out, hipStream_t st);
 // dst[i] = dropout(src[i]) for i < total, mask from the flat index i (dst may be src)
 hipError_t launch_dropout(float* dst, const float* src, long long total, const DropoutSpec& drop, hipStream_t st);
 // values factor as u[r]*u[c]?  u_out[n] (device), *ok_host = 1 when every stored entry matches within 4 ulp

@@ -204,7 +204,7 @@ def test_panels(name, k):
 # ---- bf16 ----
 @pytest.mark.parametrize("k", [128, 40])
 def test_bf16_operands(k):
-    """hot path (k = 128: bf16 group walk; launch_relay_bf16_sliced's src_vec, launch_slice_reduce_bf16's vec_out — an
+    """hot path (k = 128: bf16 group walk; launch_relay_bf16_sliced's src_vec, launch_slice_reduce's vec_out for a bf16 result — an
     8-byte rule, so 4 halves pass it and fail the 16-byte ones) and fallback (k = 40); bounds of tests/test_bf16_gpu.py"""
     g = _graph("bf16")
     adj = _cached(("plan", "bf16"), lambda: _adj(g, symmetric=True, slices=4))

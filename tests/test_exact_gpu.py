@@ -281,7 +281,7 @@ def _epi_cases():
     for pattern, widths in (("lds", (64, 100)), ("mfma", (36, 64, 128)), ("lds_all", (64, 100))):
         for k in widths:
             c.append((f"panels-{pattern}-k{k}", "panels", pattern, "int", k, {}))
-    # bf16 operands: an fp32 result through launch_slice_reduce (wide kernel), a bf16 one through launch_slice_reduce_bf16
+    # bf16 operands: an fp32 result through launch_slice_reduce (wide kernel), a bf16 one through slice_reduce_bf16_kernel
     # (one rounding after the epilogue); an unsliced plan widens, runs the fp32 entry (EPI in the main kernel) and narrows
     for kind in ("pow2", "int"):
         for k in (64, 128, 136):

@@ -333,6 +333,37 @@ def test_reports_and_results_equal_the_recorded_route_table(table, name):
     assert have["reports_after_the_calls"] == want["reports_after_the_calls"]
 
 
+# The live kernel timing (profile_begin / profile_end) on every family of the launch, both element types: (plan, operand
+# dtype, k, result dtype) -> the event pairs three calls record.  The counts are those of the library of commit 4ca21ae
+# (loaded through GCN_AMD_LIB), which had the fp32 and the bf16 group pass as two copies of the code that arms the events.
+PROFILE_CASES = {
+    "norm-f32-k64": (_c, torch.float32, 64, torch.float32, 3),
+    "norm-f32-k16": (_c, torch.float32, 16, torch.float32, 3),
+    "norm-bf16-k128-f32_result": (_c, BF16, 128, torch.float32, 3),
+    "norm-bf16-k128-bf16_result": (_c, BF16, 128, BF16, 3),
+    "perturbed-weighted-f32-k64": (_d, torch.float32, 64, torch.float32, 3),
+    "short-unsliced-f32-k64": (_a, torch.float32, 64, torch.float32, 3),
+    "banded-panels-f32-k64": (CONFIGS["g_panels"][0], torch.float32, 64, torch.float32, 3),
+    "col16-sliced_quad-f32-k64": (_f16, torch.float32, 64, torch.float32, 3),
+}
+
+
+@pytest.mark.parametrize("name", list(PROFILE_CASES))
+def test_profile_records_one_pair_per_main_launch(name):
+    make, dtype, k, out_dtype, pairs = PROFILE_CASES[name]
+    with torch.cuda.device(_dev()):
+        adj = make()
+        B = torch.from_numpy(np.random.default_rng(5).standard_normal((adj.n, k)).astype(np.float32)).to(_dev()).to(dtype)
+        out = torch.empty((adj.m, k), dtype=out_dtype, device=_dev())
+        adj.profile_begin(8)
+        for _ in range(3):
+            adj.matmul_raw(B, out=out)
+        ms = adj.profile_end()
+        print(name, adj.main_kernel(k, dtype=dtype), "pairs", len(ms), "ms", ms)
+    assert len(ms) == pairs, (name, ms)
+    assert all(np.isfinite(t) and t > 0 for t in ms), (name, ms)
+
+
 def adj_hint(have, key):
     """the kernel the width of a differing digest is reported to run on"""
     k = int(key.split("_")[1])
