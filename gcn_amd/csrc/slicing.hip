@@ -129,7 +129,7 @@ slice_reduce_kernel(const float* __restrict__ Cv, float* __restrict__ C,
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
         if (bias) acc[i] += bias[x + i];
-        if (relu) acc[i] = fmaxf(acc[i], 0.f);
+        if (relu) acc[i] = relu_keep_nan(acc[i]);
       }
       if (drop.on()) {                                  // the dropout mask of the fused epilogue (philox.h)
         const unsigned long long idx = (unsigned long long)r * (unsigned long long)k + (unsigned long long)x;
@@ -229,7 +229,7 @@ slice_reduce_wide_kernel(const float* __restrict__ Cv, float* __restrict__ C,
       const float4 b = *reinterpret_cast<const float4*>(bias + x);
       acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w;
     }
-    if (relu) { acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f); }
+    if (relu) { acc.x = relu_keep_nan(acc.x); acc.y = relu_keep_nan(acc.y); acc.z = relu_keep_nan(acc.z); acc.w = relu_keep_nan(acc.w); }
     if constexpr (DROP)                               // the dropout mask of the fused epilogue (philox.h)
       acc = dropout_apply4(drop, (unsigned long long)r * (unsigned long long)k + (unsigned long long)x, acc);
     if (outscale) { const float os = outscale[r]; acc.x *= os; acc.y *= os; acc.z *= os; acc.w *= os; }

@@ -139,7 +139,7 @@ slice_reduce_bf16_kernel(const float* __restrict__ Cv, unsigned short* __restric
     }
     if (rowscale) { const float rs = rowscale[r]; acc.x *= rs; acc.y *= rs; acc.z *= rs; acc.w *= rs; }
     if (bias) { acc.x += bias[x]; acc.y += bias[x + 1]; acc.z += bias[x + 2]; acc.w += bias[x + 3]; }
-    if (relu) { acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f); }
+    if (relu) { acc.x = relu_keep_nan(acc.x); acc.y = relu_keep_nan(acc.y); acc.z = relu_keep_nan(acc.z); acc.w = relu_keep_nan(acc.w); }
     if constexpr (DROP) acc = dropout_apply4(drop, (unsigned long long)off, acc);
     const unsigned short h0 = f2bf(acc.x), h1 = f2bf(acc.y), h2 = f2bf(acc.z), h3 = f2bf(acc.w);
     if (vec_out) {

@@ -7,6 +7,10 @@
 
 namespace gcn {
 
+// The ReLU of every fused epilogue: max(x, 0) on every number and on +-Inf, NaN kept (fmaxf alone answers 0 to a NaN, and
+// torch.relu, which the fused path stands for, answers NaN).  Same bits as fmaxf(x, 0.f) for every x that is not a NaN.
+__device__ __forceinline__ float relu_keep_nan(float x) { return x != x ? x : fmaxf(x, 0.f); }
+
 struct SpmmArgs {
   const int*   rowptr;     // [m+1] device
   const int*   col;        // [nnz] device

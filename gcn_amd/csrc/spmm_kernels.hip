@@ -180,7 +180,7 @@ spmm_chunk_kernel(const int* __restrict__ g_rowptr, const int* __restrict__ g_co
 #pragma unroll
           for (int i = 0; i < VEC; ++i) {
             acc[i] += bias[i];
-            if (a.relu) acc[i] = fmaxf(acc[i], 0.f);
+            if (a.relu) acc[i] = relu_keep_nan(acc[i]);
           }
         }
         if (active) store_vec<VEC>(a.C + (size_t)r * k + fcol, acc);
@@ -287,7 +287,7 @@ spmm_fixup_kernel(const int* __restrict__ g_rowptr, const float* __restrict__ g_
     if (accumulate) s += a.C[(size_t)r * k + x];
     if (EPI) {
       if (a.bias) s += a.bias[x];
-      if (a.relu) s = fmaxf(s, 0.f);
+      if (a.relu) s = relu_keep_nan(s);
     }
     a.C[(size_t)r * k + x] = s;
   }
@@ -340,7 +340,7 @@ fill_empty_rows_kernel(const int* __restrict__ rowptr, float* __restrict__ C, co
         }
         if (relu) {
 #pragma unroll
-          for (int i = 0; i < VEC; ++i) v[i] = fmaxf(v[i], 0.f);
+          for (int i = 0; i < VEC; ++i) v[i] = relu_keep_nan(v[i]);
         }
         store_vec<VEC>(row + x, v);
       }
@@ -366,7 +366,7 @@ __global__ void spmm_empty_kernel(float* C, const float* bias, int relu, long lo
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (; i < total; i += stride) {
     float s = bias ? bias[i % k] : 0.f;
-    if (relu) s = fmaxf(s, 0.f);
+    if (relu) s = relu_keep_nan(s);
     C[i] = s;
   }
 }
@@ -591,7 +591,7 @@ unpad_rows_kernel(float* __restrict__ dst, const float* __restrict__ src, const 
     const int c = (int)(i - r * k);
     float v = src[r * ld + c];
     if (bias) v += bias[c];
-    if (relu) v = fmaxf(v, 0.f);
+    if (relu) v = relu_keep_nan(v);
     dst[i] = v;
   }
 }

@@ -64,7 +64,7 @@ spmm_narrow_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
       } else if (last_flush != pos) {               // (empty rows belong to launch_fill_empty_rows, spmm_kernels.hip)
         if (EPI) {
           t += bias_f;
-          if (relu) t = fmaxf(t, 0.f);
+          if (relu) t = relu_keep_nan(t);
         }
         if (sub == 0 && fok) C[(size_t)r * k + f] = t;
       }
@@ -186,7 +186,7 @@ spmm_narrow16_dpp_kernel(const int* __restrict__ rowptr, const int* __restrict__
       } else if (last_flush != pos) {               // (empty rows belong to launch_fill_empty_rows, spmm_kernels.hip)
         if (EPI) {
           t += bias_f;
-          if (relu) t = fmaxf(t, 0.f);
+          if (relu) t = relu_keep_nan(t);
         }
         if (sub == 0 && fok) C[(size_t)r * k + f] = t;
       }

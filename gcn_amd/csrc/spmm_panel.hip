@@ -470,7 +470,7 @@ __global__ void panel_epilogue_kernel(float* __restrict__ C, const float* __rest
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (; i < total; i += stride) {
     float s = C[i] + (bias ? bias[i % k] : 0.f);
-    if (relu) s = fmaxf(s, 0.f);
+    if (relu) s = relu_keep_nan(s);
     C[i] = s;
   }
 }

@@ -128,7 +128,7 @@ spmm_quad_kernel(const int* __restrict__ g_rowptr, const int* __restrict__ g_col
         }
         if (EPI) {
           t.x += bias4.x; t.y += bias4.y; t.z += bias4.z; t.w += bias4.w;
-          if (relu) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
+          if (relu) { t.x = relu_keep_nan(t.x); t.y = relu_keep_nan(t.y); t.z = relu_keep_nan(t.z); t.w = relu_keep_nan(t.w); }
         }
         if (writer) {
           if (stream_rows) __builtin_nontemporal_store(f32x4_q{t.x, t.y, t.z, t.w}, reinterpret_cast<f32x4_q*>(dst));

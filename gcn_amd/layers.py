@@ -58,7 +58,8 @@ class _FusedSpmmBiasRelu(torch.autograd.Function):
         if ctx.dropout is not None and ctx.dropout[0] > 0:
             g = dropout_rows(g, *ctx.dropout)          # the same mask, the same 1/(1-p)
         if ctx.relu:
-            g = g * (out > 0)                          # (dropped elements are 0 in `out`, and their gradient is 0 already)
+            g = g * ~(out <= 0)                        # a NaN passes its gradient, as torch's threshold_backward does
+                                                       # (dropped elements are 0 in `out`, and their gradient is 0 already)
         g = g.contiguous()
         if ctx.needs_input_grad[1]:
             _check_values_version(ctx.adj, ctx.values_version, "fused SpMM epilogue")

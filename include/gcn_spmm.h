@@ -79,7 +79,13 @@ size_t  gcn_spmm_plan_workspace_bytes(const gcn_spmm_plan_t* plan, int32_t k);
  * (and builds the streams of a sliced plan); every later call with the same width
  * only enqueues kernels on `stream`, so it can be captured in a HIP graph and
  * replayed on new operand contents (tests/test_spmm_gpu.py,
- * test_spmm_can_be_captured_in_a_hip_graph_and_replayed). */
+ * test_spmm_can_be_captured_in_a_hip_graph_and_replayed).
+ * Non-finite features (every entry point below, fp32 and bf16, every plan shape; tests/test_nonfinite_gpu.py): a NaN or
+ * +-Inf in B[c, j] reaches exactly the C[i, j] whose row i stores column c, and every other element keeps the bits it has
+ * without it.  The class of a reached element — NaN, +Inf or -Inf — is that of the IEEE sum of the row's products in any
+ * order.  In the fused epilogues a ReLU keeps NaN (as torch.relu does) and maps -Inf to 0, and a dropped element is 0
+ * whatever it held.  Outside the contract: a stored zero in A (0 * Inf is NaN by IEEE; dense panels skip zeros), and, inside
+ * a dense panel's window, repeated entries of one (row, column), which are multiplied as their sum. */
 int gcn_spmm_csr_f32(gcn_spmm_plan_t* plan,
                      const int32_t* rowptr_dev, const int32_t* col_dev,
                      const float* val_dev, const float* B_dev, float* C_dev,

@@ -15,6 +15,7 @@ import torch
 
 import gcn_amd
 from gcn_amd import _lib, dropin, graphgen
+from nonfinite_ref import class_of, spmm_class
 from util import GOLDEN, banded_csr, dense_band_csr, oracle_spmm, random_csr, rel_err, sym_norm_graph
 
 pytestmark = pytest.mark.gpu
@@ -951,7 +952,9 @@ def test_group_kernel_value_free_sliced_pass(S):
     C = adj.matmul_raw(torch.from_numpy(B).to(_dev())).cpu().numpy()
     A = sp.csr_matrix((val, col, rowptr), shape=(n, n))
     touched = np.asarray((A[:, bad] != 0).sum(1)).ravel() > 0
-    assert np.all(np.isfinite(C[~touched])) and np.all(~np.isfinite(C[touched]).all(1) | True)
+    cls, hit = spmm_class(rowptr, col, val, B)           # element by element: the class twin of tests/nonfinite_ref.py
+    assert np.array_equal(hit.any(1), touched) and hit.sum() > 2
+    assert np.all(np.isfinite(C[~hit])) and np.array_equal(class_of(C)[hit], cls[hit])
     assert np.all(np.isnan(C[np.asarray((A[:, [bad[0]]] != 0).sum(1)).ravel() > 0, 5]))
 
 
