@@ -22,6 +22,9 @@ ERR_NOT_FACTORED = 6         # GCN_ERR_NOT_FACTORED
 ERR_INTERNAL = 7             # GCN_ERR_INTERNAL (a consistency guard tripped: gcn_order_rabbit_device)
 DTYPE_F32, DTYPE_BF16 = 0, 1 # GCN_DTYPE_F32 / GCN_DTYPE_BF16 (gcn_spmm_csr_bf16_epilogue)
 REDUCE_MAX, REDUCE_MIN = 0, 1 # GCN_REDUCE_MAX / GCN_REDUCE_MIN (gcn_aggregate_csr)
+REDUCE_SUM = 2               # GCN_REDUCE_SUM (gcn_edge_aggregate_csr_f32)
+EDGE_OP_ADD, EDGE_OP_MUL = 0, 1      # GCN_EDGE_OP_*: how a node row and an entry's row of features meet
+EDGE_ACT_NONE, EDGE_ACT_RELU = 0, 1  # GCN_EDGE_ACT_*
 SAMPLE_LONG_ROW = 2048       # GCN_SAMPLE_LONG_ROW: longer rows get a workgroup, not a wave (gcn_sample_neighbors_csr)
 SAMPLE_WS_BYTES = 16         # GCN_SAMPLE_WS_BYTES
 SUBGRAPH_WS_BYTES = 16       # GCN_SUBGRAPH_WS_BYTES (gcn_induced_subgraph_count_csr / _fill_csr)
@@ -152,6 +155,12 @@ SIGNATURES = {
                                          ctypes.c_size_t, _c_p]),
     "gcn_aggregate_backward_csr": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_p,
                                                   ctypes.c_size_t, _c_p]),
+    "gcn_edge_aggregate_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32,
+                                                  _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_edge_aggregate_backward_x_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i32,
+                                                             _c_i32, _c_i32, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_edge_aggregate_backward_e_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i32,
+                                                             _c_i32, _c_i32, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_sample_neighbors_csr": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_i32, ctypes.c_uint64, ctypes.c_uint64,
                                                 _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_induced_subgraph_count_csr": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_p, _c_p, ctypes.c_size_t,

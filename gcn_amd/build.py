@@ -21,8 +21,8 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 ARCH = "gfx950"
 DROPIN_NAMES = ["flexspmm.so", "cuspmm.so", "tile.so", "permutate.so", "renumber.so"]
 
-SOURCES = ["spmm_kernels.hip", "spmm_narrow.hip", "spmm_quad.hip", "spmm_group.hip", "spmm_group_bf16.hip", "spmm_panel.hip", "sddmm.hip", "edge_softmax.hip", "aggregate.hip", "multihead.hip", "sample.hip", "subgraph.hip", "lookup.hip", "construct.hip", "coalesce.hip", "spgemm.hip", "knn.hip", "slicing.hip", "reorder_device.hip", "rabbit_device.hip", "exchange.hip", "plan_policy.cpp", "plan_build.cpp", "api_spmm.cpp", "api_units.cpp", "api_reorder.cpp", "api_dropin.cpp", "reorder.cpp", "sampled_dot.hip"]
-HEADERS = ["spmm_kernels.h", "chunk_walk.h", "group_walk.h", "row_dispatch.h", "long_chunks.h", "gather_rows.h", "plan.h", "plan_policy.h", "philox.h", "reorder.h", os.path.join(INCLUDE, "gcn_spmm.h")]
+SOURCES = ["spmm_kernels.hip", "spmm_narrow.hip", "spmm_quad.hip", "spmm_group.hip", "spmm_group_bf16.hip", "spmm_panel.hip", "sddmm.hip", "edge_softmax.hip", "aggregate.hip", "multihead.hip", "edge_message.hip", "sample.hip", "subgraph.hip", "lookup.hip", "construct.hip", "coalesce.hip", "spgemm.hip", "knn.hip", "slicing.hip", "reorder_device.hip", "rabbit_device.hip", "exchange.hip", "plan_policy.cpp", "plan_build.cpp", "api_spmm.cpp", "api_units.cpp", "api_reorder.cpp", "api_dropin.cpp", "reorder.cpp", "sampled_dot.hip"]
+HEADERS = ["spmm_kernels.h", "chunk_walk.h", "group_walk.h", "row_dispatch.h", "long_chunks.h", "gather_rows.h", "edge_message.h", "plan.h", "plan_policy.h", "philox.h", "reorder.h", os.path.join(INCLUDE, "gcn_spmm.h")]
 
 
 def _hipcc():

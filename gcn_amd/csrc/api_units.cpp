@@ -1,6 +1,7 @@
 // api_units.cpp — the native C ABI of libgcnspmm.so: the plan-free units (edge softmax, head-batched attention, GATv2 scores,
-// max / min aggregation, sampling, subgraphs and walks, entry lookup, bucketing, coalescing, SpGEMM, sampled dot, kNN, row
-// gather).  Each entry point is the argument checks of include/gcn_spmm.h in front of one launcher of spmm_kernels.h.
+// max / min aggregation, edge-feature aggregation, sampling, subgraphs and walks, entry lookup, bucketing, coalescing, SpGEMM, sampled dot, kNN, row
+// gather).  Each entry point is the argument checks of include/gcn_spmm.h in front of one launcher of spmm_kernels.h (edge_message.h).
+#include "edge_message.h"
 #include "plan_policy.h"
 
 using namespace gcn;
@@ -218,6 +219,62 @@ int gcn_aggregate_backward_csr(const int32_t* trowptr, const int32_t* trow, cons
     return hip_status(hipMemsetAsync(gx, 0, (size_t)n * (size_t)k * (dtype == GCN_DTYPE_BF16 ? 2 : 4), st));
   if (!trowptr || !trow || !tperm || !g || !arg || !ws || ws_bytes < aggregate_workspace_bytes(nnz, k)) return GCN_ERR_INVALID_ARG;
   return hip_status(launch_aggregate_backward(trowptr, trow, tperm, n, nnz, g, dtype == GCN_DTYPE_BF16, arg, k, gx, ws, st));
+}
+
+static_assert(kEdgeOpAdd == GCN_EDGE_OP_ADD && kEdgeOpMul == GCN_EDGE_OP_MUL && kEdgeActNone == GCN_EDGE_ACT_NONE &&
+              kEdgeActRelu == GCN_EDGE_ACT_RELU && kEdgeReduceSum == GCN_REDUCE_SUM && kAggMax == GCN_REDUCE_MAX &&
+              kAggMin == GCN_REDUCE_MIN, "include/gcn_spmm.h");
+
+// Edge-feature aggregation (edge_message.hip).  k, the constants and the sizes first (nnz * k may pass 2^31: it is no
+// bound); then what an empty problem still needs; 1 = return *status
+static int edge_aggregate_args(int32_t rows_out, int32_t rows_in, int32_t nnz, int32_t k, int32_t op, int32_t act, int* status) {
+  *status = GCN_ERR_INVALID_ARG;
+  if (rows_out < 0 || rows_in < 0 || nnz < 0 || k < 1 || k > 16 * 65535) return 1;     // (column tiles ride in gridDim.y)
+  if ((op != GCN_EDGE_OP_ADD && op != GCN_EDGE_OP_MUL) || (act != GCN_EDGE_ACT_NONE && act != GCN_EDGE_ACT_RELU)) return 1;
+  *status = GCN_OK;
+  return rows_out == 0;
+}
+
+int gcn_edge_aggregate_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t n, int32_t nnz, const float* x,
+                               const float* w, int32_t k, int32_t op, int32_t act, int32_t reduce, float* out, int32_t* arg,
+                               void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (reduce != GCN_REDUCE_MAX && reduce != GCN_REDUCE_MIN && reduce != GCN_REDUCE_SUM) return GCN_ERR_INVALID_ARG;
+  if (edge_aggregate_args(m, n, nnz, k, op, act, &rc)) return rc;
+  const bool select = reduce != GCN_REDUCE_SUM;
+  if (!out || (select && !arg)) return GCN_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t elems = (size_t)m * (size_t)k;
+  if (nnz == 0) {                                       // every row is empty: zeros and -1, as memset nodes
+    if (hipMemsetAsync(out, 0, elems * 4, st) != hipSuccess) return GCN_ERR_HIP;
+    return select ? hip_status(hipMemsetAsync(arg, 0xff, elems * 4, st)) : GCN_OK;
+  }
+  if (!rowptr || !col || !x || !w || !ws || ws_bytes < edge_aggregate_workspace_bytes(nnz, k)) return GCN_ERR_INVALID_ARG;
+  return hip_status(launch_edge_aggregate(rowptr, col, m, nnz, x, w, k, op, act, reduce, out, arg, ws, st));
+}
+
+int gcn_edge_aggregate_backward_x_csr_f32(const int32_t* trowptr, const int32_t* trow, const int32_t* tperm, int32_t n, int32_t m,
+                                          int32_t nnz, const float* g, const float* x, const float* w, int32_t k, int32_t op,
+                                          int32_t act, float* gx, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (edge_aggregate_args(n, m, nnz, k, op, act, &rc)) return rc;
+  if (!gx) return GCN_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (nnz == 0) return hip_status(hipMemsetAsync(gx, 0, (size_t)n * (size_t)k * 4, st));
+  if (!trowptr || !trow || !tperm || !g || !x || !w || !ws || ws_bytes < edge_aggregate_workspace_bytes(nnz, k))
+    return GCN_ERR_INVALID_ARG;
+  return hip_status(launch_edge_aggregate_backward_x(trowptr, trow, tperm, n, nnz, g, x, w, k, op, act, gx, ws, st));
+}
+
+int gcn_edge_aggregate_backward_e_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t n, int32_t nnz,
+                                          const float* g, const float* x, const float* w, int32_t k, int32_t op, int32_t act,
+                                          float* ge, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (edge_aggregate_args(m, n, nnz, k, op, act, &rc)) return rc;
+  if (nnz == 0) return GCN_OK;                          // (ge has no element)
+  if (!rowptr || !col || !g || !x || !w || !ge || !ws || ws_bytes < edge_aggregate_workspace_bytes(nnz, k))
+    return GCN_ERR_INVALID_ARG;
+  return hip_status(launch_edge_aggregate_backward_e(rowptr, col, m, nnz, g, x, w, k, op, act, ge, ws, (hipStream_t)stream));
 }
 
 int gcn_sample_neighbors_csr(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t nnz, const int32_t* seeds, int32_t n_seeds,

@@ -25,6 +25,7 @@ from torch.nn.parameter import Parameter
 
 from . import preprocess, reorder, timers
 from .aggregate import aggregate
+from .edgefeat import edge_aggregate
 from .attention import edge_softmax, gat_edge_softmax, gatv2_scores, spmm_heads
 from .spgemm import HypergraphLaplacian
 from .spmm import CsrAdjacency, _SpmmFunction, _check_values_version, _values_version, dropout_rows, gather_rows, spmm
@@ -343,6 +344,85 @@ class SAGEConv(nn.Module):
     def __repr__(self):
         return (f"SAGEConv ({self.in_features} -> {self.out_features}, aggr={self.aggr}"
                 f"{'' if self.weight_root is not None else ', no root weight'})")
+
+
+class _GINBase(nn.Module):
+    """what GINConv and GINEConv share: the wrapped network, eps (a buffer, or a parameter with train_eps) and the
+    (x_src, x_dst) form of a sampled block"""
+
+    def __init__(self, net, eps=0.0, train_eps=False):
+        super().__init__()
+        self.nn = net
+        self.initial_eps = float(eps)
+        if train_eps:
+            self.eps = Parameter(torch.empty(()))
+        else:
+            self.register_buffer("eps", torch.empty(()))
+        self.eps.data.fill_(self.initial_eps)
+
+    def _pair(self, input, adj):
+        name = type(self).__name__
+        if isinstance(input, (tuple, list)):               # a bipartite block: (x_src [adj.n rows], x_dst [adj.m rows])
+            if len(input) != 2:
+                raise ValueError(f"{name}: a bipartite input is the pair (x_src, x_dst)")
+            x, root = input
+        else:
+            x = root = input
+            if adj.m != adj.n:
+                raise ValueError(f"{name}: adjacency {adj.m}x{adj.n} needs the pair (x_src, x_dst)")
+        if x.dim() != 2 or x.shape[0] != adj.n or root.dim() != 2 or root.shape[0] != adj.m or root.shape[1] != x.shape[1]:
+            raise ValueError(f"{name}: adjacency {adj.m}x{adj.n}, input ({tuple(x.shape)}, {tuple(root.shape)})")
+        return x, root
+
+
+class GINConv(_GINBase):
+    """Graph isomorphism layer (Xu et al. 2019; PyG's ``GINConv``): ``out = nn((1 + eps) * x_dst + sum_j x_j)`` over the
+    stored entries of each row of ``adj`` (pattern only), on ``aggregate(adj, x, "sum")``.  ``nn`` is any module mapping
+    [rows, in] to [rows, out]; ``eps`` is a buffer, or a parameter with ``train_eps=True``.  ``forward((x_src, x_dst), adj)``
+    takes a sampled block."""
+
+    def forward(self, input, adj):
+        x, root = self._pair(input, adj)
+        return self.nn((1.0 + self.eps) * root + aggregate(adj, _spmm_operand(x), "sum"))
+
+    def __repr__(self):
+        return f"GINConv (nn={self.nn})"
+
+
+class GINEConv(_GINBase):
+    """GIN with edge features (Hu et al. 2020; PyG's ``GINEConv``) on the native edge-feature aggregation:
+
+        out = nn((1 + eps) * x_dst + sum_j relu(x_j + e_ji))
+
+    ``forward(x, adj, edge_attr)``: ``edge_attr`` [adj.nnz, in_features] in the entry order of ``adj``, or
+    [adj.nnz, edge_dim] with ``edge_dim`` given, which adds ``lin = Linear(edge_dim, in_features)`` in front (``in_features``
+    is then needed, unless ``nn`` starts with a layer that has ``in_features``).  ``forward((x_src, x_dst), adj, edge_attr)``
+    takes a sampled block; the caller passes ``edge_attr[block.eid.long()]``.  The [nnz, in_features] messages are never
+    formed: ``gcn_amd.edge_aggregate(adj, x, e, "add", "relu")``."""
+
+    def __init__(self, nn, eps=0.0, train_eps=False, edge_dim=None, in_features=None):
+        super().__init__(nn, eps, train_eps)
+        if edge_dim is not None:
+            if in_features is None:
+                first = nn[0] if isinstance(nn, torch.nn.Sequential) and len(nn) else nn
+                in_features = getattr(first, "in_features", None)
+            if in_features is None:
+                raise ValueError("GINEConv: edge_dim needs in_features (the wrapped network does not tell its input width)")
+            self.lin = torch.nn.Linear(int(edge_dim), int(in_features))
+        else:
+            self.lin = None
+
+    def forward(self, input, adj, edge_attr):
+        x, root = self._pair(input, adj)
+        if self.lin is not None:
+            edge_attr = self.lin(edge_attr)
+        if edge_attr.dim() != 2 or tuple(edge_attr.shape) != (adj.nnz, int(x.shape[1])):
+            raise ValueError(f"GINEConv: edge_attr {tuple(edge_attr.shape)} for {adj.nnz} entries of width {int(x.shape[1])} "
+                             "(set edge_dim to map another width)")
+        return self.nn((1.0 + self.eps) * root + edge_aggregate(adj, x.float(), edge_attr.float(), "add", "relu", "sum"))
+
+    def __repr__(self):
+        return f"GINEConv (nn={self.nn})"
 
 
 class GraphSAGE(nn.Module):

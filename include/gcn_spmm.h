@@ -305,6 +305,54 @@ int gcn_aggregate_backward_csr(const int32_t* trowptr_dev, const int32_t* trow_d
                                int32_t m, int32_t nnz, const void* g, int32_t dtype, const int32_t* arg, int32_t k, void* gx,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* Edge-feature message passing (edge_message.hip; DGL's u_op_e -> reduce: GINE, MPNN, CGConv): a feature VECTOR per stored
+ * entry beside the gathered node row.  Plan-free like the aggregation family above: the caller's CSR, one memset node and
+ * kernels (no allocation, no host synchronisation, no host read of device data: legal inside a stream capture), no
+ * atomics, every output element has one writer and every sum a fixed order: the same bits at every call.  The stored
+ * VALUES of the matrix are not used; duplicated (row, column) pairs are separate entries.  Any row length (rows of more
+ * than 4096 entries are spread over the chip).  All operands fp32, row-major: x [n x k], w [nnz x k] in the CSR's entry
+ * order (row e belongs to entry e of col_dev), out [m x k].  nnz * k may pass 2^31: offsets into w and ge are 64-bit.
+ *   The message.  t = x[col[e], j] + w[e, j] (GCN_EDGE_OP_ADD) or x[col[e], j] * w[e, j] (GCN_EDGE_OP_MUL): one fp32
+ *   operation, rounded once, never fused into the accumulation.  Then act: GCN_EDGE_ACT_NONE, or GCN_EDGE_ACT_RELU:
+ *   msg = t < 0 ? +0 : t, so a NaN and -0.0 pass.  The derivative D = t <= 0 ? 0 : 1 under relu (a NaN t passes the
+ *   gradient; D selects: a zero D gives a zero, whatever g holds), 1 without.
+ *   out[r, j] = the reduce over the entries e of row r of msg(e, j).  GCN_REDUCE_SUM: slot s of 64 / LPS adds the entries
+ *   s, s + SLOTS, ... in ascending order as a compensated (Kahan) chain, the slots are merged by an xor butterfly, chunk
+ *   partials of a long row in chunk order (LPS = 16, 32 or 64 lanes for k / VEC <= 16, <= 32, more).  GCN_REDUCE_MAX / GCN_REDUCE_MIN: the selection rule
+ *   of gcn_aggregate_csr applied to the message (the first entry among equals, -0.0 equals +0.0, a NaN beats every number
+ *   and the first NaN wins; the message's bits are stored) and arg[r, j] = that entry's index.  An empty row gets 0 (arg
+ *   -1).  arg [m x k] int32 is required for max / min and ignored (may be NULL) for the sum.
+ * 16-byte accesses (VEC = 4) when x, w and out (g, gx, ge) are 16-byte aligned and k % 4 == 0, element accesses otherwise.
+ * ws: device scratch of at least GCN_EDGE_AGGREGATE_WS_BYTES(nnz, k) bytes, 16-byte aligned, owned by the call until it
+ * has run; the three calls on a pattern and its transpose may share it.  GCN_ERR_INVALID_ARG, before any pointer is read:
+ * null pointers, negative sizes, k < 1, k > 16 * 65535 (column tiles ride in the grid), an unknown op, act or reduce, a
+ * short workspace.  m == 0: GCN_OK, nothing launched; nnz == 0: out is zeroed and arg set to -1. */
+#define GCN_EDGE_AGGREGATE_WS_BYTES(nnz, k) (16 + 16 * (size_t)(k) * (((size_t)(nnz) + 4095) / 4096))
+#define GCN_EDGE_OP_ADD 0
+#define GCN_EDGE_OP_MUL 1
+#define GCN_EDGE_ACT_NONE 0
+#define GCN_EDGE_ACT_RELU 1
+#define GCN_REDUCE_SUM 2
+int gcn_edge_aggregate_csr_f32(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t n, int32_t nnz,
+                               const float* x, const float* w, int32_t k, int32_t op, int32_t act, int32_t reduce, float* out,
+                               int32_t* arg, void* ws, size_t ws_bytes, void* stream);
+/* The gradient of the SUM in x, as the forward's walk on the TRANSPOSED pattern (trowptr_dev [n + 1], trow_dev, tperm_dev as
+ * in gcn_aggregate_backward_csr): for the entry t of transposed row c, r = trow[t] and e = tperm[t],
+ *   gx[c, j] = sum of g[r, j] * D * (w[e, j] if mul),   D from t = x[c, j] op w[e, j], recomputed
+ * in the forward's fixed order; nothing of size nnz x k is kept by the forward.  g [m x k], gx [n x k]; an empty row gets
+ * zeros.  n == 0: nothing written; nnz == 0: gx is zeroed. */
+int gcn_edge_aggregate_backward_x_csr_f32(const int32_t* trowptr_dev, const int32_t* trow_dev, const int32_t* tperm_dev, int32_t n,
+                                          int32_t m, int32_t nnz, const float* g, const float* x, const float* w, int32_t k,
+                                          int32_t op, int32_t act, float* gx, void* ws, size_t ws_bytes, void* stream);
+/* The gradient of the SUM in w, one writer per element of ge [nnz x k]:
+ *   ge[e, j] = g[row(e), j] * D * (x[col[e], j] if mul)
+ * x is gathered only where D or mul needs it and w read only where D needs it.  m == 0 or nnz == 0: nothing written.
+ * (The backward of max / min needs neither kernel: with arg it is element-wise work on [m x k] arrays and one
+ * gcn_aggregate_backward_csr.) */
+int gcn_edge_aggregate_backward_e_csr_f32(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t n, int32_t nnz,
+                                          const float* g, const float* x, const float* w, int32_t k, int32_t op, int32_t act,
+                                          float* ge, void* ws, size_t ws_bytes, void* stream);
+
 /* Head-batched attention primitives (multihead.hip): the edge softmax family, the weighted SpMM and the SDDMM for H heads
  * in one pass over the adjacency.  Plan-free like the two families above: the caller's CSR, one 4-byte memset node and
  * kernels (legal inside a stream capture), no host read of device data, no atomics, the same bits at every call; any row
