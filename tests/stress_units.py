@@ -8,16 +8,68 @@ column-sorted.  Row-length styles by seed % 4, as in test_stress_gpu._case: shor
 b - 1, b, b + 1 of every bound b of the unit (and one row of exactly a bound's length right after a run of empty rows);
 a few hubs up to 2 * 8192 + 1; dense-ish rows.  One seed in four — one of each style in every 16 — forces a long row (longer
 than the unit's largest bound) at item 0, one at item m - 1, two side by side, and makes one of them a single repeated
-column.  Values are eighths, features and gradients small integers: every sum is exact in fp32 in any order."""
+column.  Values are eighths, features and gradients small integers: every sum is exact in fp32 in any order.
+
+The first eight units came with the sweep; the head-batched and edge units were added later, and units added later append to
+``UNITS`` (``_base`` seeds its generator with the unit's index, so the earlier cases stay bit for bit):
+
+* ``heads``: edge_softmax and gat_edge_softmax on [nnz, H], spmm_heads, sddmm_heads and segment_sum on [nnz, H], through the
+  public functions and their autograd on ONE adjacency.  H is a function of the seed (``H_LIST``), step 1 takes another H.
+  The softmax family changes path at len * hp = 32 / 256 / 1024 ELEMENTS (hp = H on the fast route, 1 for one head and on
+  the slow route), so the bounds are ``heads_bounds(H)``: those divided by hp, 8192, and the gather engine's 4 / 64 / 4096.
+  Two of the five kinds have a width: those steps take ``F_LIST`` in turn within their style, so every F meets every style.
+* ``gatv2``: gatv2_scores and its four gradients on the exact grid; ``edge_aggregate``: every (op, act, reduce) with both
+  gradients, level-valued operands so that the selections tie.  Both draw one seed in two transposed (hub columns).
+* ``sampled_dot``: P [q x q] samples X · Yᵀ in both modes, with own, given and no values, and one step goes through
+  SparseProduct.values with at least one value vector given and the backward for what is given; rows of P around 64 and SAMPLE_LONG_ROW, rows of X around 16, 64 and it.
+* ``linkpred``: find_edges and negative_sample interleaved on one column-sorted matrix with repeated columns and one row that
+  stores every column; the launch and the tries are proven axis by axis, as the kNN's dimensions are (a negative_sample step
+  of more than 65 queries keeps num_neg = 1 and at most 5 tries: the twin draws count * num_neg * max_tries Philox words).
+* ``mixed``: three DIFFERENT units in turn on one square, mutable adjacency — they share its one cached ``tpattern()`` and its
+  one Scratch keeper — and, one seed in two, new values between steps 1 and 2.  Its widths are taken in turn over the seeds;
+  a style has fewer steps of a kind than there are widths, so they are proven over all styles together.
+
+The matrices of these units keep two more caps, nnz * k <= 4 000 000 and nnz * H <= 2 000 000, by emptying ordinary rows; the
+special rows (bound rows, hubs, forced rows) survive, and where they alone exceed a cap the step takes the widest width that
+fits (``fit_width``; node arrays keep the same cap).  One step in two keeps every operand on a 16-byte boundary, since the
+16-byte forms need all of them there.  Their operands are not kept on the case: ``step_inputs(c, i)`` draws them again."""
 import numpy as np
 
 from gcn_amd import _lib
 
-UNITS = ("construct", "coalesce", "sampling", "aggregate", "attention", "sddmm", "spgemm", "knn")
+UNITS = ("construct", "coalesce", "sampling", "aggregate", "attention", "sddmm", "spgemm", "knn",
+         "heads", "gatv2", "edge_aggregate", "sampled_dot", "linkpred", "mixed")     # (units added later append: _base seeds by index)
 K_LIST = (1, 2, 3, 4, 5, 8, 9, 16, 17, 33, 64, 65, 100, 128, 200)
 NNZ_MAX = 60000
+NNZ_K_MAX, NNZ_H_MAX = 4_000_000, 2_000_000            # elements of an [nnz, k] and of an [nnz, H] array (and of a node array)
 HUB_TOP = 2 * 8192 + 1
 LONG = _lib.SAMPLE_LONG_ROW
+# the head counts of the head-batched units: every fast-route count of edge_softmax.hip / multihead.hip (a power of two up to
+# kMaxFastHeads = 16), slow-route ones, and one above kMaxFastHeads.  H is a function of the seed; at most 12 entries, so
+# that every H meets every row-length style within 48 seeds (seed >> 2 takes 12 values in every style)
+# (the fast-route counts sit where seed >> 2 is 2, 3, 6, 7: there the one clustered-length seed of a head count is not a forced
+# one, whose long rows use up the budget of the rows around 8192)
+H_LIST = (1, 3, 2, 4, 5, 32, 8, 16, 6, 12)
+# head widths: F % 4 != 0 (VEC = 1) and F % 4 == 0 (VEC = 4 when the operands are aligned); U = F / VEC odd (4, 12), 2 mod 4
+# (8) and 0 mod 4 (16, 32, 64): P = 1, 2, 4 lanes an (entry, head) of sddmm_heads; k = H F on both sides of 64, 128, 256
+F_LIST = (1, 2, 3, 4, 5, 8, 12, 16, 17, 32, 33, 64, 65)
+SOFTMAX_ELEMENTS = (32, 256, 1024)                     # len * hp of a row at which edge_softmax.hip changes path
+SOFTMAX_LONG = 8192                                    # ... and the entries from which a row is split over blocks
+GATHER_BOUNDS = (4, 64, 4096)                          # gather_rows.h: a slot's batch, a fetch of indices, the chunk
+
+
+def head_pack(H):
+    """hp of edge_softmax.hip: the heads of an entry that adjacent lanes share — H on the fast route, 1 for one head and on
+    the slow route (a pass per head)"""
+    return H if H in (2, 4, 8, 16) else 1
+
+
+def heads_bounds(H):
+    """the row lengths, in ENTRIES, at which a head-batched call of H heads changes path: the softmax family's element
+    bounds divided by hp, its long-row bound, and the gather engine's"""
+    return tuple(sorted({b // head_pack(H) for b in SOFTMAX_ELEMENTS} | {SOFTMAX_LONG} | set(GATHER_BOUNDS)))
+
+
 # the row (item) lengths at which a unit's kernels change path
 BOUNDS = {"construct": (64, _lib.BUCKET_WAVE_MAX, _lib.BUCKET_BLOCK_MAX),       # entries of a bucket
           "coalesce": (64, 128, 256, LONG),
@@ -26,11 +78,19 @@ BOUNDS = {"construct": (64, _lib.BUCKET_WAVE_MAX, _lib.BUCKET_BLOCK_MAX),       
           "attention": (32, 256, 1024, 8192),
           "sddmm": (64, 256),
           "spgemm": (64, _lib.SPGEMM_WAVE_MAX, _lib.SPGEMM_BLOCK_MAX),           # products of a row of A
-          "knn": (32, 64)}               # the feature chunk; KNN_TILE_Q = KNN_TILE_C = KNN_K_MAX (asserted in the CPU test)
-WIDTH_UNITS = ("aggregate", "sddmm", "knn")                                      # (kNN's width is the feature count d)
+          "knn": (32, 64),               # the feature chunk; KNN_TILE_Q = KNN_TILE_C = KNN_K_MAX (asserted in the CPU test)
+          "heads": tuple(sorted({b for H in (1, 2, 4, 8, 16) for b in heads_bounds(H)})),   # (a case draws heads_bounds(its H))
+          "gatv2": GATHER_BOUNDS,
+          "edge_aggregate": GATHER_BOUNDS,
+          "sampled_dot": (16, 64, LONG),                                         # rows of X (all three) and rows of P (LONG)
+          "linkpred": (64, 256, LONG),                                           # the sampling unit's
+          "mixed": GATHER_BOUNDS + (SOFTMAX_LONG,)}
+WIDTH_UNITS = ("aggregate", "sddmm", "knn", "edge_aggregate")                    # (kNN's width is the feature count d)
+HEAD_UNITS = ("heads", "gatv2")                                                  # widths k = H F, F of F_LIST
 TWO_DTYPES = {"construct": ("int32", "int64"), "sampling": ("int32", "int64"), "coalesce": ("int32", "int64"),
-              "aggregate": ("fp32", "bf16"), "sddmm": ("fp32", "bf16")}
-LONG_ROW_UNITS = ("construct", "coalesce", "sampling", "aggregate", "attention", "spgemm")
+              "aggregate": ("fp32", "bf16"), "sddmm": ("fp32", "bf16"), "linkpred": ("int32", "int64")}
+LONG_ROW_UNITS = ("construct", "coalesce", "sampling", "aggregate", "attention", "spgemm",
+                  "heads", "gatv2", "edge_aggregate", "sampled_dot", "linkpred", "mixed")
 SPGEMM_WIDE_N = _lib.SPGEMM_BLOCK_MAX + _lib.SPGEMM_BLOCK_MAX // 4
 
 
@@ -42,9 +102,9 @@ def forced(seed):
     return ((seed >> 2) & 3) == (seed & 3)
 
 
-def row_lengths(rng, seed, m, bounds, cap=NNZ_MAX):
+def row_lengths(rng, seed, m, bounds, cap=NNZ_MAX, keep=None):
     """-> (lens int64 [m], long rows placed by force: dict name -> row).  The special rows survive the cap; ordinary rows
-    are emptied at random until the total fits"""
+    are emptied at random until the total fits.  keep: a set that receives the special rows"""
     style, top = style_of(seed), max(bounds)
     special = {}
     if style == 0:
@@ -95,6 +155,8 @@ def row_lengths(rng, seed, m, bounds, cap=NNZ_MAX):
     if lens.sum() == 0:
         lens[m // 2] = 3
     assert lens.sum() <= cap
+    if keep is not None:
+        keep.update(special)
     return lens.astype(np.int64), placed
 
 
@@ -368,8 +430,324 @@ def _knn(seed):
     return c
 
 
+# ---- the units added after the first sweep ------------------------------------------------------------------------------------
+# Their matrices carry two more caps (nnz * k <= NNZ_K_MAX for the widest step, nnz * H <= NNZ_H_MAX), reached by emptying
+# ordinary rows; the special rows survive, and where they alone exceed a cap the step narrows its width (fit_width).  The
+# operands of a step are not kept on the case (one may reach 4 000 000 elements): step_inputs(c, i) draws them again.
+HEADS_OPS = ("edge_softmax", "gat_edge_softmax", "spmm_heads", "sddmm_heads", "segment_sum")
+GATHER_KINDS = ("spmm_heads", "sddmm_heads", "gatv2_scores")                     # the kinds whose width is k = H F
+MIXED_KINDS = ("aggregate", "edge_aggregate", "spmm_heads", "gatv2_scores", "edge_softmax", "sample_neighbors")
+EDGE_TRIPLES = tuple((op, act, red) for op in ("add", "mul") for act in (None, "relu") for red in ("sum", "mean", "max", "min"))
+QUERY_COUNTS = (1, 63, 64, 65, 65535, 65536, 65537)                              # both sides of 64 and of lookup.hip's kLookupSmall
+NEW_UNITS = UNITS[8:]
+
+
+def fit_width(widths, drawn, rows, per=1):
+    """the largest width of `widths` not above `drawn` with rows * per * width <= NNZ_K_MAX"""
+    return max([w for w in widths if w <= drawn and rows * per * w <= NNZ_K_MAX] or [min(widths)])
+
+
+def step_heads(seed, i):
+    """H of step i: the case's H (a function of the seed) at steps 0 and 2, ANOTHER one at step 1, so that the adjacency's
+    scratch is outgrown and then under-used"""
+    at = (seed >> 2) % len(H_LIST)
+    return H_LIST[at if i != 1 else (at + 1 + seed % (len(H_LIST) - 1)) % len(H_LIST)]
+
+
+def step_width(seed, i):
+    fs = sorted(F_LIST[(3 * seed + j) % len(F_LIST)] for j in range(3))
+    return (fs[0], fs[2], fs[1])[i]                    # narrow -> wide -> narrow
+
+
+def _matrix(seed, unit, bounds, k_top=1, square=False, window=False, reserve=0):
+    """_base with the caps of the later units -> (rng, case, special rows)"""
+    rng = np.random.default_rng([seed, UNITS.index(unit)])
+    m = int(rng.integers(12, (600 if style_of(seed) == 3 else 1500) + 1))
+    n = m if square else int(rng.integers(1, 4001))
+    special = set()
+    lens, placed = row_lengths(rng, seed, m, bounds, cap=NNZ_MAX - reserve, keep=special)
+    over = int(lens.sum()) - min(NNZ_MAX, NNZ_K_MAX // k_top)
+    for r in rng.permutation(m):
+        if over <= 0:
+            break
+        if int(r) not in special:
+            over -= int(lens[r])
+            lens[r] = 0
+    if lens.sum() == 0:
+        lens[m // 2] = 3
+    rp, ci = csr_of_lengths(rng, lens, n, window, placed.get("pair2"))
+    c = dict(seed=seed, unit=unit, style=style_of(seed), forced=forced(seed), placed=placed, m=m, n=n, rp=rp, ci=ci,
+             va=eighths(rng, len(ci)), lens=np.diff(rp).astype(np.int64), adj_offsets=tuple(int(o) for o in rng.integers(0, 4, 3)),
+             transposed=False)
+    return rng, c, special
+
+
+def _transpose_case(c):
+    """the adjacency becomes the transpose of the drawn matrix: its COLUMNS have the drawn lengths (c["lens"] stays), and
+    the backward walks over the transposed pattern meet them"""
+    trp, trow, tva = transpose_host(c["rp"], c["ci"], c["va"], c["n"])
+    c.update(rp=trp, ci=trow, va=tva, m=c["n"], n=c["m"], transposed=True)
+
+
+def _align(s, seed, i):
+    """one step in two keeps every operand on a 16-byte boundary: the 16-byte forms (VEC = 4) need ALL their operands
+    there, which offsets drawn one by one from 0 .. 3 give once in 4^operands"""
+    s["aligned"] = bool((seed + i + (seed >> 2)) & 1)
+    if s["aligned"]:
+        s["offsets"] = (0,) * 6
+
+
+def vec_of(s, operands):
+    """VEC as the kernels choose it (edgefeat.route, multihead.hip's `wide`): 4 when a head's (or the row's) width is a
+    multiple of 4 and every one of the step's first `operands` operands starts on a 16-byte boundary, else 1"""
+    return 4 if s.get("F", s["k"]) % 4 == 0 and all(o % 4 == 0 for o in s["offsets"][:operands]) else 1
+
+
+HEADS_F_START = (1, 4, 1, 7)                            # where each style's turn through F_LIST begins
+
+
+def heads_kinds(seed):
+    return [HEADS_OPS[((seed & 3) + (seed >> 2) + i) % 5] for i in range(3)]
+
+
+def heads_width(seed, i):
+    """F of step i of the heads unit.  Only two of its five step kinds have a width, so its gather steps take F_LIST in turn
+    WITHIN their row-length style (14 or 15 of them in 48 seeds, for 13 widths): every F meets every style"""
+    before = sum(kind in GATHER_KINDS for earlier in range(seed & 3, seed, 4) for kind in heads_kinds(earlier))
+    before += sum(kind in GATHER_KINDS for kind in heads_kinds(seed)[:i])
+    return F_LIST[(before + HEADS_F_START[seed & 3]) % len(F_LIST)]
+
+
+def _head_step(s, c, seed, i, kind, width=step_width):
+    H, F = step_heads(seed, i), width(seed, i)
+    rows = max(len(c["ci"]), c["m"], c["n"])
+    s.update(kind=kind, H=H, F_drawn=F, F=fit_width(F_LIST, F, rows, H) if kind in GATHER_KINDS else 1)
+    s["k"] = H * s["F"]
+    _align(s, seed, i)
+
+
+def _k_top(seed, kinds, width=step_width):
+    """the widest k a case's steps ask for (what its nnz is capped for)"""
+    return max(step_heads(seed, i) * (width(seed, i) if kind in GATHER_KINDS else 1) for i, kind in enumerate(kinds))
+
+
+def _heads(seed):
+    kinds = heads_kinds(seed)
+    rng, c, _ = _matrix(seed, "heads", heads_bounds(step_heads(seed, 0)), _k_top(seed, kinds, heads_width))
+    c.update(H=step_heads(seed, 0), hp=head_pack(step_heads(seed, 0)), steps=[])
+    for i in range(3):
+        s = _common(rng, seed, i, "heads")
+        _head_step(s, c, seed, i, kinds[i], heads_width)
+        s.update(op=kinds[i], rows=_row_range(rng, c["m"], i), slope=(0.2, 1.5)[int(rng.integers(0, 2))], perm=bool(rng.integers(0, 2)))
+        c["steps"].append(s)
+    return c
+
+
+def _gatv2(seed):
+    rng, c, _ = _matrix(seed, "gatv2", GATHER_BOUNDS, _k_top(seed, ["gatv2_scores"] * 3))
+    if (seed >> 2) & 1 and c["style"] != 3:             # (one seed in two of every style but the dense-ish one)
+        _transpose_case(c)
+    c["steps"] = []
+    for i in range(3):
+        s = _common(rng, seed, i, "gatv2")
+        _head_step(s, c, seed, i, "gatv2_scores")
+        s.update(op="gatv2_scores", slope=(0.5, 0.25)[(seed + i + (seed >> 3)) & 1])
+        c["steps"].append(s)
+    return c
+
+
+def _edge_step(s, c, seed, i):
+    msg, act, reduce = EDGE_TRIPLES[(3 * seed + i) % len(EDGE_TRIPLES)]
+    s.update(kind="edge_aggregate", msg=msg, act=act, reduce=reduce, k_drawn=s["k"],
+             k=fit_width(K_LIST, s["k"], max(len(c["ci"]), c["m"], c["n"])))
+    _align(s, seed, i)
+
+
+def _edge_aggregate(seed):
+    k_top = max(K_LIST[(3 * seed + j) % len(K_LIST)] for j in range(3))
+    rng, c, _ = _matrix(seed, "edge_aggregate", GATHER_BOUNDS, k_top)
+    if (seed >> 2) & 1 and c["style"] != 3:
+        _transpose_case(c)
+    c["steps"] = []
+    for i in range(3):
+        s = _common(rng, seed, i, "edge_aggregate")
+        _edge_step(s, c, seed, i)
+        s["op"] = s["msg"]
+        c["steps"].append(s)
+    return c
+
+
+def mixed_kinds(seed):
+    """three DIFFERENT kinds of MIXED_KINDS, a function of the seed"""
+    a = seed + (seed >> 2)
+    return tuple(MIXED_KINDS[(a + o) % 6] for o in (0, 1 + ((seed >> 2) & 1), 3 + (seed >> 3) % 3))
+
+
+def mixed_width(seed, i, widths=F_LIST, kinds=GATHER_KINDS):
+    """the width of step i of the mixed unit: the steps of `kinds` take `widths` in turn over the seeds (a seed has three
+    steps of six kinds: the narrow-wide-narrow triples of the other units would leave widths out)"""
+    before = sum(k in kinds for earlier in range(seed) for k in mixed_kinds(earlier)) + sum(k in kinds for k in mixed_kinds(seed)[:i])
+    return widths[before % len(widths)]
+
+
+def _mixed_k(seed, i):
+    return mixed_width(seed, i, K_LIST, ("aggregate", "edge_aggregate"))
+
+
+def _mixed(seed):
+    """one square, mutable adjacency that three different units use in turn"""
+    kinds = mixed_kinds(seed)
+    k_top = max([_mixed_k(seed, i) for i, kind in enumerate(kinds) if kind in ("aggregate", "edge_aggregate")] + [_k_top(seed, kinds, mixed_width)])
+    rng, c, _ = _matrix(seed, "mixed", BOUNDS["mixed"], k_top, square=True)
+    heavy = np.argsort(-c["lens"], kind="stable")[:4]
+    c.update(steps=[], update=bool(((seed >> 2) ^ seed) & 1), new_va=eighths(rng, len(c["ci"])))
+    for i, kind in enumerate(kinds):
+        s = _common(rng, seed, i, "mixed")
+        s["k"] = _mixed_k(seed, i)
+        if kind == "edge_aggregate":
+            _edge_step(s, c, seed, i)
+        elif kind == "aggregate":
+            s.update(kind=kind, k_drawn=s["k"], k=fit_width(K_LIST, s["k"], max(len(c["ci"]), c["m"])), select=("max", "min")[(seed + i) & 1])
+            _align(s, seed, i)
+        elif kind == "sample_neighbors":
+            ids = np.concatenate([rng.permutation(c["m"])[:int(rng.integers(1, c["m"] + 1))], heavy])
+            s.update(kind=kind, k=1, ids=ids.astype(np.int64), fanout=int(rng.choice([1, 2, 5, 63, 64, 65, 256, 257, -1])))
+        else:
+            _head_step(s, c, seed, i, kind, mixed_width)
+            s["slope"] = (0.5, 0.25)[(seed + i) & 1]
+        s["op"] = kind
+        c["steps"].append(s)
+    return c
+
+
+def _linkpred(seed):
+    """a column-sorted matrix whose rows repeat columns (the window drawing), with one row that stores EVERY column: a
+    negative for it is refused at every try"""
+    rng, c, special = _matrix(seed, "linkpred", BOUNDS["linkpred"], window=True, reserve=4000)
+    full = next(int(r) for r in rng.permutation(np.arange(1, c["m"] - 1)) if int(r) not in special)
+    rp, ci, n = c["rp"].astype(np.int64), c["ci"], c["n"]
+    ci = np.concatenate([ci[:rp[full]], np.arange(n, dtype=np.int32), ci[rp[full + 1]:]])
+    lens = np.diff(rp)
+    lens[full] = n
+    rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    c.update(rp=rp, ci=ci, va=eighths(rng, len(ci)), lens=lens.astype(np.int64), full=full, steps=[])
+    for i in range(3):
+        s = _common(rng, seed, i, "linkpred")
+        op = ("find_edges", "negative_sample")[(i + (seed >> 1)) & 1]           # interleaved: f n f or n f n
+        count = QUERY_COUNTS[(seed + 3 * i + (seed >> 3)) % len(QUERY_COUNTS)]
+        tries = int(rng.choice([1, 4, 5, 32, 64]))
+        num_neg = int(rng.choice([1, 3]))
+        if op == "negative_sample" and count > 65:      # (the twin draws count * num_neg * max_tries Philox words)
+            tries, num_neg = min(tries, 5), 1
+        s.update(op=op, kind=op, count=count, num_neg=num_neg, max_tries=tries, exclude_self=bool(rng.integers(0, 2)))
+        c["steps"].append(s)
+    return c
+
+
+def _sampled_dot(seed):
+    """P [q x q] samples X [q x w] · Y [q x w]ᵀ: X's rows are unsorted and repeat columns, Y's ascend strictly.  The twin is a
+    Python loop over (entry of P) x (entries of X's row), so P's long rows belong to, and nearly always point at, short rows
+    of X (test_sampled_dot_gpu.main_case's rule).  Values are eighths: a product is a 64th, every sum is exact"""
+    rng = np.random.default_rng([seed, UNITS.index("sampled_dot")])
+    style = style_of(seed)
+    q = int(rng.integers(40, (300 if style == 3 else 800) + 1))
+    w = int(rng.integers(8, 200))
+    special = set()
+    p_lens, placed = row_lengths(rng, seed, q, BOUNDS["sampled_dot"], cap=30000, keep=special)
+    x_lens = rng.integers(0, 9, q)
+    x_lens[rng.random(q) < 0.15] = 0
+    free = [int(r) for r in rng.permutation(q) if p_lens[r] <= (100 if style == 3 else 8)]
+    x_bounds = (15, 16, 17, 63, 64, 65) + ((LONG - 1, LONG, LONG + 1) if style in (1, 2) else ())
+    for r, L in zip(free, x_bounds):
+        x_lens[r] = L
+    short = np.flatnonzero(x_lens <= 17)
+    p_rows = np.repeat(np.arange(q), p_lens)
+    p_cols = rng.choice(short, len(p_rows))
+    anywhere = rng.random(len(p_rows)) < 0.03
+    p_cols[anywhere] = rng.integers(0, q, int(anywhere.sum()))
+    if "pair2" in placed:
+        p_cols[p_rows == placed["pair2"]] = int(rng.choice(short))
+    p_cols = p_cols[np.lexsort((p_cols, p_rows))]
+    ptr = lambda lens: np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    y_rows = [np.sort(rng.choice(w, int(L), replace=False)) for L in rng.integers(0, min(w, 40) + 1, q)]
+    c = dict(seed=seed, unit="sampled_dot", style=style, forced=forced(seed), placed=placed, m=q, n=q, w=w, rp=ptr(p_lens),
+             ci=p_cols.astype(np.int32), va=eighths(rng, len(p_cols)), lens=p_lens.astype(np.int64), x_lens=x_lens.astype(np.int64),
+             x_rp=ptr(x_lens), x_ci=rng.integers(0, w, int(x_lens.sum())).astype(np.int32), y_rp=ptr([len(r) for r in y_rows]),
+             y_ci=np.concatenate(y_rows).astype(np.int32), adj_offsets=tuple(int(o) for o in rng.integers(0, 4, 3)), steps=[])
+    c.update(x_va=eighths(rng, len(c["x_ci"])), y_va=eighths(rng, len(c["y_ci"])))
+    # the product step: A = the first ra rows of X, every row cut to 65 entries (the twin walks X's row once per entry of
+    # C), B = Yᵀ, C's pattern by scipy on patterns of ones (nothing cancels)
+    import scipy.sparse as sp
+    ra = min(q, max(12, 20000 // q))
+    sub = sub_rows(c["x_rp"], 0, ra, c["x_ci"], c["x_va"])
+    a_rp, a_ci, a_va = cut_rows(sub[0], 65, sub[1], sub[2])
+    ones = lambda rp_, ci_, shape: sp.csr_matrix((np.ones(len(ci_)), ci_.astype(np.int64), rp_.astype(np.int64)), shape=shape)
+    C = (ones(a_rp, a_ci, (ra, w)) @ ones(c["y_rp"], c["y_ci"], (q, w)).T).tocsr()
+    C.sort_indices()
+    c["prod"] = dict(ra=ra, a_rp=a_rp, a_ci=a_ci, a_va=a_va, c_rp=C.indptr.astype(np.int32), c_ci=C.indices.astype(np.int32))
+    for i in range(3):
+        s = _common(rng, seed, i, "sampled_dot")
+        op = ("dot", "dot_by_col", "product")[(seed + i + (seed >> 2)) % 3]
+        xm, ym = (("own", "given", "none")[int(rng.integers(0, 3))] for _ in range(2))
+        if op == "product":                             # (a_values / b_values: given, or the operand's own — never both the
+            xm, ym = (v if v != "none" else "own" for v in (xm, ym))            # operands' own: a backward runs at every product step)
+            if xm == ym == "own":
+                xm, ym = (("given", "own"), ("own", "given"))[(seed >> 2) & 1]
+        nx = len(a_ci) if op == "product" else len(c["x_ci"])
+        s.update(op=op, kind=op, x_mode=xm, y_mode=ym, xv=eighths(rng, nx) if xm == "given" else None,
+                 yv=eighths(rng, len(c["y_ci"])) if ym == "given" else None, g=eighths(rng, len(C.indices)))
+        c["steps"].append(s)
+    return c
+
+
+def step_inputs(c, i):
+    """the operands of step i of a later unit, drawn from (seed, unit, step) at every call -> dict of arrays.  Grids: node
+    features small integers, per-entry weights eighths (halves for edge_aggregate: with five feature levels nearly every
+    selection ties), softmax scores in [-8, 8)"""
+    s = c["steps"][i]
+    rng = np.random.default_rng([c["seed"], UNITS.index(c["unit"]), i, 1])
+    m, n, nnz, kind = c["m"], c["n"], len(c["ci"]), s["kind"]
+    H, k = s.get("H", 1), s.get("k", 1)
+    ints = lambda top, *shape: rng.integers(-top, top + 1, shape).astype(np.float32)
+    if kind in ("edge_softmax", "segment_sum"):
+        return dict(scores=(rng.random((nnz, H)) * 16 - 8).astype(np.float32), g=ints(8, nnz, H), perm=rng.permutation(nnz).astype(np.int32))
+    if kind == "gat_edge_softmax":
+        return dict(a_dst=(rng.random((m, H)) * 8 - 4).astype(np.float32), a_src=(rng.random((n, H)) * 8 - 4).astype(np.float32),
+                    g=ints(8, nnz, H))
+    if kind == "spmm_heads":
+        return dict(x=ints(3, n, k), vals=(rng.integers(0, 8, (nnz, H)) / 8.0).astype(np.float32), g=ints(3, m, k))
+    if kind == "sddmm_heads":
+        return dict(a=ints(3, m, k), b=ints(3, n, k), g=(rng.integers(-7, 8, (nnz, H)) / 8.0).astype(np.float32))
+    if kind == "gatv2_scores":
+        return dict(hd=ints(2, m, k), hs=ints(2, n, k), att=ints(2, H, s["F"]), g=(rng.integers(-7, 8, (nnz, H)) / 8.0).astype(np.float32))
+    if kind == "edge_aggregate":
+        return dict(x=ints(2, n, k), w=(rng.integers(-2, 3, (nnz, k)) / 2.0).astype(np.float32), g=ints(3, m, k))
+    if kind == "aggregate":
+        return dict(x=ints(2, n, k), g=ints(8, m, k))
+    if kind == "find_edges":                            # stored pairs, their neighbours, the full row, ids out of range
+        e = rng.integers(0, nnz, s["count"])
+        rows = (np.searchsorted(c["rp"], e, side="right") - 1).astype(np.int64)
+        cols = c["ci"][e].astype(np.int64) + rng.choice([0, 0, 0, 1, -1], s["count"])
+        odd = rng.random(s["count"])
+        rows = np.where(odd < 0.05, rng.choice([-1, m, m + 7, c["full"]], s["count"]), rows)
+        cols = np.where(odd > 0.95, rng.choice([-1, n, n + 5], s["count"]), cols)
+        if s["count"] >= 63:                            # (both ends of both ranges, whatever was drawn)
+            rows[:2], cols[2:4] = (-1, m), (-1, n)
+        return dict(q_rows=rows, q_cols=cols)
+    if kind == "negative_sample":
+        rows = rng.integers(0, m, s["count"])
+        odd = rng.random(s["count"])
+        rows = np.where(odd < 0.1, rng.choice([-1, m, m + 7, c["full"], int(np.argmax(c["lens"]))], s["count"]), rows)
+        rows[0] = c["full"]
+        if s["count"] >= 63:
+            rows[1:3] = (-1, m)
+        return dict(q_rows=rows.astype(np.int64))
+    return {}
+
+
 _MAKERS = dict(construct=_construct, coalesce=_coalesce, sampling=_sampling, aggregate=_aggregate, attention=_attention,
-               sddmm=_sddmm, spgemm=_spgemm, knn=_knn)
+               sddmm=_sddmm, spgemm=_spgemm, knn=_knn, heads=_heads, gatv2=_gatv2, edge_aggregate=_edge_aggregate,
+               sampled_dot=_sampled_dot, linkpred=_linkpred, mixed=_mixed)
 _CASES = {}
 
 
@@ -444,6 +822,9 @@ def twin(c, cut=None, narrow=False):
     from subgraph_ref import induced_subgraph_ref, random_walk_ref
     unit, out = c["unit"], []
     for i, s in enumerate(c["steps"]):
+        if unit in NEW_UNITS:
+            out.append(twin_step(c, i, cut, narrow))
+            continue
         if unit == "knn":
             x, y = s["x"], s["y"]
             if cut is not None:
@@ -515,6 +896,97 @@ def twin(c, cut=None, narrow=False):
                 rp, ci, a_va = cut_products(rp, ci, a_va, c["b_rp"] if s["op"] != "spgemm" else b[0], cut)
             out.append(spgemm_ref(rp, ci, a_va, b[0], b[1], b_va, c["p"], c["n"]))
     return out
+
+
+def drop_last_of_every_head(a, H):
+    """[rows, H F] -> [rows, H (F - 1)]: every head loses its last column"""
+    return np.ascontiguousarray(a.reshape(len(a), H, -1)[:, :, :-1].reshape(len(a), -1))
+
+
+def dot_operands(c, i, cut=None):
+    """a sampled_dot step as sampled_dot_ref takes it: (p = (rowptr, col), number of columns of p, x = (rowptr, col, values
+    or None), y likewise, the common width, x_by_col).  The product step samples A · B on C's pattern with X = A and
+    Y = Bᵀ = Y (B's stable transpose has Y's entry order again, because Y's rows ascend strictly)"""
+    s = c["steps"][i]
+    xv = {"own": c["x_va"], "given": s["xv"], "none": None}[s["x_mode"]]
+    yv = {"own": c["y_va"], "given": s["yv"], "none": None}[s["y_mode"]]
+    if s["op"] == "product":
+        pr = c["prod"]
+        p, x = (pr["c_rp"], pr["c_ci"]), (pr["a_rp"], pr["a_ci"], pr["a_va"] if s["x_mode"] == "own" else xv)
+    else:
+        p, x = (c["rp"], c["ci"]), (c["x_rp"], c["x_ci"], xv)
+    if cut is not None:
+        x = cut_rows(x[0], cut, x[1], x[2])
+        if s["op"] != "product":
+            p = cut_rows(p[0], cut, p[1])
+    return p, c["n"], x, (c["y_rp"], c["y_ci"], yv), c["w"], s["op"] == "dot_by_col"
+
+
+def twin_step(c, i, cut=None, narrow=False):
+    """the twin of step i of a later unit -> tuple of arrays (a per-entry result is followed by its row sums, so that a cut
+    changes values and not only shapes)"""
+    import edge_aggregate_ref as ea
+    import gatv2_ref
+    import heads_ref
+    from linkpred_ref import find_entries_ref, negative_sample_ref
+    from sampled_dot_ref import sampled_dot_ref
+    from sampling_ref import sample_neighbors_ref
+    s = c["steps"][i]
+    kind, H = s["kind"], s.get("H", 1)
+    if c["unit"] == "sampled_dot":
+        p, np_cols, x, y, w, by_col = dot_operands(c, i, cut)
+        vals = sampled_dot_ref(p[0], p[1], np_cols, *x, *y, w, x_by_col=by_col)
+        return vals, heads_ref.row_sums(p[0], vals[:, None])
+    x = step_inputs(c, i)
+    rp, ci = c["rp"], c["ci"]
+    keep = np.ones(len(ci), bool)
+    if cut is not None:
+        keep = (np.arange(len(ci)) - np.repeat(rp[:-1].astype(np.int64), np.diff(rp))) < cut
+        rp, ci = cut_rows(rp, cut, ci)
+    if kind == "find_edges":
+        return (find_entries_ref(rp, ci, x["q_rows"], x["q_cols"]),)
+    if kind == "negative_sample":
+        return (negative_sample_ref(rp, ci, c["n"], x["q_rows"], s["num_neg"], *s["philox"], s["max_tries"], s["exclude_self"]),)
+    if kind == "sample_neighbors":
+        return sample_neighbors_ref(rp, ci, s["ids"], s["fanout"], *s["philox"])
+    if kind == "edge_softmax":
+        sc = x["scores"][keep]
+        return heads_ref.edge_softmax(rp, sc), heads_ref.row_sums(rp, sc)
+    if kind == "gat_edge_softmax":
+        sc = heads_ref.gat_scores(rp, ci, x["a_dst"], x["a_src"], s["slope"])
+        return heads_ref.edge_softmax(rp, sc), heads_ref.row_sums(rp, sc)
+    if kind == "segment_sum":
+        sub, xs, perm = segment_operands(c, i, x, keep)
+        return (heads_ref.segment_sum(sub, xs, perm),)
+    if kind == "aggregate":
+        return select_host(rp, ci, x["x"][:, :-1] if narrow and s["k"] > 1 else x["x"], s["select"])
+    if kind == "edge_aggregate":
+        xx, ww = (x["x"][:, :-1], x["w"][keep][:, :-1]) if narrow and s["k"] > 1 else (x["x"], x["w"][keep])
+        return ea.forward(rp, ci, xx, ww, s["msg"], s["act"], s["reduce"])
+    less = (lambda a: drop_last_of_every_head(a, H)) if narrow and s["F"] > 1 else (lambda a: a)
+    if kind == "spmm_heads":
+        return (heads_ref.spmm_heads(rp, ci, None, x["vals"][keep], less(x["x"]), H),)
+    if kind == "sddmm_heads":
+        out = heads_ref.sddmm_heads(rp, ci, less(x["a"]), less(x["b"]), H)
+        return out, heads_ref.row_sums(rp, out)
+    if kind == "gatv2_scores":
+        att = x["att"][:, :-1] if narrow and s["F"] > 1 else x["att"]
+        out = gatv2_ref.scores(rp, ci, less(x["hd"]), less(x["hs"]), att, s["slope"])
+        return out, heads_ref.row_sums(rp, out)
+    raise KeyError(kind)
+
+
+def segment_operands(c, i, x, keep=None):
+    """(rowptr of the step's rows, their entries of x [., H], the permutation to read them through or None): as in the
+    attention unit, a stretch of the rows through a permutation of its own entries"""
+    s, rp = c["steps"][i], c["rp"]
+    lo, hi = s["rows"]
+    b, e = int(rp[lo]), int(rp[hi])
+    k = np.ones(e - b, bool) if keep is None else keep[b:e]
+    lens = np.bincount(np.repeat(np.arange(hi - lo), np.diff(rp[lo:hi + 1]))[k], minlength=hi - lo)
+    sub = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    perm = np.argsort(x["perm"][b:e][k]).astype(np.int32) if s["perm"] else None
+    return sub, x["scores"][b:e][k], perm
 
 
 def cut_products(rp, ci, va, b_rp, cut):
