@@ -23,6 +23,7 @@ ERR_INTERNAL = 7             # GCN_ERR_INTERNAL (a consistency guard tripped: gc
 DTYPE_F32, DTYPE_BF16 = 0, 1 # GCN_DTYPE_F32 / GCN_DTYPE_BF16 (gcn_spmm_csr_bf16_epilogue)
 REDUCE_MAX, REDUCE_MIN = 0, 1 # GCN_REDUCE_MAX / GCN_REDUCE_MIN (gcn_aggregate_csr)
 REDUCE_SUM = 2               # GCN_REDUCE_SUM (gcn_edge_aggregate_csr_f32)
+REDUCE_MEAN, REDUCE_VAR, REDUCE_STD = 3, 4, 5       # GCN_REDUCE_MEAN / _VAR / _STD (gcn_aggregate_multi_csr_f32)
 EDGE_OP_ADD, EDGE_OP_MUL = 0, 1      # GCN_EDGE_OP_*: how a node row and an entry's row of features meet
 EDGE_ACT_NONE, EDGE_ACT_RELU = 0, 1  # GCN_EDGE_ACT_*
 SAMPLE_LONG_ROW = 2048       # GCN_SAMPLE_LONG_ROW: longer rows get a workgroup, not a wave (gcn_sample_neighbors_csr)
@@ -155,6 +156,11 @@ SIGNATURES = {
                                          ctypes.c_size_t, _c_p]),
     "gcn_aggregate_backward_csr": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_p,
                                                   ctypes.c_size_t, _c_p]),
+    "gcn_aggregate_multi_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_i32, _c_p, ctypes.c_float,
+                                                   _c_p, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_aggregate_multi_backward_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i32,
+                                                            _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t,
+                                                            _c_p]),
     "gcn_edge_aggregate_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32,
                                                   _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_edge_aggregate_backward_x_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i32,

@@ -4,6 +4,7 @@ GraphSAGE's aggregators (PyG ``SAGEConv(aggr=...)``, DGL ``copy_u_max``).
     h = gcn_amd.aggregate(adj, x, "max")                      # h[r, j] = max over the entries e of row r of x[col[e], j]
     h, arg = gcn_amd.aggregate(adj, x, "min", return_arg=True)  # arg[r, j]: the CSR entry index that supplied h[r, j]
     h = gcn_amd.aggregate(adj, x, "mean")                     # the SpMM on a pattern-valued twin of adj
+    h = gcn_amd.aggregate_multi(adj, x, ("mean", "max", "min", "std"))   # [m, 4 k]: four statistics from one gather per entry
 
 Only the pattern of ``adj`` is used: its values are ignored, and every stored entry counts, duplicated (row, column)
 pairs included.  max / min run on gcn_amd/csrc/aggregate.hip (fp32 or bf16, exact: a selection rounds nothing); an empty
@@ -12,6 +13,8 @@ selected entry only — torch's ``scatter_reduce`` splits it among ties — and 
 the transposed pattern.  The kernels take no plan and only enqueue, so after one eager call everything here runs
 inside a captured step.  There is no CPU path: CPU tensors raise.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -21,6 +24,8 @@ from .spmm import CsrAdjacency, spmm
 _CHUNK = 4096                # entries per workspace partial: GCN_AGGREGATE_WS_BYTES in include/gcn_spmm.h
 _REDUCE = {"max": _lib.REDUCE_MAX, "min": _lib.REDUCE_MIN}
 _DTYPE = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16}
+_MULTI = {"max": _lib.REDUCE_MAX, "min": _lib.REDUCE_MIN, "sum": _lib.REDUCE_SUM, "mean": _lib.REDUCE_MEAN,
+          "var": _lib.REDUCE_VAR, "std": _lib.REDUCE_STD}
 
 
 def _ws_bytes(nnz, k):
@@ -114,3 +119,86 @@ def aggregate(adj, x, reduce="max", return_arg=False):
     if adj.m == 0 or adj.nnz == 0:                       # (nothing to sum: no twin, no plan)
         return x.new_zeros((adj.m, int(x.shape[1])))
     return spmm(_pattern_twin(adj, reduce), x)
+
+
+def _multi_scratch(adj, k, device):
+    """the "aggregate_multi" buffer of the adjacency (GCN_AGGREGATE_MULTI_WS_BYTES: a flag and a 32-byte column state per
+    chunk, long row and column), shared by the forward and the backward; None for a pattern without entries"""
+    return adj._scratch.get("aggregate_multi", 16 + 64 * int(k) * ((adj.nnz + _CHUNK - 1) // _CHUNK), device) if adj.nnz else None
+
+
+class _MultiFunction(torch.autograd.Function):
+    """(out, argmax, argmin) = the requested statistics side by side and the entries that supplied the extrema (None for a
+    plane not requested); the gradient in x by one walk of the transposed pattern"""
+
+    @staticmethod
+    def forward(ctx, adj, x, reduce, eps):
+        x = x.detach().contiguous()
+        k, nred = int(x.shape[1]), len(reduce)
+        codes = (ctypes.c_int32 * nred)(*[_MULTI[r] for r in reduce])
+        new = lambda dtype, width=k: torch.empty((adj.m, width), dtype=dtype, device=x.device)
+        out = new(torch.float32, nred * k)
+        argmax = new(torch.int32) if "max" in reduce else None
+        argmin = new(torch.int32) if "min" in reduce else None
+        moments = "var" in reduce or "std" in reduce
+        # the backward of var / std reads the mean: a plane of out, or a buffer of its own
+        mean = new(torch.float32) if ctx.needs_input_grad[1] and moments and "mean" not in reduce else None
+        ws = _multi_scratch(adj, k, x.device)
+        call("gcn_aggregate_multi_csr_f32", adj.rowptr, adj.col, adj.m, adj.n, adj.nnz, x, k, nred, codes, eps, out, argmax, argmin,
+             mean, ws, ws.numel() if ws is not None else 0, device=x.device)
+        ctx.adj, ctx.reduce, ctx.codes = adj, reduce, codes
+        ctx.slots = [t is not None for t in (argmax, argmin, mean)]
+        ctx.save_for_backward(x, out, *[t for t in (argmax, argmin, mean) if t is not None])
+        ctx.mark_non_differentiable(*[t for t in (argmax, argmin) if t is not None])
+        return out, argmax, argmin
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_max, _g_min):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        x, out, *rest = ctx.saved_tensors
+        rest = iter(rest)
+        argmax, argmin, mean = [next(rest) if have else None for have in ctx.slots]
+        adj, reduce = ctx.adj, ctx.reduce
+        g = g.contiguous()
+        k = int(x.shape[1])
+        gx = torch.empty((adj.n, k), dtype=torch.float32, device=g.device)
+        affine = any(r in reduce for r in ("sum", "mean", "var", "std"))
+        ab = torch.empty((adj.m, 2 * k), dtype=torch.float32, device=g.device) if affine else None
+        trowptr, trow, tperm = adj.tpattern()
+        ws = _multi_scratch(adj, k, g.device)
+        call("gcn_aggregate_multi_backward_csr_f32", trowptr, trow, tperm, adj.rowptr, adj.n, adj.m, adj.nnz, g, x, k, len(reduce),
+             ctx.codes, out, argmax, argmin, mean, ab, gx, ws, ws.numel() if ws is not None else 0, device=g.device)
+        return None, gx, None, None
+
+
+def aggregate_multi(adj, x, reduce=("mean", "max", "min", "std"), eps=1e-5, return_arg=False):
+    """Several statistics of every row's neighbourhood from ONE gather per stored entry (PNA's aggregators, PyG's
+    ``MultiAggregation(mode="cat")``): out[r, p k : (p + 1) k] = the element-wise ``reduce[p]`` of x[c, :] over the stored
+    entries (r, c) of row r of ``adj`` (any CsrAdjacency: pattern only, duplicates are separate entries).
+
+    x: [n, k] fp32 device tensor, differentiable (one walk of the transposed pattern for all planes).  reduce: distinct
+    names of "max", "min", "sum", "mean", "var" (population variance, from sums shifted by the row's first entry: no
+    cancellation), "std" = sqrt(var + eps); eps >= 0, and > 0 with "std".  An empty row gives zeros in every plane; a row of
+    one entry or of equal entries has var exactly 0; a non-finite entry makes the row's var / std NaN.  max / min follow
+    ``aggregate``'s rule and their gradient goes to the selected entry.  ``return_arg=True`` also returns (argmax, argmin),
+    int32 [m, k] CSR entry indices (-1 for an empty row), None for a plane not requested, not differentiable.
+    TypeError for a non-CsrAdjacency, ValueError for a wrong shape, an empty, unknown or repeated reduce or a bad eps,
+    GcnAmdError for a CPU tensor or a dtype other than fp32 (bf16 is not served by this unit)."""
+    if not isinstance(adj, CsrAdjacency):
+        raise TypeError("aggregate_multi: adj must be a CsrAdjacency")
+    reduce = (reduce,) if isinstance(reduce, str) else tuple(reduce)
+    if not reduce or any(r not in _MULTI for r in reduce) or len(set(reduce)) != len(reduce):
+        raise ValueError(f"aggregate_multi: reduce must be distinct names of {sorted(_MULTI)}, not {reduce!r}")
+    eps = float(eps)
+    if not 0.0 <= eps < float("inf") or (eps == 0.0 and "std" in reduce):
+        raise ValueError(f"aggregate_multi: eps must be finite and >= 0 (> 0 with 'std'), not {eps!r}")
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != adj.n or x.shape[1] < 1:
+        raise ValueError(f"aggregate_multi: x must be a 2-D tensor of n = {adj.n} rows and at least one column")
+    if not x.is_cuda:
+        raise _lib.GcnAmdError("aggregate_multi: x must be a CUDA/HIP tensor (no CPU path in gcn_amd)")
+    if x.dtype != torch.float32:
+        raise _lib.GcnAmdError("aggregate_multi: x must be fp32")
+    out, argmax, argmin = _MultiFunction.apply(adj, x, reduce, eps)
+    return (out, argmax, argmin) if return_arg else out

@@ -20,7 +20,7 @@
 // Dispatch by row length happens in the kernels (the host never reads a row length) and is gather_rows.h's: 8 rows a
 // wave, rows of more than kAggChunk entries by chunk partials (here a (value, entry) pair) merged in chunk order.
 //
-// Selection rule (numpy's argmax / argmin): the first entry in CSR order among equals, -0.0 == +0.0; a NaN beats every
+// Selection rule (numpy's argmax / argmin; select_rule.h): the first entry in CSR order among equals, -0.0 == +0.0; a NaN beats every
 // number and the first NaN wins; +-inf are ordinary values.  No arithmetic touches a value: the bits stored are the
 // winner's bits, so bf16 and fp32 share the code and the result is exact.
 #include <hip/hip_runtime.h>
@@ -29,12 +29,11 @@
 #include <cmath>
 
 #include "gather_rows.h"
+#include "select_rule.h"
 #include "spmm_kernels.h"
 
 namespace gcn {
 namespace {
-
-constexpr int kNone = INT_MAX;                         // "no entry yet" (a stored entry index is below nnz <= INT_MAX)
 
 using bf16_t = unsigned short;
 
@@ -115,16 +114,6 @@ struct State {
 };
 struct Pair { float v; int e; };                       // one column of a State in the workspace
 
-// is (av, ae) the better candidate than (bv, be)?  A total order (kNone, "no entry", below everything): usable in any
-// merge order.
-template <bool MAX>
-__device__ __forceinline__ bool better(float av, int ae, float bv, int be) {
-  const bool an = av != av, bn = bv != bv;
-  const bool gt = MAX ? av > bv : av < bv;             // (false when either is a NaN)
-  const bool eq = av == bv || (an && bn);
-  return ae != kNone && (be == kNone || (an && !bn) || gt || (eq && ae < be));
-}
-
 // ---- the operations -----------------------------------------------------------------------------------------------------
 // index(t): what entry t of the walked CSR names (loaded by one lane per entry, broadcast to the slot that takes it);
 // fetch(ix, j): the gathered data of that entry at columns j .. j + VEC (always a legal address: issued before it is known
@@ -154,20 +143,11 @@ struct SelectOp {                                      // the forward
   }
   static __device__ void fold(State<VEC>& s, const Item& it, Index, int t, bool ok) {
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      const float v = it.v[i], b = s.v[i];
-      const bool take = ok && (s.e[i] == kNone || (MAX ? v > b : v < b) || (v != v && b == b));
-      s.v[i] = take ? v : b;
-      s.e[i] = take ? t : s.e[i];
-    }
+    for (int i = 0; i < VEC; ++i) select_fold<MAX>(s.v[i], s.e[i], it.v[i], t, ok);
   }
   static __device__ void merge(State<VEC>& s, const State<VEC>& o) {
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      const bool take = better<MAX>(o.v[i], o.e[i], s.v[i], s.e[i]);
-      s.v[i] = take ? o.v[i] : s.v[i];
-      s.e[i] = take ? o.e[i] : s.e[i];
-    }
+    for (int i = 0; i < VEC; ++i) select_merge<MAX>(s.v[i], s.e[i], o.v[i], o.e[i]);
   }
   static __device__ void merge_next(Pair& s, Pair o) {
     if (better<MAX>(o.v, o.e, s.v, s.e)) s = o;

@@ -1,6 +1,9 @@
 // api_units.cpp — the native C ABI of libgcnspmm.so: the plan-free units (edge softmax, head-batched attention, GATv2 scores,
-// max / min aggregation, edge-feature aggregation, sampling, subgraphs and walks, entry lookup, bucketing, coalescing, SpGEMM, sampled dot, kNN, row
-// gather).  Each entry point is the argument checks of include/gcn_spmm.h in front of one launcher of spmm_kernels.h (edge_message.h).
+// max / min aggregation, multi-aggregation, edge-feature aggregation, sampling, subgraphs and walks, entry lookup, bucketing, coalescing, SpGEMM, sampled dot, kNN, row
+// gather).  Each entry point is the argument checks of include/gcn_spmm.h in front of one launcher of spmm_kernels.h (edge_message.h, aggregate_multi.h).
+#include <cmath>
+
+#include "aggregate_multi.h"
 #include "edge_message.h"
 #include "plan_policy.h"
 
@@ -219,6 +222,56 @@ int gcn_aggregate_backward_csr(const int32_t* trowptr, const int32_t* trow, cons
     return hip_status(hipMemsetAsync(gx, 0, (size_t)n * (size_t)k * (dtype == GCN_DTYPE_BF16 ? 2 : 4), st));
   if (!trowptr || !trow || !tperm || !g || !arg || !ws || ws_bytes < aggregate_workspace_bytes(nnz, k)) return GCN_ERR_INVALID_ARG;
   return hip_status(launch_aggregate_backward(trowptr, trow, tperm, n, nnz, g, dtype == GCN_DTYPE_BF16, arg, k, gx, ws, st));
+}
+
+// Multi-aggregation (aggregate_multi.hip).  The reduce codes, a short HOST array, into the plane table: false for a null
+// array, nred outside 1 .. 6, an unknown or a repeated code.
+static bool multi_planes(int32_t nred, const int32_t* codes, MultiPlanes* pl) {
+  if (nred < 1 || nred > kMultiStats || !codes) return false;
+  for (int s = 0; s < kMultiStats; ++s) pl->at[s] = -1;
+  pl->nred = nred;
+  for (int p = 0; p < nred; ++p) {
+    if (codes[p] < 0 || codes[p] >= kMultiStats || pl->at[codes[p]] >= 0) return false;
+    pl->at[codes[p]] = (signed char)p;
+  }
+  return true;
+}
+
+static_assert(kMultiMax == GCN_REDUCE_MAX && kMultiMin == GCN_REDUCE_MIN && kMultiSum == GCN_REDUCE_SUM &&
+              kMultiMean == GCN_REDUCE_MEAN && kMultiVar == GCN_REDUCE_VAR && kMultiStd == GCN_REDUCE_STD, "include/gcn_spmm.h");
+
+int gcn_aggregate_multi_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t n, int32_t nnz, const float* x,
+                                int32_t k, int32_t nred, const int32_t* reduce_codes, float eps, float* out, int32_t* argmax,
+                                int32_t* argmin, float* save_mean, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  MultiPlanes pl;
+  if (!multi_planes(nred, reduce_codes, &pl)) return GCN_ERR_INVALID_ARG;
+  if (!std::isfinite(eps) || eps < 0.f || (eps == 0.f && pl.has(kMultiStd))) return GCN_ERR_INVALID_ARG;
+  if (aggregate_args(m, n, nnz, GCN_DTYPE_F32, k, &rc)) return rc;
+  if (!out || (pl.has(kMultiMax) && !argmax) || (pl.has(kMultiMin) && !argmin)) return GCN_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (nnz == 0) return hip_status(launch_aggregate_multi_empty(m, k, pl, out, argmax, argmin, save_mean, st));
+  if (!rowptr || !col || !x || !ws || ws_bytes < aggregate_multi_workspace_bytes(nnz, k)) return GCN_ERR_INVALID_ARG;
+  return hip_status(launch_aggregate_multi(rowptr, col, m, nnz, x, k, pl, eps, out, argmax, argmin, save_mean, ws, st));
+}
+
+int gcn_aggregate_multi_backward_csr_f32(const int32_t* trowptr, const int32_t* trow, const int32_t* tperm, const int32_t* rowptr,
+                                         int32_t n, int32_t m, int32_t nnz, const float* g, const float* x, int32_t k, int32_t nred,
+                                         const int32_t* reduce_codes, const float* out, const int32_t* argmax, const int32_t* argmin,
+                                         const float* save_mean, float* ab, float* gx, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  MultiPlanes pl;
+  if (!multi_planes(nred, reduce_codes, &pl)) return GCN_ERR_INVALID_ARG;
+  if (aggregate_args(n, m, nnz, GCN_DTYPE_F32, k, &rc)) return rc;
+  if (!gx) return GCN_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (nnz == 0) return hip_status(launch_fill_words(gx, (size_t)n * (size_t)k, 0u, st));
+  if (!trowptr || !trow || !tperm || !g || !x || !ws || ws_bytes < aggregate_multi_workspace_bytes(nnz, k)) return GCN_ERR_INVALID_ARG;
+  if ((pl.has(kMultiMax) && !argmax) || (pl.has(kMultiMin) && !argmin) || (pl.affine() && (!rowptr || !ab))) return GCN_ERR_INVALID_ARG;
+  if (pl.moments() && (pl.has(kMultiMean) || pl.has(kMultiStd)) && !out) return GCN_ERR_INVALID_ARG;
+  if (pl.moments() && !pl.has(kMultiMean) && !save_mean) return GCN_ERR_INVALID_ARG;
+  return hip_status(launch_aggregate_multi_backward(trowptr, trow, tperm, rowptr, n, m, nnz, g, x, k, pl, out, argmax, argmin,
+                                                    save_mean, ab, gx, ws, st));
 }
 
 static_assert(kEdgeOpAdd == GCN_EDGE_OP_ADD && kEdgeOpMul == GCN_EDGE_OP_MUL && kEdgeActNone == GCN_EDGE_ACT_NONE &&

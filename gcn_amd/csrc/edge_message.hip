@@ -39,14 +39,13 @@
 #include "edge_message.h"
 #include "gather_rows.h"
 #include "long_chunks.h"
+#include "select_rule.h"
 #include "spmm_kernels.h"
 
 #pragma clang fp contract(off)
 
 namespace gcn {
 namespace {
-
-constexpr int kNone = INT_MAX;                         // "no entry yet" (a stored entry index is below nnz <= INT_MAX)
 
 struct EdgeArgs {
   const int *idx, *perm;                               // per entry of the walked CSR: the gathered row; the entry's row of w (null: itself)
@@ -161,16 +160,6 @@ struct State {
   int e[VEC];                                          // its entry index, kNone before the first
 };
 struct Pair { float v; int e; };                       // one column of a State in the workspace
-
-// is (av, ae) the better candidate than (bv, be)?  A total order (kNone, "no entry", below everything): usable in any
-// merge order.  (aggregate.hip's rule.)
-template <bool MAX>
-__device__ __forceinline__ bool better(float av, int ae, float bv, int be) {
-  const bool an = av != av, bn = bv != bv;
-  const bool gt = MAX ? av > bv : av < bv;             // (false when either is a NaN)
-  const bool eq = av == bv || (an && bn);
-  return ae != kNone && (be == kNone || (an && !bn) || gt || (eq && ae < be));
-}
 
 template <int VEC_, int LPS_, bool MAX>
 struct EdgeSelectOp : EdgeArgs {

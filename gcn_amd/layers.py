@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from torch.nn.parameter import Parameter
 
 from . import preprocess, reorder, timers
-from .aggregate import aggregate
+from .aggregate import aggregate, aggregate_multi
 from .edgefeat import edge_aggregate
 from .attention import edge_softmax, gat_edge_softmax, gatv2_scores, spmm_heads
 from .spgemm import HypergraphLaplacian
@@ -344,6 +344,99 @@ class SAGEConv(nn.Module):
     def __repr__(self):
         return (f"SAGEConv ({self.in_features} -> {self.out_features}, aggr={self.aggr}"
                 f"{'' if self.weight_root is not None else ', no root weight'})")
+
+
+class PNAConv(nn.Module):
+    """Principal neighbourhood aggregation (Corso et al. 2020; PyG's / DGL's ``PNAConv``) in its simple form, one tower and
+    no edge features, on the one-pass multi-aggregation:
+
+        h   = aggregate_multi(adj, x_src, aggregators)         # [m, A k]: every statistic from one gather per entry
+        s   = log(n_r + 1) / avg_log_degree                    # per row of adj, from its row lengths
+        h   = cat([h, h * s, h / s])                           # the requested scalers (h / s is 0 where n_r = 0)
+        out = cat([x_dst, h]) · weight + bias
+
+    ``aggregators``: distinct names of "mean", "max", "min", "std", "var", "sum"; ``scalers``: of "identity",
+    "amplification", "attenuation".  ``avg_log_degree`` is the mean of log(n_r + 1) over the TRAINING graph's rows,
+    ``PNAConv.avg_log_degree(adj)``.  ``forward((x_src, x_dst), adj)`` takes a sampled block as ``SAGEConv`` does.
+    Parameters: ``weight`` [(1 + A S) in_features, out_features] and ``bias``, uniform in +-1/sqrt(out_features).  The
+    aggregation is fp32 (under autocast too)."""
+
+    SCALERS = ("identity", "amplification", "attenuation")
+
+    def __init__(self, in_features, out_features, aggregators=("mean", "max", "min", "std"),
+                 scalers=("identity", "amplification", "attenuation"), *, avg_log_degree, bias=True, eps=1e-5):
+        super().__init__()
+        self.aggregators, self.scalers = tuple(aggregators), tuple(scalers)
+        if not self.scalers or any(s not in self.SCALERS for s in self.scalers) or len(set(self.scalers)) != len(self.scalers):
+            raise ValueError(f"PNAConv: scalers must be distinct names of {self.SCALERS}, not {scalers!r}")
+        if not float(avg_log_degree) > 0.0:
+            raise ValueError(f"PNAConv: avg_log_degree must be > 0, not {avg_log_degree!r}")
+        self.in_features, self.out_features = int(in_features), int(out_features)
+        self.delta, self.eps = float(avg_log_degree), float(eps)
+        _check_aggregators(self.aggregators, self.eps)
+        width = (1 + len(self.aggregators) * len(self.scalers)) * self.in_features
+        self.weight = Parameter(torch.empty(width, self.out_features))
+        if bias:
+            self.bias = Parameter(torch.empty(self.out_features))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    @staticmethod
+    def avg_log_degree(adj):
+        """the mean of log(n_r + 1) over the rows of ``adj`` (a Python float; one host read)"""
+        return float(_log_degree(adj).mean()) if adj.m else 0.0
+
+    def reset_parameters(self):
+        stdv = 1.0 / math.sqrt(self.out_features)
+        for p in (self.weight, self.bias):
+            if p is not None:
+                p.data.uniform_(-stdv, stdv)
+
+    def forward(self, input, adj):
+        if isinstance(input, (tuple, list)):               # a bipartite block: (x_src [adj.n rows], x_dst [adj.m rows])
+            if len(input) != 2:
+                raise ValueError("PNAConv: a bipartite input is the pair (x_src, x_dst)")
+            x, root = input
+        else:
+            x = root = input
+            if adj.m != adj.n:
+                raise ValueError(f"PNAConv: adjacency {adj.m}x{adj.n} needs the pair (x_src, x_dst)")
+        if x.dim() != 2 or x.shape[0] != adj.n or root.dim() != 2 or root.shape[0] != adj.m or root.shape[1] != x.shape[1]:
+            raise ValueError(f"PNAConv: adjacency {adj.m}x{adj.n}, input ({tuple(x.shape)}, {tuple(root.shape)})")
+        h = aggregate_multi(adj, x.float(), self.aggregators, self.eps)
+        s = _log_degree(adj) / self.delta                  # [m, 1]
+        parts = [root.float()]
+        for name in self.scalers:
+            if name == "identity":
+                parts.append(h)
+            elif name == "amplification":
+                parts.append(h * s)
+            else:
+                parts.append(h * torch.where(s > 0, 1.0 / s, torch.zeros_like(s)))
+        out = torch.mm(torch.cat(parts, dim=1), self.weight)
+        return out + self.bias if self.bias is not None else out
+
+    def __repr__(self):
+        return (f"PNAConv ({self.in_features} -> {self.out_features}, aggregators={list(self.aggregators)}, "
+                f"scalers={list(self.scalers)})")
+
+
+def _log_degree(adj):
+    """log(n_r + 1) per row of ``adj`` as [m, 1] fp32, computed once per adjacency and kept on it"""
+    t = getattr(adj, "_log_degree", None)
+    if t is None:
+        rp = adj.rowptr
+        t = adj._log_degree = torch.log1p((rp[1:] - rp[:-1]).to(torch.float32)).unsqueeze(1)
+    return t
+
+
+def _check_aggregators(aggregators, eps):
+    known = ("mean", "max", "min", "std", "var", "sum")
+    if not aggregators or any(a not in known for a in aggregators) or len(set(aggregators)) != len(aggregators):
+        raise ValueError(f"PNAConv: aggregators must be distinct names of {known}, not {aggregators!r}")
+    if not 0.0 <= eps < float("inf") or (eps == 0.0 and "std" in aggregators):
+        raise ValueError(f"PNAConv: eps must be finite and >= 0 (> 0 with 'std'), not {eps!r}")
 
 
 class _GINBase(nn.Module):

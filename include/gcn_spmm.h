@@ -305,6 +305,63 @@ int gcn_aggregate_backward_csr(const int32_t* trowptr_dev, const int32_t* trow_d
                                int32_t m, int32_t nnz, const void* g, int32_t dtype, const int32_t* arg, int32_t k, void* gx,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* Multi-aggregation (aggregate_multi.hip; PNA, PyG's MultiAggregation, DGL's PNAConv): up to six statistics of every row's
+ * neighbourhood from ONE gather per stored entry, and the gradient of all of them in one walk of the transposed pattern.
+ * Plan-free like the family above: the caller's CSR, one 4-byte memset node and kernels (no allocation, no host
+ * synchronisation, no host read of device data: legal inside a stream capture, after one eager call), no atomics, every
+ * output element has one writer and every reduction a fixed order: the same bits at every call.  Only the pattern is
+ * used; duplicated (row, column) pairs are separate entries; any row length.  All operands fp32, row-major.
+ *   reduce_codes: a HOST array of nred distinct codes (1 <= nred <= 6) of GCN_REDUCE_MAX, _MIN, _SUM, _MEAN, _VAR, _STD; it is
+ *   read during the call and travels in the kernel argument.
+ *   out [m x nred k]: plane p of row r, the statistic reduce_codes[p] of { x[col[e], j] : e in row r }, sits at columns
+ *   p k .. p k + k - 1 (PyG's mode="cat" layout).  Planes not requested are neither computed into out nor reflected in its
+ *   width.  argmax / argmin [m x k] int32: the entry that supplied the max / min; each is required when its plane is
+ *   requested and ignored (may be NULL) otherwise.  save_mean [m x k] or NULL: when given, the mean is also written there
+ *   (the backward of var / std needs it when no mean plane is requested).
+ *   sum = S0 = the fp32 sum of x (slot s of 4 adds the entries s, s + 4, ... of a run of at most 4096 in ascending order,
+ *   the slots are merged by an xor butterfly, a long row's runs in order); mean = S0 / n_r.
+ *   var = (S2 - S1 S1 / n_r) / n_r, the population variance, from the shifted sums S1 = sum d, S2 = sum d d (fmaf),
+ *   d = x - K with K the row's FIRST entry; then var < 0 ? 0 : var (a NaN passes).  std = sqrtf(var + eps).
+ *   max / min: the selection rule of gcn_aggregate_csr; the winner's bits are stored.
+ * Contract.  An empty row: 0 in every plane, std included, and arg -1.  A row of one entry, or whose entries are all
+ * equal: var exactly 0, std == sqrtf(eps).  A row with a non-finite entry: sum, mean, max, min as IEEE arithmetic and
+ * the selection rule give them; var and std NaN (fp64 numpy's answer).  (|x - K| above 1.8e19 overflows d d: var is then NaN
+ * or inf where fp64 would still be finite.)
+ * 16-byte accesses when x, out, argmax, argmin and save_mean are 16-byte aligned and k % 4 == 0, element accesses otherwise;
+ * both give the same bits.
+ * ws: device scratch of at least GCN_AGGREGATE_MULTI_WS_BYTES(nnz, k) bytes, 16-byte aligned, owned by the call until it
+ * has run: a flag and one 32-byte column state per (chunk of 4096 entries, long row, column).
+ * GCN_ERR_INVALID_ARG, before any device pointer is read: null pointers, negative sizes, k < 1, k > 16 * 65535, nred
+ * outside 1 .. 6, a repeated or unknown code, eps < 0 or not finite, eps == 0 with GCN_REDUCE_STD requested, a missing
+ * arg array for a requested extremum, a short workspace.  m == 0: GCN_OK, nothing launched; nnz == 0: out is zeroed and
+ * the arg arrays set to -1, by kernels. */
+#define GCN_AGGREGATE_MULTI_WS_BYTES(nnz, k) (16 + 64 * (size_t)(k) * (((size_t)(nnz) + 4095) / 4096))
+#define GCN_REDUCE_MEAN 3
+#define GCN_REDUCE_VAR 4
+#define GCN_REDUCE_STD 5
+int gcn_aggregate_multi_csr_f32(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t n, int32_t nnz,
+                                const float* x, int32_t k, int32_t nred, const int32_t* reduce_codes, float eps, float* out,
+                                int32_t* argmax, int32_t* argmin, float* save_mean, void* ws, size_t ws_bytes, void* stream);
+/* Its backward: the gradient in x of all requested planes in one walk of the TRANSPOSED pattern (trowptr_dev [n + 1],
+ * trow_dev, tperm_dev as in gcn_aggregate_backward_csr), no atomics, one writer per element, nothing of size nnz x k.
+ * For transposed row c and its entries t, r = trow[t], e = tperm[t], every factor at [r, j]:
+ *   gx[c, j] = sum_t  g_sum + g_mean / n_r + g_var 2 (x[c, j] - mean) / n_r + g_std (x[c, j] - mean) / (n_r std)
+ *                     + g_max [argmax == e] + g_min [argmin == e]
+ * The moment part is affine in x[c, j]: an element-wise kernel writes a | b [m x 2 k] into `ab` (a = g_sum + g_mean / n_r -
+ * b mean, b = 2 g_var / n_r + g_std / (n_r std); rowptr_dev gives n_r, zeros for an empty row), and the walk stores
+ * sum a + x[c, j] sum b + the selected g (a zero sum b takes nothing of x).  The split rounds relative to |b| (|x| + |mean|),
+ * not to |b| |x - mean|: features far from 0 with a small spread lose that ratio in the var / std gradient.  The formula
+ * does not depend on whether var was clamped.
+ * g [m x nred k] in the forward's layout; x [n x k]; out, argmax, argmin, save_mean as the forward wrote them: out is read
+ * when var or std is requested together with mean or std (the mean and std planes), save_mean when var or std is
+ * requested without mean; ab is needed when any of sum, mean, var, std is requested; the arg arrays when their planes
+ * are.  gx [n x k].  n == 0: nothing launched; nnz == 0: gx is zeroed.  Same workspace rule and argument errors. */
+int gcn_aggregate_multi_backward_csr_f32(const int32_t* trowptr_dev, const int32_t* trow_dev, const int32_t* tperm_dev,
+                                         const int32_t* rowptr_dev, int32_t n, int32_t m, int32_t nnz, const float* g,
+                                         const float* x, int32_t k, int32_t nred, const int32_t* reduce_codes, const float* out,
+                                         const int32_t* argmax, const int32_t* argmin, const float* save_mean, float* ab,
+                                         float* gx, void* ws, size_t ws_bytes, void* stream);
+
 /* Edge-feature message passing (edge_message.hip; DGL's u_op_e -> reduce: GINE, MPNN, CGConv): a feature VECTOR per stored
  * entry beside the gathered node row.  Plan-free like the aggregation family above: the caller's CSR, one memset node and
  * kernels (no allocation, no host synchronisation, no host read of device data: legal inside a stream capture), no
