@@ -1,11 +1,12 @@
 // api_units.cpp — the native C ABI of libgcnspmm.so: the plan-free units (edge softmax, head-batched attention, GATv2 scores,
-// max / min aggregation, multi-aggregation, edge-feature aggregation, sampling, subgraphs and walks, entry lookup, bucketing, coalescing, SpGEMM, sampled dot, kNN, row
-// gather).  Each entry point is the argument checks of include/gcn_spmm.h in front of one launcher of spmm_kernels.h (edge_message.h, aggregate_multi.h).
+// max / min aggregation, multi-aggregation, relation-typed aggregation, edge-feature aggregation, sampling, subgraphs and walks, entry lookup, bucketing, coalescing, SpGEMM, sampled dot, kNN, row
+// gather).  Each entry point is the argument checks of include/gcn_spmm.h in front of one launcher of spmm_kernels.h (edge_message.h, aggregate_multi.h, relational.h).
 #include <cmath>
 
 #include "aggregate_multi.h"
 #include "edge_message.h"
 #include "plan_policy.h"
+#include "relational.h"
 
 using namespace gcn;
 
@@ -272,6 +273,69 @@ int gcn_aggregate_multi_backward_csr_f32(const int32_t* trowptr, const int32_t* 
   if (pl.moments() && !pl.has(kMultiMean) && !save_mean) return GCN_ERR_INVALID_ARG;
   return hip_status(launch_aggregate_multi_backward(trowptr, trow, tperm, rowptr, n, m, nnz, g, x, k, pl, out, argmax, argmin,
                                                     save_mean, ab, gx, ws, st));
+}
+
+// Relation-typed aggregation (relational.hip).  k, R, B and the sizes first (B k, the width of out, and R B stay below 2^31);
+// then what an empty problem still needs; 1 = return *status
+static int relation_args(int32_t rows_out, int32_t rows_in, int32_t nnz, int32_t k, int32_t R, int32_t B, int* status) {
+  *status = GCN_ERR_INVALID_ARG;
+  if (rows_out < 0 || rows_in < 0 || nnz < 0 || k < 1 || k > 16 * 65535 || R < 1 || B < 1) return 1;  // (column tiles ride in gridDim.y)
+  if ((long long)B * k >= (1LL << 31) || (long long)R * B >= (1LL << 31)) return 1;
+  *status = GCN_OK;
+  return rows_out == 0;
+}
+
+int gcn_relation_aggregate_ws_bytes(int32_t nnz, int32_t k, int32_t num_bases, size_t* bytes) {
+  int rc;
+  relation_args(0, 0, nnz, k, 1, num_bases, &rc);                              // (the size rules alone)
+  if (rc != GCN_OK || !bytes) return GCN_ERR_INVALID_ARG;
+  *bytes = relation_workspace_bytes(nnz, k, num_bases);
+  return GCN_OK;
+}
+
+int gcn_relation_aggregate_csr_f32(const int32_t* rowptr, const int32_t* col, const int32_t* etype, int32_t m, int32_t n,
+                                   int32_t nnz, const float* x, int32_t k, const float* coeff, int32_t num_relations,
+                                   int32_t num_bases, const float* values, float* out, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (!coeff && num_bases != num_relations) return GCN_ERR_INVALID_ARG;       // (typed mode: a plane per relation)
+  if (relation_args(m, n, nnz, k, num_relations, num_bases, &rc)) return rc;
+  if (!out) return GCN_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (nnz == 0) return hip_status(launch_fill_words(out, (size_t)m * (size_t)num_bases * (size_t)k, 0u, st));
+  if (!rowptr || !col || !etype || !x || !ws || ws_bytes < relation_workspace_bytes(nnz, k, num_bases)) return GCN_ERR_INVALID_ARG;
+  return hip_status(launch_relation_aggregate(rowptr, col, etype, m, nnz, x, k, coeff, num_relations, num_bases, values, out, ws, st));
+}
+
+int gcn_relation_aggregate_backward_x_csr_f32(const int32_t* trowptr, const int32_t* trow, const int32_t* tperm,
+                                              const int32_t* etype, int32_t n, int32_t m, int32_t nnz, const float* g, int32_t k,
+                                              const float* coeff, int32_t num_relations, int32_t num_bases, const float* values,
+                                              float* gx, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (!coeff && num_bases != num_relations) return GCN_ERR_INVALID_ARG;
+  if (relation_args(n, m, nnz, k, num_relations, num_bases, &rc)) return rc;
+  if (!gx) return GCN_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (nnz == 0) return hip_status(launch_fill_words(gx, (size_t)n * (size_t)k, 0u, st));
+  if (!trowptr || !trow || !tperm || !etype || !g || !ws || ws_bytes < relation_workspace_bytes(nnz, k, num_bases))
+    return GCN_ERR_INVALID_ARG;
+  return hip_status(launch_relation_aggregate_backward_x(trowptr, trow, tperm, etype, n, nnz, g, k, coeff, num_relations, num_bases,
+                                                         values, gx, ws, st));
+}
+
+int gcn_relation_aggregate_backward_coeff_f32(const int32_t* relptr, const int32_t* rel_row, const int32_t* rel_col,
+                                              const int32_t* rel_perm, int32_t num_relations, int32_t m, int32_t n, int32_t nnz,
+                                              const float* g, const float* x, int32_t k, int32_t num_bases, const float* values,
+                                              float* gcoeff, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (relation_args(m, n, nnz, k, num_relations, num_bases, &rc) && rc != GCN_OK) return rc;
+  if (!gcoeff) return GCN_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (m == 0 || n == 0 || nnz == 0)                      // (no entry: every relation is empty)
+    return hip_status(launch_fill_words(gcoeff, (size_t)num_relations * (size_t)num_bases, 0u, st));
+  if (!relptr || !rel_row || !rel_col || !rel_perm || !g || !x || !ws || ws_bytes < relation_workspace_bytes(nnz, k, num_bases))
+    return GCN_ERR_INVALID_ARG;
+  return hip_status(launch_relation_aggregate_backward_coeff(relptr, rel_row, rel_col, rel_perm, num_relations, nnz, g, x, k,
+                                                             num_bases, values, gcoeff, ws, st));
 }
 
 static_assert(kEdgeOpAdd == GCN_EDGE_OP_ADD && kEdgeOpMul == GCN_EDGE_OP_MUL && kEdgeActNone == GCN_EDGE_ACT_NONE &&

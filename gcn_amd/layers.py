@@ -27,6 +27,7 @@ from . import preprocess, reorder, timers
 from .aggregate import aggregate, aggregate_multi
 from .edgefeat import edge_aggregate
 from .attention import edge_softmax, gat_edge_softmax, gatv2_scores, spmm_heads
+from .relational import EdgeTypes, relation_aggregate
 from .spgemm import HypergraphLaplacian
 from .spmm import CsrAdjacency, _SpmmFunction, _check_values_version, _values_version, dropout_rows, gather_rows, spmm
 
@@ -516,6 +517,75 @@ class GINEConv(_GINBase):
 
     def __repr__(self):
         return f"GINEConv (nn={self.nn})"
+
+
+class RGCNConv(nn.Module):
+    """Relational graph convolution (Schlichtkrull et al. 2018; PyG's ``RGCNConv``, DGL's ``RelGraphConv``) on the
+    relation-typed aggregation, the neighbour's row gathered once per stored entry:
+
+        y   = relation_aggregate(types, x_src, comp, values)       # [m, B in_dim]: the B basis planes side by side
+        out = y @ weight.view(B * in_dim, out_dim) + x_dst @ root + bias
+
+    ``num_bases=B``: ``weight`` [B, in_dim, out_dim] and ``comp`` [num_relations, B], relation t acting by
+    ``sum_b comp[t, b] weight[b]``.  ``num_bases=None``: ``weight`` [num_relations, in_dim, out_dim], a matrix per relation, on
+    the typed mode of the aggregation (meant for a handful of relations: the planes are num_relations * in_dim wide).
+    ``forward(types, x, values=None)``: ``types`` an ``EdgeTypes``; ``x`` [n, in_dim], or the pair (x_src, x_dst) of a
+    sampled block; ``values`` [nnz] weighs the entries (no gradient flows to it) and defaults to ``types.norm()``, the mean
+    over the neighbours of each relation.  ``weight``, ``root`` and ``bias`` are uniform in +-1/sqrt(out_dim), ``comp`` is
+    Glorot-uniform."""
+
+    def __init__(self, in_dim, out_dim, num_relations, num_bases=None, root_weight=True, bias=True):
+        super().__init__()
+        for name, v in (("num_relations", num_relations), ("num_bases", 1 if num_bases is None else num_bases)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"RGCNConv: {name} must be an int >= 1, not {v!r}")
+        self.in_dim, self.out_dim, self.num_relations, self.num_bases = int(in_dim), int(out_dim), num_relations, num_bases
+        self.weight = Parameter(torch.empty(num_bases or num_relations, self.in_dim, self.out_dim))
+        if num_bases is not None:
+            self.comp = Parameter(torch.empty(num_relations, num_bases))
+        else:
+            self.register_parameter("comp", None)
+        if root_weight:
+            self.root = Parameter(torch.empty(self.in_dim, self.out_dim))
+        else:
+            self.register_parameter("root", None)
+        if bias:
+            self.bias = Parameter(torch.empty(self.out_dim))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        stdv = 1.0 / math.sqrt(self.out_dim)
+        for p in (self.weight, self.root, self.bias):
+            if p is not None:
+                p.data.uniform_(-stdv, stdv)
+        if self.comp is not None:
+            nn.init.xavier_uniform_(self.comp)
+
+    def forward(self, types, x, values=None):
+        if not isinstance(types, EdgeTypes) or types.num_relations != self.num_relations:
+            raise ValueError(f"RGCNConv: types must be an EdgeTypes of {self.num_relations} relations")
+        adj = types.adj
+        if isinstance(x, (tuple, list)):                   # a bipartite block: (x_src [adj.n rows], x_dst [adj.m rows])
+            if len(x) != 2:
+                raise ValueError("RGCNConv: a bipartite input is the pair (x_src, x_dst)")
+            x, root = x
+        else:
+            root = x
+            if self.root is not None and adj.m != adj.n:
+                raise ValueError(f"RGCNConv: adjacency {adj.m}x{adj.n} needs the pair (x_src, x_dst)")
+        if x.dim() != 2 or tuple(x.shape) != (adj.n, self.in_dim) or (self.root is not None and tuple(root.shape) != (adj.m, self.in_dim)):
+            raise ValueError(f"RGCNConv: adjacency {adj.m}x{adj.n}, in_dim {self.in_dim}, input ({tuple(x.shape)}, {tuple(root.shape)})")
+        y = relation_aggregate(types, x.float(), self.comp, types.norm() if values is None else values)
+        out = torch.mm(y, self.weight.view(-1, self.out_dim))
+        if self.root is not None:
+            out = out + torch.mm(root.float(), self.root)
+        return out + self.bias if self.bias is not None else out
+
+    def __repr__(self):
+        return (f"RGCNConv ({self.in_dim} -> {self.out_dim}, relations={self.num_relations}, "
+                f"bases={self.num_bases if self.num_bases is not None else 'none'})")
 
 
 class GraphSAGE(nn.Module):

@@ -362,6 +362,62 @@ int gcn_aggregate_multi_backward_csr_f32(const int32_t* trowptr_dev, const int32
                                          const int32_t* argmax, const int32_t* argmin, const float* save_mean, float* ab,
                                          float* gx, void* ws, size_t ws_bytes, void* stream);
 
+/* Relation-typed aggregation (relational.hip; R-GCN with basis decomposition, PyG's RGCNConv, DGL's RelGraphConv): every
+ * stored entry carries a relation type and ONE gather of the neighbour's row feeds num_bases planes,
+ *   out[r, b k + j] = sum over the entries e of row r of  w(e, b) x[col[e], j],   w(e, b) = coeff[etype[e], b] values[e]
+ * (the layer is out.view(m, B k) @ V.view(B k, out_dim)).  Plan-free like the families above: the caller's CSR, one 4-byte
+ * memset node and kernels per pass (no allocation, no host synchronisation, no host read of device data: legal inside a
+ * stream capture, after one eager call), no atomics, every output element has one writer and every sum a fixed order: the
+ * same bits at every call.  Duplicated (row, column) pairs are separate entries; any row length.  All operands fp32,
+ * row-major; element offsets are 64-bit (m B k may pass 2^31).
+ *   etype int32 [nnz], in entry order.  An entry whose type is outside [0, num_relations) — one unsigned compare, so -1
+ *   is a mask — contributes nothing, forward and backward, and coeff is not read for it.
+ *   coeff [num_relations x num_bases] or NULL.  NULL is the typed mode and needs num_bases == num_relations: plane b takes
+ *   exactly the entries of type b, weighted by values[e], as a predicated fma — a non-finite row of x reached only through
+ *   relation t touches plane t alone.  With coeff, 0 * NaN = NaN reaches every plane, as the dense formula's would.
+ *   values [nnz] or NULL (ones).  There is no gradient in values.
+ *   w = coeff * values is rounded once, then acc = fmaf(w, x, acc): slot s of 64 / LPS adds the entries s, s + SLOTS, ... of
+ *   a run of at most 4096 in ascending order, the slots are merged by an xor butterfly, a long row's runs in order (LPS =
+ *   16, 32 or 64 lanes for k / VEC <= 16, <= 32, more).  num_bases > 8 runs as passes of 8 planes, each gathering x again.
+ * 16-byte accesses (VEC = 4) when x and out (g and gx; g and x) are 16-byte aligned and k % 4 == 0, element accesses
+ * otherwise; 16-byte coefficient loads when coeff is 16-byte aligned and num_bases % 4 == 0; all give the same bits, but
+ * for the coefficient gradient, whose order of adds depends on VEC.
+ * ws: device scratch of at least the bytes gcn_relation_aggregate_ws_bytes reports for (nnz, k, num_bases) — enough for
+ * the three entry points on the pattern, its transpose and its relation-major view — 16-byte aligned, owned by the call
+ * until it has run: a flag and one float per (chunk of 4096 entries, long row, column, plane of a pass).
+ * GCN_ERR_INVALID_ARG, before any device pointer is read: null pointers, negative sizes, k < 1, k > 16 * 65535,
+ * num_relations < 1, num_bases < 1, num_bases * k or num_relations * num_bases >= 2^31, a NULL coeff with num_bases !=
+ * num_relations, a short workspace.  m == 0: GCN_OK, nothing launched; nnz == 0: out is zeroed, by a kernel. */
+int gcn_relation_aggregate_ws_bytes(int32_t nnz, int32_t k, int32_t num_bases, size_t* bytes);
+int gcn_relation_aggregate_csr_f32(const int32_t* rowptr_dev, const int32_t* col_dev, const int32_t* etype_dev, int32_t m,
+                                   int32_t n, int32_t nnz, const float* x, int32_t k, const float* coeff, int32_t num_relations,
+                                   int32_t num_bases, const float* values, float* out, void* ws, size_t ws_bytes, void* stream);
+/* The gradient in x, as a walk of the TRANSPOSED pattern (trowptr_dev [n + 1], trow_dev, tperm_dev as in
+ * gcn_aggregate_backward_csr; etype_dev and values stay in the forward's entry order and are read through tperm): for the
+ * entry t of transposed row c, r = trow[t] and e = tperm[t],
+ *   gx[c, j] = sum_t sum_b w(e, b) g[r, b k + j]
+ * one fma chain per entry over b ascending, straight into the running sum; the typed mode gathers the one plane of the
+ * entry's type.  Entries, slots and runs in the forward's order.  g [m x num_bases k], gx [n x k].  n == 0: nothing
+ * launched; nnz == 0: gx is zeroed. */
+int gcn_relation_aggregate_backward_x_csr_f32(const int32_t* trowptr_dev, const int32_t* trow_dev, const int32_t* tperm_dev,
+                                              const int32_t* etype_dev, int32_t n, int32_t m, int32_t nnz, const float* g,
+                                              int32_t k, const float* coeff, int32_t num_relations, int32_t num_bases,
+                                              const float* values, float* gx, void* ws, size_t ws_bytes, void* stream);
+/* The gradient in coeff, one writer per element of gcoeff [num_relations x num_bases]:
+ *   gcoeff[t, b] = sum over the entries e of type t of  values[e] sum_j x[col[e], j] g[row[e], b k + j]
+ * on the RELATION-MAJOR view of the entries: relptr_dev [num_relations + 1] and, per entry in type-major stable order
+ * (gcn_bucket_fill_i32 on the types, out-of-range types in one bucket behind the last relation, which is not walked), its
+ * row (rel_row_dev), its column (rel_col_dev) and its index in the CSR (rel_perm_dev; values is read through it).  A
+ * relation is a row of the walk: one of more than 4096 entries is spread over the chip.  Per (entry, tile of LPS VEC
+ * columns) t = values * x is rounded once and s[b][v] = fmaf(t, g, s[b][v]); slot s takes the entries s, s + SLOTS, ... of a
+ * run ascending, an entry's tiles ascending; at a run's end a lane adds its VEC sums left to right, the 64 lanes are merged by
+ * an xor butterfly 1 .. 32, runs in order.  An empty relation gets 0.  num_bases > 8 runs as passes of 8 planes.  m, n as
+ * in the forward (sizes only).  m == 0, n == 0 or nnz == 0: gcoeff is zeroed. */
+int gcn_relation_aggregate_backward_coeff_f32(const int32_t* relptr_dev, const int32_t* rel_row_dev, const int32_t* rel_col_dev,
+                                              const int32_t* rel_perm_dev, int32_t num_relations, int32_t m, int32_t n,
+                                              int32_t nnz, const float* g, const float* x, int32_t k, int32_t num_bases,
+                                              const float* values, float* gcoeff, void* ws, size_t ws_bytes, void* stream);
+
 /* Edge-feature message passing (edge_message.hip; DGL's u_op_e -> reduce: GINE, MPNN, CGConv): a feature VECTOR per stored
  * entry beside the gathered node row.  Plan-free like the aggregation family above: the caller's CSR, one memset node and
  * kernels (no allocation, no host synchronisation, no host read of device data: legal inside a stream capture), no
