@@ -10,7 +10,7 @@ Drop-in shared objects for gcn6.py live in gcn_amd/dropin/ (see INTEGRATION.md).
 from ._lib import GcnAmdError, LIB_PATH, DROPIN_DIR, load as load_library  # noqa: F401
 from .spmm import CsrAdjacency, spmm, gather_rows, dropout_rows, install, uninstall  # noqa: F401
 from .attention import edge_softmax, gat_edge_softmax, gatv2_scores, sddmm_heads, segment_sum, spmm_heads  # noqa: F401
-from .aggregate import aggregate, aggregate_multi  # noqa: F401
+from .aggregate import aggregate, aggregate_multi, aggregate_quantile  # noqa: F401
 from .edgefeat import edge_aggregate  # noqa: F401
 from .relational import EdgeTypes, relation_aggregate  # noqa: F401
 from .sampling import Block, NeighborLoader, sample_blocks, sample_neighbors  # noqa: F401
@@ -21,6 +21,6 @@ from .linkpred import LinkNeighborLoader, edge_subgraph, find_edges, negative_sa
 from .spgemm import HypergraphLaplacian, SparseProduct, hypergraph_laplacian, sampled_dot, spgemm  # noqa: F401
 from .knn import KNN_K_MAX, knn, knn_graph, knn_hypergraph  # noqa: F401
 from . import reorder, dropin  # noqa: F401
-from .layers import GCN, GINConv, GINEConv, HGNN, GraphAttention, GraphAttentionV2, GraphConvolution, GraphConvolution2, GraphSAGE, HGNNConv, PNAConv, RGCNConv, SAGEConv  # noqa: F401
+from .layers import GCN, GINConv, GINEConv, HGNN, GraphAttention, GraphAttentionV2, GraphConvolution, GraphConvolution2, GraphSAGE, HGNNConv, MedianConv, PNAConv, RGCNConv, SAGEConv  # noqa: F401
 
 __version__ = "0.4.0"

@@ -161,6 +161,8 @@ SIGNATURES = {
     "gcn_aggregate_multi_backward_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i32,
                                                             _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t,
                                                             _c_p]),
+    "gcn_aggregate_quantile_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_p, _c_p,
+                                                      ctypes.c_size_t, _c_p]),
     "gcn_relation_aggregate_ws_bytes": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, ctypes.POINTER(ctypes.c_size_t)]),
     "gcn_relation_aggregate_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_i32,
                                                       _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),

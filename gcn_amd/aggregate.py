@@ -5,6 +5,7 @@ GraphSAGE's aggregators (PyG ``SAGEConv(aggr=...)``, DGL ``copy_u_max``).
     h, arg = gcn_amd.aggregate(adj, x, "min", return_arg=True)  # arg[r, j]: the CSR entry index that supplied h[r, j]
     h = gcn_amd.aggregate(adj, x, "mean")                     # the SpMM on a pattern-valued twin of adj
     h = gcn_amd.aggregate_multi(adj, x, ("mean", "max", "min", "std"))   # [m, 4 k]: four statistics from one gather per entry
+    h = gcn_amd.aggregate_quantile(adj, x, 0.5)               # the lower median of every neighbourhood (Median-GCN)
 
 Only the pattern of ``adj`` is used: its values are ignored, and every stored entry counts, duplicated (row, column)
 pairs included.  max / min run on gcn_amd/csrc/aggregate.hip (fp32 or bf16, exact: a selection rounds nothing); an empty
@@ -202,3 +203,79 @@ def aggregate_multi(adj, x, reduce=("mean", "max", "min", "std"), eps=1e-5, retu
         raise _lib.GcnAmdError("aggregate_multi: x must be fp32")
     out, argmax, argmin = _MultiFunction.apply(adj, x, reduce, eps)
     return (out, argmax, argmin) if return_arg else out
+
+
+class _QuantileFunction(torch.autograd.Function):
+    """(out, arg) = the order statistics of every row, plane by plane, and the entries that supplied them; the gradient of
+    each plane goes to x[col[arg]] by the max / min backward walk, and the planes' gradients are summed"""
+
+    @staticmethod
+    def forward(ctx, adj, x, q):
+        x = x.detach().contiguous()
+        k, nq = int(x.shape[1]), len(q)
+        out = torch.empty((adj.m, nq * k), dtype=torch.float32, device=x.device)
+        arg = torch.empty((adj.m, nq * k), dtype=torch.int32, device=x.device)
+        ws = adj._scratch.get("aggregate_quantile", 16, x.device) if adj.nnz else None   # GCN_AGGREGATE_QUANTILE_WS_BYTES
+        call("gcn_aggregate_quantile_csr_f32", adj.rowptr, adj.col, adj.m, adj.n, adj.nnz, x, k, (ctypes.c_double * nq)(*q), nq,
+             out, arg, ws, ws.numel() if ws is not None else 0, device=x.device)
+        ctx.adj, ctx.nq = adj, nq
+        ctx.save_for_backward(arg)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_arg):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None
+        (arg,) = ctx.saved_tensors
+        adj, nq = ctx.adj, ctx.nq
+        k = int(g.shape[1]) // nq
+        trowptr, trow, tperm = adj.tpattern()
+        ws = _scratch(adj, k, g.device)
+        total = None
+        for i in range(nq):                              # one walk of the transposed pattern per plane
+            gi, ai = g[:, i * k:(i + 1) * k].contiguous(), arg[:, i * k:(i + 1) * k].contiguous()
+            gx = torch.empty((adj.n, k), dtype=torch.float32, device=g.device)
+            call("gcn_aggregate_backward_csr", trowptr, trow, tperm, adj.n, adj.m, adj.nnz, gi, _lib.DTYPE_F32, ai, k, gx,
+                 ws, ws.numel() if ws is not None else 0, device=g.device)
+            total = gx if total is None else total.add_(gx)
+        return None, total, None
+
+
+def _quantiles(q, what):
+    """q as a tuple of 1 to 4 floats in [0, 1]; ValueError otherwise"""
+    try:
+        qs = (float(q),) if isinstance(q, (int, float)) and not isinstance(q, bool) else tuple(float(v) for v in q)
+    except (TypeError, ValueError):
+        qs = ()
+    if not 1 <= len(qs) <= 4 or not all(0.0 <= v <= 1.0 for v in qs):
+        raise ValueError(f"{what}: q must be a float or a tuple of 1 to 4 floats in [0, 1], not {q!r}")
+    return qs
+
+
+def aggregate_quantile(adj, x, q=0.5, return_arg=False):
+    """Order statistics of every row's neighbourhood (PyG's ``QuantileAggregation(interpolation="lower")``; q = 0.5 is
+    ``MedianAggregation`` / ``torch.median``'s lower median, the reduction of Median-GCN): for each quantile q[i],
+    out[r, i k + j] = the element of rank floor(q[i] (d - 1)) of x[c, j] over the d stored entries (r, c) of row r of ``adj``
+    (any CsrAdjacency: pattern only, duplicates are separate entries), on gcn_amd/csrc/aggregate_quantile.hip.
+
+    x: [n, k] fp32 device tensor, differentiable.  q: a float or a tuple of 1 to 4 floats in [0, 1]; the result is
+    [m, len(q) k] fp32, the planes side by side as in ``aggregate_multi``.  Entries are ordered by (value, entry index),
+    -0.0 equal to +0.0, +-inf ordinary values; a column that holds a NaN gives the first NaN entry in every plane; an empty
+    row gives zeros.  Exact: a selection rounds nothing.  The gradient of each plane goes to the selected entry only (the
+    max / min backward walk, once per plane).  ``return_arg=True`` also returns the int32 [m, len(q) k] CSR entry indices
+    that supplied the values (-1 for an empty row), not differentiable.
+    TypeError for a non-CsrAdjacency, ValueError for a bad q or a wrong shape, GcnAmdError for a CPU tensor or a dtype other
+    than fp32."""
+    if not isinstance(adj, CsrAdjacency):
+        raise TypeError("aggregate_quantile: adj must be a CsrAdjacency")
+    qs = _quantiles(q, "aggregate_quantile")
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != adj.n or x.shape[1] < 1:
+        raise ValueError(f"aggregate_quantile: x must be a 2-D tensor of n = {adj.n} rows and at least one column")
+    if not x.is_cuda:
+        raise _lib.GcnAmdError("aggregate_quantile: x must be a CUDA/HIP tensor (no CPU path in gcn_amd)")
+    if x.dtype != torch.float32:
+        raise _lib.GcnAmdError("aggregate_quantile: x must be fp32")
+    out, arg = _QuantileFunction.apply(adj, x, qs)
+    return (out, arg) if return_arg else out

@@ -1,9 +1,10 @@
 // api_units.cpp — the native C ABI of libgcnspmm.so: the plan-free units (edge softmax, head-batched attention, GATv2 scores,
-// max / min aggregation, multi-aggregation, relation-typed aggregation, edge-feature aggregation, sampling, subgraphs and walks, entry lookup, bucketing, coalescing, SpGEMM, sampled dot, kNN, row
-// gather).  Each entry point is the argument checks of include/gcn_spmm.h in front of one launcher of spmm_kernels.h (edge_message.h, aggregate_multi.h, relational.h).
+// max / min aggregation, multi-aggregation, quantile aggregation, relation-typed aggregation, edge-feature aggregation, sampling, subgraphs and walks, entry lookup, bucketing, coalescing, SpGEMM, sampled dot, kNN, row
+// gather).  Each entry point is the argument checks of include/gcn_spmm.h in front of one launcher of spmm_kernels.h (edge_message.h, aggregate_multi.h, aggregate_quantile.h, relational.h).
 #include <cmath>
 
 #include "aggregate_multi.h"
+#include "aggregate_quantile.h"
 #include "edge_message.h"
 #include "plan_policy.h"
 #include "relational.h"
@@ -273,6 +274,28 @@ int gcn_aggregate_multi_backward_csr_f32(const int32_t* trowptr, const int32_t* 
   if (pl.moments() && !pl.has(kMultiMean) && !save_mean) return GCN_ERR_INVALID_ARG;
   return hip_status(launch_aggregate_multi_backward(trowptr, trow, tperm, rowptr, n, m, nnz, g, x, k, pl, out, argmax, argmin,
                                                     save_mean, ab, gx, ws, st));
+}
+
+// Quantile aggregation (aggregate_quantile.hip).  The quantiles, a short HOST array, first; then aggregate_args' order.
+static_assert(kQuantileWsBytes == GCN_AGGREGATE_QUANTILE_WS_BYTES && kQuantileMax == GCN_QUANTILE_MAX, "include/gcn_spmm.h");
+
+int gcn_aggregate_quantile_csr_f32(const int32_t* rowptr, const int32_t* col, int32_t m, int32_t n, int32_t nnz, const float* x,
+                                   int32_t k, const double* q, int32_t nq, float* out, int32_t* arg, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  int rc;
+  if (nq < 1 || nq > kQuantileMax || !q) return GCN_ERR_INVALID_ARG;
+  for (int i = 0; i < nq; ++i)
+    if (!(q[i] >= 0.0 && q[i] <= 1.0)) return GCN_ERR_INVALID_ARG;            // (a NaN fails both)
+  if (aggregate_args(m, n, nnz, GCN_DTYPE_F32, k, &rc)) return rc;
+  if (!out || !arg) return GCN_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t elems = (size_t)m * (size_t)nq * (size_t)k;
+  if (nnz == 0) {                                       // every row is empty: zeros and -1, by kernels
+    if (hipError_t e = launch_fill_words(out, elems, 0u, st); e != hipSuccess) return hip_status(e);
+    return hip_status(launch_fill_words(arg, elems, 0xffffffffu, st));
+  }
+  if (!rowptr || !col || !x || !ws || ws_bytes < kQuantileWsBytes) return GCN_ERR_INVALID_ARG;
+  return hip_status(launch_aggregate_quantile(rowptr, col, m, nnz, x, k, q, nq, out, arg, ws, st));
 }
 
 // Relation-typed aggregation (relational.hip).  k, R, B and the sizes first (B k, the width of out, and R B stay below 2^31);

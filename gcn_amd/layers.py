@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from torch.nn.parameter import Parameter
 
 from . import preprocess, reorder, timers
-from .aggregate import aggregate, aggregate_multi
+from .aggregate import aggregate, aggregate_multi, aggregate_quantile
 from .edgefeat import edge_aggregate
 from .attention import edge_softmax, gat_edge_softmax, gatv2_scores, spmm_heads
 from .relational import EdgeTypes, relation_aggregate
@@ -344,6 +344,62 @@ class SAGEConv(nn.Module):
 
     def __repr__(self):
         return (f"SAGEConv ({self.in_features} -> {self.out_features}, aggr={self.aggr}"
+                f"{'' if self.weight_root is not None else ', no root weight'})")
+
+
+class MedianConv(nn.Module):
+    """Median-GCN layer (Chen et al. 2021; DeepRobust's ``MedianGCN``) on the native quantile aggregation:
+
+        out = aggregate_quantile(adj, x · weight, q)  (+ x_dst · weight_root)  (+ bias)
+
+    The linear map comes first: an order statistic does not commute with it.  ``q``: one quantile in [0, 1], 0.5 the lower
+    median (see ``gcn_amd.aggregate_quantile``).  Pattern only: the values of ``adj`` are ignored, and the caller's
+    adjacency carries the self-loops.  ``root_weight=True`` adds the vertex's own features through a second matrix and
+    needs a square adjacency, or the bipartite form ``forward((x_src, x_dst), adj)`` of a sampled block as in ``SAGEConv``.
+
+    Parameters: ``weight`` and ``weight_root`` [in_features, out_features] and ``bias`` [out_features], uniform in
+    +-1/sqrt(out_features) like the GCN layers.  The aggregation runs in fp32."""
+
+    def __init__(self, in_features, out_features, q=0.5, root_weight=False, with_bias=True):
+        super().__init__()
+        if isinstance(q, bool) or not isinstance(q, (int, float)) or not 0.0 <= float(q) <= 1.0:
+            raise ValueError(f"q must be one float in [0, 1], not {q!r}")
+        self.in_features, self.out_features, self.q = int(in_features), int(out_features), float(q)
+        self.weight = Parameter(torch.empty(self.in_features, self.out_features))
+        if root_weight:
+            self.weight_root = Parameter(torch.empty(self.in_features, self.out_features))
+        else:
+            self.register_parameter("weight_root", None)
+        if with_bias:
+            self.bias = Parameter(torch.empty(self.out_features))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        stdv = 1.0 / math.sqrt(self.out_features)
+        for p in (self.weight, self.weight_root, self.bias):
+            if p is not None:
+                p.data.uniform_(-stdv, stdv)
+
+    def forward(self, input, adj):
+        if isinstance(input, (tuple, list)):               # a bipartite block: (x_src [adj.n rows], x_dst [adj.m rows])
+            if len(input) != 2:
+                raise ValueError("MedianConv: a bipartite input is the pair (x_src, x_dst)")
+            input, root = input
+            if input.dim() != 2 or input.shape[0] != adj.n or root.dim() != 2 or root.shape[0] != adj.m:
+                raise ValueError(f"MedianConv: adjacency {adj.m}x{adj.n}, input ({tuple(input.shape)}, {tuple(root.shape)})")
+        else:
+            if input.dim() != 2 or input.shape[0] != adj.n or (self.weight_root is not None and adj.m != adj.n):
+                raise ValueError(f"MedianConv: adjacency {adj.m}x{adj.n} (square with root_weight), input {tuple(input.shape)}")
+            root = input
+        out = aggregate_quantile(adj, torch.mm(input, self.weight).float(), self.q)
+        if self.weight_root is not None:
+            out = out + torch.mm(root, self.weight_root)
+        return out + self.bias if self.bias is not None else out
+
+    def __repr__(self):
+        return (f"MedianConv ({self.in_features} -> {self.out_features}, q={self.q}"
                 f"{'' if self.weight_root is not None else ', no root weight'})")
 
 

@@ -362,6 +362,35 @@ int gcn_aggregate_multi_backward_csr_f32(const int32_t* trowptr_dev, const int32
                                          const int32_t* argmax, const int32_t* argmin, const float* save_mean, float* ab,
                                          float* gx, void* ws, size_t ws_bytes, void* stream);
 
+/* Quantile / median aggregation (aggregate_quantile.hip; Median-GCN, PyG's MedianAggregation and QuantileAggregation with
+ * interpolation="lower"): up to GCN_QUANTILE_MAX order statistics of every row's neighbourhood and the entries that
+ * supplied them.  Plan-free like the families above: the caller's CSR, kernels only (no memset node, no allocation, no
+ * host synchronisation, no host read of device data: legal inside a stream capture, after one eager call), no atomics,
+ * one writer per output element: the same bits at every call.  The stored VALUES of the matrix are not used; every stored
+ * entry is a candidate of its own, duplicated (row, column) pairs included.  Any row length from 0 to nnz: a row of at
+ * most 32 entries is sorted in registers, one of at most 2048 gets a wave's radix select, a longer one a workgroup's.
+ *   q: a HOST array of nq doubles (1 <= nq <= 4), each finite and in [0, 1]; read during the call, travels in the kernel
+ *   argument.  x [n x k]; out [m x nq k] fp32 and arg [m x nq k] int32, plane i at columns i k .. i k + k - 1.
+ * For a row r of d entries, a column j and a quantile i:
+ *   order   the entries ascending by (value, entry index), -0.0 equal to +0.0, +-inf ordinary values;
+ *   rank    t = (int)floor(q[i] * (double)(d - 1)), one multiply in double precision (q = 0.5: torch.median's lower median;
+ *           q = 0: the min and q = 1: the max of gcn_aggregate_csr, except that among equal maxima the LAST entry has rank d - 1);
+ *   output  out[r, i k + j] = the bits of the element of rank t, arg[r, i k + j] = its index into col_dev;
+ *   NaN     a column that holds a NaN gets the first NaN entry's bits and index in every plane (gcn_aggregate_csr's rule);
+ *   empty   out = 0, arg = -1.
+ * Nothing is rounded: the result is a selection, and gcn_aggregate_backward_csr on a plane's [m x k] slices of g and arg is
+ * its gradient.  Element accesses throughout: any alignment of x, out and arg, any k >= 1.
+ * ws: device scratch of at least GCN_AGGREGATE_QUANTILE_WS_BYTES bytes (two flag words; it does not grow with the
+ * problem), 4-byte aligned, owned by the call until it has run.
+ * GCN_ERR_INVALID_ARG, before any device pointer is read: nq outside 1 .. 4, a null q, a q[i] outside [0, 1] or NaN,
+ * negative sizes, k < 1, k > 16 * 65535, null pointers, a short workspace.  m == 0: GCN_OK, nothing launched; nnz == 0: out
+ * is zeroed and arg set to -1, by kernels. */
+#define GCN_AGGREGATE_QUANTILE_WS_BYTES 16
+#define GCN_QUANTILE_MAX 4
+int gcn_aggregate_quantile_csr_f32(const int32_t* rowptr_dev, const int32_t* col_dev, int32_t m, int32_t n, int32_t nnz,
+                                   const float* x, int32_t k, const double* q, int32_t nq, float* out, int32_t* arg, void* ws,
+                                   size_t ws_bytes, void* stream);
+
 /* Relation-typed aggregation (relational.hip; R-GCN with basis decomposition, PyG's RGCNConv, DGL's RelGraphConv): every
  * stored entry carries a relation type and ONE gather of the neighbour's row feeds num_bases planes,
  *   out[r, b k + j] = sum over the entries e of row r of  w(e, b) x[col[e], j],   w(e, b) = coeff[etype[e], b] values[e]
