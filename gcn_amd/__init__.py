@@ -12,7 +12,8 @@ from .spmm import CsrAdjacency, spmm, gather_rows, dropout_rows, install, uninst
 from .attention import edge_softmax, gat_edge_softmax, gatv2_scores, sddmm_heads, segment_sum, spmm_heads  # noqa: F401
 from .aggregate import aggregate, aggregate_multi, aggregate_quantile  # noqa: F401
 from .edgefeat import edge_aggregate  # noqa: F401
-from .relational import EdgeTypes, relation_aggregate  # noqa: F401
+from .relational import EdgeTypes, relation_aggregate, relation_transform_aggregate  # noqa: F401
+from .segment_mm import RowGather, TypedLinear, segment_matmul  # noqa: F401
 from .sampling import Block, NeighborLoader, sample_blocks, sample_neighbors  # noqa: F401
 from .subgraph import ClusterLoader, RandomWalkLoader, Subgraph, induced_subgraph, random_walk  # noqa: F401
 from .construct import bucket_by_key, csr_from_edges, transpose_csr  # noqa: F401

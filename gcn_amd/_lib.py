@@ -39,7 +39,9 @@ SPGEMM_WAVE_MAX = 512        # GCN_SPGEMM_WAVE_MAX: rows of at most this many po
 SPGEMM_BLOCK_MAX = 8192      # GCN_SPGEMM_BLOCK_MAX: ... by a workgroup with a table in LDS; above, a dense accumulator
 SPGEMM_DENSE_BLOCKS = 16     # GCN_SPGEMM_DENSE_BLOCKS: the workgroups (and accumulators in the workspace) of the dense rows
 SAMPLED_DOT_WS_BYTES = 16    # GCN_SAMPLED_DOT_WS_BYTES (gcn_csr_sampled_dot_f32)
-KNN_K_MAX = 64               # GCN_KNN_K_MAX: the most neighbours gcn_knn_f32 returns per query
+SEGMENT_MM_TILE = 64         # rows and columns of a tile of gcn_segment_mm_f32 (kSegTM, kSegTN in csrc/segment_mm.h)
+SEGMENT_MM_CHUNK = 512       # GCN_SEGMENT_MM_CHUNK: rows of one partial of gcn_segment_mm_wgrad_f32
+KNN_K_MAX = 64             # GCN_KNN_K_MAX: the most neighbours gcn_knn_f32 returns per query
 KNN_TILE_Q = 64              # GCN_KNN_TILE_Q: queries of a workgroup
 KNN_TILE_C = 64              # GCN_KNN_TILE_C: candidates of a tile; the candidate range is split in whole tiles
 
@@ -170,6 +172,11 @@ SIGNATURES = {
                                                                  _c_i32, _c_i32, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_relation_aggregate_backward_coeff_f32": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p,
                                                                  _c_i32, _c_i32, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_segment_mm_ws_bytes": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i32, ctypes.POINTER(ctypes.c_size_t)]),
+    "gcn_segment_mm_f32": (ctypes.c_int, [_c_p, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p,
+                                          ctypes.c_size_t, _c_p]),
+    "gcn_segment_mm_wgrad_f32": (ctypes.c_int, [_c_p, _c_i32, _c_p, _c_p, _c_i32, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32,
+                                                _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_edge_aggregate_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_i32,
                                                   _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
     "gcn_edge_aggregate_backward_x_csr_f32": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i32,

@@ -21,12 +21,12 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 ARCH = "gfx950"
 DROPIN_NAMES = ["flexspmm.so", "cuspmm.so", "tile.so", "permutate.so", "renumber.so"]
 
-SOURCES = ["spmm_kernels.hip", "spmm_narrow.hip", "spmm_quad.hip", "spmm_group.hip", "spmm_group_bf16.hip", "spmm_panel.hip", "sddmm.hip", "edge_softmax.hip", "aggregate.hip", "aggregate_multi.hip", "aggregate_quantile.hip", "relational.hip", "multihead.hip", "edge_message.hip", "sample.hip", "subgraph.hip", "lookup.hip", "construct.hip", "coalesce.hip", "spgemm.hip", "knn.hip", "slicing.hip", "reorder_device.hip", "rabbit_device.hip", "exchange.hip", "plan_policy.cpp", "plan_build.cpp", "api_spmm.cpp", "api_units.cpp", "api_reorder.cpp", "api_dropin.cpp", "reorder.cpp", "sampled_dot.hip"]
+SOURCES = ["spmm_kernels.hip", "spmm_narrow.hip", "spmm_quad.hip", "spmm_group.hip", "spmm_group_bf16.hip", "spmm_panel.hip", "sddmm.hip", "edge_softmax.hip", "aggregate.hip", "aggregate_multi.hip", "aggregate_quantile.hip", "relational.hip", "segment_mm.hip", "multihead.hip", "edge_message.hip", "sample.hip", "subgraph.hip", "lookup.hip", "construct.hip", "coalesce.hip", "spgemm.hip", "knn.hip", "slicing.hip", "reorder_device.hip", "rabbit_device.hip", "exchange.hip", "plan_policy.cpp", "plan_build.cpp", "api_spmm.cpp", "api_units.cpp", "api_reorder.cpp", "api_dropin.cpp", "reorder.cpp", "sampled_dot.hip"]
 # per-unit compiler flags: the sums of aggregate_multi.hip and relational.hip are specified operation by operation
 # (include/gcn_spmm.h), so the packed two-lane fp32 instructions are kept out of them
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"aggregate_multi.hip": _NO_PACKED_FP32, "aggregate_quantile.hip": _NO_PACKED_FP32, "relational.hip": _NO_PACKED_FP32}
-HEADERS = ["spmm_kernels.h", "chunk_walk.h", "group_walk.h", "row_dispatch.h", "long_chunks.h", "gather_rows.h", "select_rule.h", "edge_message.h", "aggregate_multi.h", "aggregate_quantile.h", "relational.h", "plan.h", "plan_policy.h", "philox.h", "reorder.h", os.path.join(INCLUDE, "gcn_spmm.h")]
+HEADERS = ["spmm_kernels.h", "chunk_walk.h", "group_walk.h", "row_dispatch.h", "long_chunks.h", "gather_rows.h", "select_rule.h", "edge_message.h", "aggregate_multi.h", "aggregate_quantile.h", "relational.h", "segment_mm.h", "plan.h", "plan_policy.h", "philox.h", "reorder.h", os.path.join(INCLUDE, "gcn_spmm.h")]
 
 
 def _hipcc():

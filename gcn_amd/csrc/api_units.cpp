@@ -1,6 +1,6 @@
 // api_units.cpp — the native C ABI of libgcnspmm.so: the plan-free units (edge softmax, head-batched attention, GATv2 scores,
 // max / min aggregation, multi-aggregation, quantile aggregation, relation-typed aggregation, edge-feature aggregation, sampling, subgraphs and walks, entry lookup, bucketing, coalescing, SpGEMM, sampled dot, kNN, row
-// gather).  Each entry point is the argument checks of include/gcn_spmm.h in front of one launcher of spmm_kernels.h (edge_message.h, aggregate_multi.h, aggregate_quantile.h, relational.h).
+// gather).  Each entry point is the argument checks of include/gcn_spmm.h in front of one launcher of spmm_kernels.h (edge_message.h, aggregate_multi.h, aggregate_quantile.h, relational.h, segment_mm.h).
 #include <cmath>
 
 #include "aggregate_multi.h"
@@ -8,6 +8,7 @@
 #include "edge_message.h"
 #include "plan_policy.h"
 #include "relational.h"
+#include "segment_mm.h"
 
 using namespace gcn;
 
@@ -359,6 +360,46 @@ int gcn_relation_aggregate_backward_coeff_f32(const int32_t* relptr, const int32
     return GCN_ERR_INVALID_ARG;
   return hip_status(launch_relation_aggregate_backward_coeff(relptr, rel_row, rel_col, rel_perm, num_relations, nnz, g, x, k,
                                                              num_bases, values, gcoeff, ws, st));
+}
+
+// Grouped matrix product (segment_mm.hip).  The sizes first; 1 = return *status
+static_assert(kSegChunk == GCN_SEGMENT_MM_CHUNK, "include/gcn_spmm.h");
+
+static int segment_mm_args(int32_t N, int32_t T, int32_t K, int32_t O, int* status) {
+  *status = GCN_ERR_INVALID_ARG;
+  if (N < 0 || T < 0 || K < 1 || O < 1 || (long long)K * O >= (1LL << 31)) return 1;
+  if ((K + kSegTN - 1) / kSegTN > 65535 || (O + kSegTN - 1) / kSegTN > 65535) return 1;      // (tiles ride in gridDim.y / .z)
+  if ((long long)N / kSegTM + T + 3 >= (1LL << 31)) return 1;
+  *status = GCN_OK;
+  return 0;
+}
+
+int gcn_segment_mm_ws_bytes(int32_t N, int32_t T, int32_t K, int32_t O, size_t* bytes) {
+  int rc;
+  if (segment_mm_args(N, T, K, O, &rc) || !bytes) return GCN_ERR_INVALID_ARG;
+  *bytes = segment_mm_workspace_bytes(N, T, K, O);
+  return GCN_OK;
+}
+
+int gcn_segment_mm_f32(const float* x, int32_t x_rows, const int32_t* x_index, const float* scale, const int32_t* segptr,
+                       const float* W, int32_t transpose_w, int32_t N, int32_t T, int32_t K, int32_t O, float* y, void* ws,
+                       size_t ws_bytes, void* stream) {
+  int rc;
+  if (segment_mm_args(N, T, K, O, &rc) || x_rows < 0) return GCN_ERR_INVALID_ARG;
+  if (N == 0) return GCN_OK;
+  if (!x || !segptr || (!W && T > 0) || !y || !ws || ws_bytes < segment_mm_workspace_bytes(N, T, K, O)) return GCN_ERR_INVALID_ARG;
+  return hip_status(launch_segment_mm(x, x_rows, x_index, scale, segptr, W, transpose_w != 0, N, T, K, O, y, ws, (hipStream_t)stream));
+}
+
+int gcn_segment_mm_wgrad_f32(const float* x, int32_t x_rows, const int32_t* x_index, const float* g, int32_t g_rows,
+                             const int32_t* g_index, const float* scale, const int32_t* segptr, int32_t N, int32_t T, int32_t K,
+                             int32_t O, float* dW, void* ws, size_t ws_bytes, void* stream) {
+  int rc;
+  if (segment_mm_args(N, T, K, O, &rc) || x_rows < 0 || g_rows < 0) return GCN_ERR_INVALID_ARG;
+  if (T == 0) return GCN_OK;
+  if (!dW || !segptr || !ws || ws_bytes < segment_mm_workspace_bytes(N, T, K, O) || (N > 0 && (!x || !g))) return GCN_ERR_INVALID_ARG;
+  return hip_status(launch_segment_mm_wgrad(x, x_rows, x_index, g, g_rows, g_index, scale, segptr, N, T, K, O, dW, ws,
+                                            (hipStream_t)stream));
 }
 
 static_assert(kEdgeOpAdd == GCN_EDGE_OP_ADD && kEdgeOpMul == GCN_EDGE_OP_MUL && kEdgeActNone == GCN_EDGE_ACT_NONE &&

@@ -14,7 +14,9 @@ import torch
 
 from . import _lib
 from ._lib import call
+from .attention import _segment_sum_raw
 from .construct import bucket_by_key
+from .segment_mm import _check_fp32, _forward_raw, _wgrad_raw
 from .spmm import CsrAdjacency
 
 _CHUNK = 4096                # entries per workspace partial: gcn_relation_aggregate_ws_bytes in include/gcn_spmm.h
@@ -43,7 +45,7 @@ class EdgeTypes:
             etype = torch.where((etype >= 0) & (etype < R), etype, torch.full_like(etype, -1))
         self.adj, self.num_relations = adj, R
         self.etype = etype.to(device=adj.device, dtype=torch.int32).contiguous()
-        self._view = self._norm = None
+        self._view = self._norm = self._grouped = None
 
     def _keys(self):
         """the type of every entry, out-of-range types as num_relations (int64)"""
@@ -63,6 +65,17 @@ class EdgeTypes:
             at = perm.long()
             self._view = (relptr, self._rows().index_select(0, at).to(torch.int32), self.adj.col.index_select(0, at).contiguous(), perm)
         return self._view
+
+    def grouped_positions(self):
+        """(perm int64 [nnz], inverse int32 [nnz], tpos int32 [nnz]) for ``relation_transform_aggregate``: the view's perm
+        as an index, the position in the view of every entry of ``adj`` (its inverse), and the position in the view of
+        every entry of the transposed pattern (``adj.tpattern()``).  Built once, with the view, and kept."""
+        if self._grouped is None:
+            perm = self.relation_view()[3].long()
+            inverse = torch.empty(self.adj.nnz, dtype=torch.int32, device=self.adj.device)
+            inverse[perm] = torch.arange(self.adj.nnz, dtype=torch.int32, device=self.adj.device)
+            self._grouped = (perm, inverse, inverse.index_select(0, self.adj.tpattern()[2].long()).contiguous())
+        return self._grouped
 
     def norm(self):
         """fp32 [nnz]: 1 / the number of entries with the same (row, type), R-GCN's 1 / c_{i,r} (PyG's aggr="mean");
@@ -156,3 +169,67 @@ def relation_aggregate(types, x, coeff=None, values=None):
     if planes * int(x.shape[1]) >= 2 ** 31:
         raise ValueError("relation_aggregate: the output's width B * k must stay below 2^31")
     return _RelationFunction.apply(types, x, coeff, values)
+
+
+class _RelationTransformFunction(torch.autograd.Function):
+    """out [m, O]; one gathered segment GEMM over the relation-major view and the row sums back, forward and backward"""
+
+    @staticmethod
+    def forward(ctx, types, x, weight, values):
+        adj = types.adj
+        x, weight = x.detach().contiguous(), weight.detach().contiguous()
+        relptr, _rrow, rcol, _rperm = types.relation_view()
+        perm, inverse, _tpos = types.grouped_positions()
+        scale = values.detach().index_select(0, perm) if values is not None else None      # values in the view's order
+        msg = _forward_raw(adj._scratch, x, rcol, scale, relptr, weight, False, adj.nnz)     # [nnz, O]; the masked bucket zeros
+        out = torch.empty((adj.m, weight.shape[2]), dtype=torch.float32, device=x.device)
+        ctx.types = types
+        ctx.save_for_backward(x, weight, scale)
+        return _segment_sum_raw(adj, adj.rowptr, adj.m, msg, inverse, out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, weight, scale = ctx.saved_tensors
+        types = ctx.types
+        adj = types.adj
+        g = g.contiguous()
+        relptr, rrow, rcol, _rperm = types.relation_view()
+        gx = gw = None
+        if ctx.needs_input_grad[1]:
+            gz = _forward_raw(adj._scratch, g, rrow, scale, relptr, weight, True, adj.nnz)   # [nnz, K]
+            gx = torch.empty((adj.n, x.shape[1]), dtype=torch.float32, device=g.device)
+            _segment_sum_raw(adj, adj.tpattern()[0], adj.n, gz, types.grouped_positions()[2], gx)
+        if ctx.needs_input_grad[2]:
+            gw = _wgrad_raw(adj._scratch, x, rcol, g, rrow, scale, relptr, types.num_relations, adj.nnz)
+        return None, gx, gw, None
+
+
+def relation_transform_aggregate(types, x, weight, values=None):
+    """out[r] = sum over the stored entries e of row r of ``values[e] * x[col[e]] @ weight[etype[e]]``: [m, O], a matrix per
+    relation WITHOUT the [m, R k] planes of the typed mode, so the number of relations may be in the hundreds.
+
+    Forward: one gathered segment GEMM (``segment_mm.hip``) over ``types.relation_view()`` — the entries in type-major
+    order, x gathered by their columns, scaled by their values — then atomic-free row sums (``segment_sum``) back into the
+    rows.  Gradient in x: the same kernel on the transposed weights with the rows of g gathered, then the row sums over
+    ``adj.tpattern()``; in weight: the weight-gradient kernel with both operands gathered.  The only nnz-sized intermediates
+    are [nnz, O] forward and [nnz, K] backward (DGL's low-memory path); nnz * max(K, O) must stay below 2^31.
+    types: an ``EdgeTypes``; an entry with a type outside [0, R) contributes nothing.  x: [n, K] fp32, differentiable.
+    weight: [R, K, O] fp32, differentiable.  values: [nnz] fp32 in the entry order of the adjacency, or None (ones); NOT
+    differentiable.  The first call builds the view (one host synchronisation); later calls only enqueue (capturable).
+    TypeError for a non-EdgeTypes, ValueError for a wrong shape, GcnAmdError for a CPU tensor or a dtype other than fp32."""
+    if not isinstance(types, EdgeTypes):
+        raise TypeError("relation_transform_aggregate: types must be an EdgeTypes")
+    adj, R = types.adj, types.num_relations
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != adj.n or x.shape[1] < 1:
+        raise ValueError(f"relation_transform_aggregate: x must be a 2-D tensor of n = {adj.n} rows and at least one column")
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 3 or tuple(weight.shape[:2]) != (R, x.shape[1]) or weight.shape[2] < 1:
+        raise ValueError(f"relation_transform_aggregate: weight must be [R, K, O] with R = {R} and K = {x.shape[1]}")
+    if values is not None and (not isinstance(values, torch.Tensor) or values.dim() != 1 or values.shape[0] != adj.nnz):
+        raise ValueError(f"relation_transform_aggregate: values must be a 1-D tensor of nnz = {adj.nnz} entries")
+    _check_fp32("relation_transform_aggregate", (("x", x), ("weight", weight), ("values", values)))
+    if values is not None and values.requires_grad:
+        raise ValueError("relation_transform_aggregate: values is not differentiable (detach it)")
+    if adj.nnz * max(int(x.shape[1]), int(weight.shape[2])) >= 2 ** 31:
+        raise ValueError("relation_transform_aggregate: nnz * max(K, O) must stay below 2^31")
+    return _RelationTransformFunction.apply(types, x, weight, values)

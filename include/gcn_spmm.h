@@ -447,6 +447,38 @@ int gcn_relation_aggregate_backward_coeff_f32(const int32_t* relptr_dev, const i
                                               int32_t nnz, const float* g, const float* x, int32_t k, int32_t num_bases,
                                               const float* values, float* gcoeff, void* ws, size_t ws_bytes, void* stream);
 
+/* Grouped matrix product (segment_mm.hip; DGL's segment_mm / gather_mm, pyg_lib's segment_matmul): the rows are cut into T
+ * consecutive segments by segptr_dev int32 [T + 1] and segment t is multiplied by its own weight W[t].  fp32 on the matrix
+ * cores (v_mfma_f32_32x32x2_f32: exact fp32, an fma chain over ascending k).  Plan-free: kernels only, no allocation, no
+ * host synchronisation, no host read of segptr_dev (legal inside a stream capture), no atomics, one writer per output
+ * element: the same bits at every call.  With t(i) the segment of row i, xi(i) = x_index ? x_index[i] : i (gi likewise):
+ *   y[i, :] = scale[i] * ( x[xi(i), :] @ op(W[t(i)]) )          for i in [0, N)
+ * x [x_rows x K]; x_index int32 [N] or NULL, repeats allowed, an index outside [0, x_rows) reads a row of zeros; scale [N]
+ * or NULL, applied once to the finished dot product; W [T x K x O], or with transpose_w != 0 [T x O x K] read as its
+ * transpose (no copy); y [N x O].  The segment bounds are made monotone on the device: bound s is the largest of
+ * segptr[0 .. s], clamped to [0, N], so a decreasing pointer is an empty segment.  Rows in front of segptr[0] and behind
+ * segptr[T] are written as zeros; an empty segment costs nothing.  N K and N O may pass 2^31 (row offsets are 64-bit).
+ * Non-finite values: a NaN or Inf in row xi(i) of x reaches row i of y only, one in W[t] the rows of segment t only (the
+ * tiles' padding is zero on both operands).
+ * ws: device scratch of at least the bytes gcn_segment_mm_ws_bytes reports for (N, T, K, O), 16-byte aligned, owned by the
+ * call while it runs; both entry points share it.  GCN_SEGMENT_MM_CHUNK rows make one partial of the weight gradient.
+ * GCN_ERR_INVALID_ARG: N < 0, T < 0, x_rows < 0, K < 1, O < 1, K O >= 2^31, more than 65535 tiles of 64 in K or O, N / 64 +
+ * T + 2 >= 2^31, a NULL operand, a short workspace.  N == 0: GCN_OK, nothing launched. */
+#define GCN_SEGMENT_MM_CHUNK 512
+int gcn_segment_mm_ws_bytes(int32_t N, int32_t T, int32_t K, int32_t O, size_t* bytes);
+int gcn_segment_mm_f32(const float* x, int32_t x_rows, const int32_t* x_index_dev, const float* scale,
+                       const int32_t* segptr_dev, const float* W, int32_t transpose_w, int32_t N, int32_t T, int32_t K,
+                       int32_t O, float* y, void* ws, size_t ws_bytes, void* stream);
+/* The weight gradient, dW [T x K x O]:
+ *   dW[t] = sum over the rows i of segment t of  scale[i] * x[xi(i), :]^T (x) g[gi(i), :]
+ * x [x_rows x K] and g [g_rows x O], both gathered (either index may be NULL).  scale[i] x is rounded once, then the rows
+ * are an fma chain in ascending order within a chunk of GCN_SEGMENT_MM_CHUNK rows; a longer segment's chunk partials go to
+ * the workspace and are added in chunk order by a second kernel.  An empty segment gives exact zeros.  T == 0: GCN_OK,
+ * nothing launched. */
+int gcn_segment_mm_wgrad_f32(const float* x, int32_t x_rows, const int32_t* x_index_dev, const float* g, int32_t g_rows,
+                             const int32_t* g_index_dev, const float* scale, const int32_t* segptr_dev, int32_t N, int32_t T,
+                             int32_t K, int32_t O, float* dW, void* ws, size_t ws_bytes, void* stream);
+
 /* Edge-feature message passing (edge_message.hip; DGL's u_op_e -> reduce: GINE, MPNN, CGConv): a feature VECTOR per stored
  * entry beside the gathered node row.  Plan-free like the aggregation family above: the caller's CSR, one memset node and
  * kernels (no allocation, no host synchronisation, no host read of device data: legal inside a stream capture), no
