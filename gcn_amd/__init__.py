@@ -21,6 +21,7 @@ from .coalesce import coalesce_csr, gcn_adjacency, normalize_csr, symmetrize  # 
 from .linkpred import LinkNeighborLoader, edge_subgraph, find_edges, negative_sample, pair_scores, reverse_entries, split_edges  # noqa: F401
 from .spgemm import HypergraphLaplacian, SparseProduct, hypergraph_laplacian, sampled_dot, spgemm  # noqa: F401
 from .knn import KNN_K_MAX, knn, knn_graph, knn_hypergraph  # noqa: F401
+from .points import fps, radius, radius_graph  # noqa: F401
 from . import reorder, dropin  # noqa: F401
 from .layers import GCN, GINConv, GINEConv, HGNN, GraphAttention, GraphAttentionV2, GraphConvolution, GraphConvolution2, GraphSAGE, HGNNConv, MedianConv, PNAConv, RGCNConv, SAGEConv  # noqa: F401
 

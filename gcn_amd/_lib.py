@@ -213,6 +213,13 @@ SIGNATURES = {
     "gcn_knn_ws_bytes": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, _c_i32, ctypes.POINTER(ctypes.c_size_t)]),
     "gcn_knn_f32": (ctypes.c_int, [_c_p, ctypes.c_int64, _c_p, ctypes.c_int64, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32,
                                    _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_knn_segmented_ws_bytes": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, ctypes.POINTER(ctypes.c_size_t)]),
+    "gcn_knn_segmented_f32": (ctypes.c_int, [_c_p, ctypes.c_int64, _c_p, ctypes.c_int64, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32,
+                                             ctypes.c_float, _c_p, _c_p, _c_i32, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+    "gcn_fps_resident_points": (ctypes.c_int, [_c_i32]),
+    "gcn_fps_ws_bytes": (ctypes.c_int, [_c_i32, _c_i32, _c_i32, ctypes.POINTER(ctypes.c_size_t)]),
+    "gcn_fps_f32": (ctypes.c_int, [_c_p, ctypes.c_int64, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_i32, _c_p, _c_p, _c_p,
+                                   ctypes.c_size_t, _c_p]),
     "gcn_spmm_plan_sddmm_kernel":(ctypes.c_int, [_c_p, _c_i32, ctypes.c_char_p, _c_i32]),
     "gcn_spmm_plan_enable_panels": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_p]),
     "gcn_spmm_plan_panel_rows": (_c_i32, [_c_p]),

@@ -21,7 +21,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 ARCH = "gfx950"
 DROPIN_NAMES = ["flexspmm.so", "cuspmm.so", "tile.so", "permutate.so", "renumber.so"]
 
-SOURCES = ["spmm_kernels.hip", "spmm_narrow.hip", "spmm_quad.hip", "spmm_group.hip", "spmm_group_bf16.hip", "spmm_panel.hip", "sddmm.hip", "edge_softmax.hip", "aggregate.hip", "aggregate_multi.hip", "aggregate_quantile.hip", "relational.hip", "segment_mm.hip", "multihead.hip", "edge_message.hip", "sample.hip", "subgraph.hip", "lookup.hip", "construct.hip", "coalesce.hip", "spgemm.hip", "knn.hip", "slicing.hip", "reorder_device.hip", "rabbit_device.hip", "exchange.hip", "plan_policy.cpp", "plan_build.cpp", "api_spmm.cpp", "api_units.cpp", "api_reorder.cpp", "api_dropin.cpp", "reorder.cpp", "sampled_dot.hip"]
+SOURCES = ["spmm_kernels.hip", "spmm_narrow.hip", "spmm_quad.hip", "spmm_group.hip", "spmm_group_bf16.hip", "spmm_panel.hip", "sddmm.hip", "edge_softmax.hip", "aggregate.hip", "aggregate_multi.hip", "aggregate_quantile.hip", "relational.hip", "segment_mm.hip", "multihead.hip", "edge_message.hip", "sample.hip", "subgraph.hip", "lookup.hip", "construct.hip", "coalesce.hip", "spgemm.hip", "knn.hip", "fps.hip", "slicing.hip", "reorder_device.hip", "rabbit_device.hip", "exchange.hip", "plan_policy.cpp", "plan_build.cpp", "api_spmm.cpp", "api_units.cpp", "api_reorder.cpp", "api_dropin.cpp", "reorder.cpp", "sampled_dot.hip"]
 # per-unit compiler flags: the sums of aggregate_multi.hip and relational.hip are specified operation by operation
 # (include/gcn_spmm.h), so the packed two-lane fp32 instructions are kept out of them
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]

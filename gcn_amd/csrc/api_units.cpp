@@ -685,6 +685,40 @@ int gcn_knn_f32(const float* x, int64_t ldx, const float* y, int64_t ldy, int32_
   return hip_status(launch_knn(x, ldx, y, ldy, q, n, d, k, self_offset, eff, out_idx, out_dist2, out_sum, ws, (hipStream_t)stream));
 }
 
+int gcn_knn_segmented_ws_bytes(int32_t q, int32_t n, int32_t k, size_t* bytes) {
+  if (!knn_sizes_ok(q, n, k, 0) || !bytes) return GCN_ERR_INVALID_ARG;
+  *bytes = kKnnSegmentedWsBytes;
+  return GCN_OK;
+}
+
+int gcn_knn_segmented_f32(const float* x, int64_t ldx, const float* y, int64_t ldy, int32_t q, int32_t n, int32_t d, int32_t k,
+                          int32_t self_offset, float radius2, const int32_t* ptr_x, const int32_t* ptr_y, int32_t segments,
+                          int32_t* out_idx, float* out_dist2, void* ws, size_t ws_bytes, void* stream) {
+  if (!knn_sizes_ok(q, n, k, 0) || d < 1 || ldx < d || ldy < d || self_offset < -1 || segments < 0 || !(radius2 >= 0.0f))
+    return GCN_ERR_INVALID_ARG;
+  if (q == 0) return GCN_OK;
+  if (!x || (n > 0 && !y) || !out_idx || !ptr_x || !ptr_y || !ws || ws_bytes < kKnnSegmentedWsBytes) return GCN_ERR_INVALID_ARG;
+  return hip_status(launch_knn_segmented(x, ldx, y, ldy, q, n, d, k, self_offset, radius2, ptr_x, ptr_y, segments, out_idx,
+                                         out_dist2, (hipStream_t)stream));
+}
+
+int gcn_fps_resident_points(int32_t d) { return fps_resident_points(d); }
+
+int gcn_fps_ws_bytes(int32_t n, int32_t d, int32_t segments, size_t* bytes) {
+  if (n < 0 || d < 1 || segments < 0 || !bytes) return GCN_ERR_INVALID_ARG;
+  *bytes = fps_workspace_bytes(n, d);
+  return GCN_OK;
+}
+
+int gcn_fps_f32(const float* x, int64_t ldx, int32_t n, int32_t d, const int32_t* seg_ptr, const int32_t* out_ptr,
+                const int32_t* start, int32_t segments, int32_t* out_idx, float* out_dist2, void* ws, size_t ws_bytes,
+                void* stream) {
+  if (n < 0 || d < 1 || segments < 0 || ldx < d) return GCN_ERR_INVALID_ARG;
+  if (n == 0 || segments == 0) return GCN_OK;
+  if (!x || !seg_ptr || !out_ptr || !out_idx || !ws || ws_bytes < fps_workspace_bytes(n, d)) return GCN_ERR_INVALID_ARG;
+  return hip_status(launch_fps(x, ldx, n, d, seg_ptr, out_ptr, start, segments, out_idx, out_dist2, ws, (hipStream_t)stream));
+}
+
 int gcn_gather_rows_f32(float* dst, const float* src, const int32_t* idx, int32_t nrows, int32_t k,
                         void* stream) {
   if (nrows < 0 || k < 0) return GCN_ERR_INVALID_ARG;

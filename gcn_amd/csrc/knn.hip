@@ -27,6 +27,12 @@
 // threads of the row are added by a fixed shuffle tree, and the tile's sum is added to the running fp64 sum of the row.  The
 // order depends on nothing but `splits` (a part's tiles are added first, then the parts).
 //
+// SEGMENTS AND RADIUS (gcn_knn_segmented_f32).  The tile kernel's SEG instantiation: one thread per query finds the query's
+// segment in ptr_x by bisection and writes its candidate window [ptr_y[s], ptr_y[s + 1]), clamped to [0, n], to LDS; the
+// workgroup walks the tiles from its smallest window start to its largest window end, and a candidate is admissible only
+// inside the query's window and, under a finite radius2, at d2 <= radius2 (a NaN never is).  One part, no merge kernel: the
+// tile kernel writes idx / dist2 itself.
+//
 // Every global access is a 4- or 8-byte one at its natural alignment: operands need 4-byte alignment and any row stride >= d.
 #include <hip/hip_runtime.h>
 
@@ -55,6 +61,10 @@ struct KnnArgs {
   int* out_idx;
   float* out_dist2;
   double* out_sum;
+  float radius2;                                       // the segmented mode only, as the three below
+  const int* ptr_x;                                    // [segments + 1]
+  const int* ptr_y;
+  int segments;
 };
 
 // a wave's steps on LDS are ordered by keeping the compiler from moving the accesses (spgemm.hip's unit_sync)
@@ -87,8 +97,11 @@ __device__ __forceinline__ int compact(u64* buf, int cnt, int k, int lane) {
   return cnt < k ? cnt : k;
 }
 
-template <bool WANT_SUM>
+// SEG: query i sees the candidates [lo_i, hi_i) that its segment names, and of those the ones within the radius; the
+// workgroup walks the tiles from its smallest lo to its largest hi, a.splits is 1 and the result goes straight out.
+template <bool WANT_SUM, bool SEG>
 __global__ void __launch_bounds__(256) knn_tile_kernel(KnnArgs a) {
+  static_assert(!(WANT_SUM && SEG), "no row sums over windows");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int cap = a.k + kKnnTileC;
   float* xs = reinterpret_cast<float*>(smem);          // [2][kChunk][kLd]: column-major tiles, two buffers
@@ -102,13 +115,56 @@ __global__ void __launch_bounds__(256) knn_tile_kernel(KnnArgs a) {
   const int part = (int)(blockIdx.x % (unsigned)a.splits);
   const long long q0 = (long long)(blockIdx.x / (unsigned)a.splits) * kKnnTileQ;
   const long long tiles = ((long long)a.n + kKnnTileC - 1) / kKnnTileC;
-  const long long t_begin = (long long)part * tiles / a.splits, t_end = ((long long)part + 1) * tiles / a.splits;
+  long long t_begin = (long long)part * tiles / a.splits, t_end = ((long long)part + 1) * tiles / a.splits;
   const int nch = (a.d + kChunk - 1) / kChunk;
 
   if (tid < kKnnTileQ) {
     thr[tid] = kEmpty;
     cnt[tid] = 0;
   }
+  int win_lo[4] = {0, 0, 0, 0}, win_hi[4] = {0, 0, 0, 0};  // (SEG) the windows of the thread's four queries
+  if constexpr (SEG) {
+    int* seg_lo = cnt + kKnnTileQ;                     // [64]
+    int* seg_hi = seg_lo + kKnnTileQ;                  // [64]
+    if (tid < kKnnTileQ) {
+      // the last s in [0, segments] with ptr_x[s] <= row; whatever the array holds, s stays inside it and the window
+      // inside [0, n]
+      const long long row = q0 + tid;
+      int lo = 0, hi = 0, s = -1;
+      for (int b0 = 0, b1 = a.segments + 1; b0 < b1;) {
+        const int mid = b0 + (b1 - b0) / 2;
+        if (a.ptr_x[mid] <= row) {
+          s = mid;
+          b0 = mid + 1;
+        } else {
+          b1 = mid;
+        }
+      }
+      if (row < a.q && s >= 0 && s < a.segments && row < a.ptr_x[s + 1]) {
+        const int y0 = a.ptr_y[s], y1 = a.ptr_y[s + 1];
+        lo = y0 < 0 ? 0 : (y0 > a.n ? a.n : y0);
+        hi = y1 < 0 ? 0 : (y1 > a.n ? a.n : y1);
+        if (hi < lo) hi = lo;
+      }
+      seg_lo[tid] = lo;
+      seg_hi[tid] = hi;
+    }
+    __syncthreads();
+    int wlo = a.n, whi = 0;
+    for (int i = 0; i < kKnnTileQ; ++i)
+      if (seg_hi[i] > seg_lo[i]) {
+        wlo = seg_lo[i] < wlo ? seg_lo[i] : wlo;
+        whi = seg_hi[i] > whi ? seg_hi[i] : whi;
+      }
+    t_begin = wlo / kKnnTileC;
+    t_end = whi > wlo ? ((long long)whi + kKnnTileC - 1) / kKnnTileC : t_begin;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      win_lo[i] = seg_lo[ty * 4 + i];
+      win_hi[i] = seg_hi[ty * 4 + i];
+    }
+  }
+  const bool bounded = SEG && a.radius2 < __uint_as_float(0x7f800000u);
 
   float px[8], py[8];
   auto gload = [&](long long tile, int ch) {
@@ -185,7 +241,9 @@ __global__ void __launch_bounds__(256) knn_tile_kernel(KnnArgs a) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const long long cj = j0 + j;
-            if (cj < a.n && cj != self) {
+            bool ok = cj < a.n && cj != self;
+            if constexpr (SEG) ok = ok && cj >= win_lo[i] && cj < win_hi[i] && (!bounded || acc[i][j] <= a.radius2);
+            if (ok) {
               const u64 key = make_key(acc[i][j], cj);
               if (key < t) keys[(size_t)qi * cap + atomicAdd(&cnt[qi], 1)] = key;
             }
@@ -230,7 +288,16 @@ __global__ void __launch_bounds__(256) knn_tile_kernel(KnnArgs a) {
     if (row >= a.q) break;                             // (wave-uniform)
     u64* buf = keys + (size_t)qi * cap;
     const int c = compact(buf, cnt[qi], a.k, lane);
-    if (lane < a.k) a.part_keys[((size_t)row * a.splits + part) * a.k + lane] = lane < c ? buf[lane] : kEmpty;
+    if constexpr (SEG) {
+      if (lane < a.k) {
+        const u64 key = lane < c ? buf[lane] : kEmpty;
+        const size_t o = (size_t)row * a.k + lane;
+        a.out_idx[o] = key == kEmpty ? -1 : (int)(unsigned)(key & 0xffffffffull);
+        if (a.out_dist2) a.out_dist2[o] = key == kEmpty ? __uint_as_float(0x7f800000u) : __uint_as_float((unsigned)(key >> 32));
+      }
+    } else {
+      if (lane < a.k) a.part_keys[((size_t)row * a.splits + part) * a.k + lane] = lane < c ? buf[lane] : kEmpty;
+    }
   }
   if (WANT_SUM && tx == 0) {
 #pragma unroll
@@ -278,8 +345,24 @@ __global__ void __launch_bounds__(256) knn_merge_kernel(KnnArgs a) {
   }
 }
 
-size_t tile_lds_bytes(int k) {
-  return (size_t)4 * kStage * 4 + (size_t)kKnnTileQ * (k + kKnnTileC) * 8 + kKnnTileQ * 8 + kKnnTileQ * 4;
+size_t tile_lds_bytes(int k, bool seg = false) {
+  return (size_t)4 * kStage * 4 + (size_t)kKnnTileQ * (k + kKnnTileC) * 8 + kKnnTileQ * 8 + kKnnTileQ * 4 + (seg ? kKnnTileQ * 8 : 0);
+}
+
+// dynamic LDS above 64 KiB has to be asked for, once per device
+hipError_t raise_tile_lds() {
+  static bool raised[64];
+  int dev = 0;
+  if (hipError_t err = hipGetDevice(&dev); err != hipSuccess) return err;
+  if (dev < 0 || dev >= 64 || !raised[dev]) {
+    for (const void* f : {reinterpret_cast<const void*>(&knn_tile_kernel<false, false>), reinterpret_cast<const void*>(&knn_tile_kernel<true, false>),
+                          reinterpret_cast<const void*>(&knn_tile_kernel<false, true>)})
+      if (hipError_t err = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds_bytes(kKnnKMax, true));
+          err != hipSuccess)
+        return err;
+    if (dev >= 0 && dev < 64) raised[dev] = true;
+  }
+  return hipSuccess;
 }
 
 }  // namespace
@@ -300,23 +383,24 @@ hipError_t launch_knn(const float* x, long long ldx, const float* y, long long l
   KnnArgs a{x, y, ldx, ldy, q, n, d, k, self_offset, eff_splits, nullptr, nullptr, out_idx, out_dist2, out_sum};
   a.part_keys = reinterpret_cast<u64*>(ws);
   if (out_sum) a.part_sum = reinterpret_cast<double*>(a.part_keys + (size_t)q * eff_splits * k);
-  static bool raised[64];                              // (dynamic LDS above 64 KiB has to be asked for, once per device)
-  int dev = 0;
-  if (hipError_t err = hipGetDevice(&dev); err != hipSuccess) return err;
-  if (dev < 0 || dev >= 64 || !raised[dev]) {
-    for (const void* f : {reinterpret_cast<const void*>(&knn_tile_kernel<false>), reinterpret_cast<const void*>(&knn_tile_kernel<true>)})
-      if (hipError_t err = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds_bytes(kKnnKMax));
-          err != hipSuccess)
-        return err;
-    if (dev >= 0 && dev < 64) raised[dev] = true;
-  }
+  if (hipError_t err = raise_tile_lds(); err != hipSuccess) return err;
   const long long qblocks = ((long long)q + kKnnTileQ - 1) / kKnnTileQ;
   if (out_sum)
-    knn_tile_kernel<true><<<(unsigned)(qblocks * eff_splits), 256, tile_lds_bytes(k), st>>>(a);
+    knn_tile_kernel<true, false><<<(unsigned)(qblocks * eff_splits), 256, tile_lds_bytes(k), st>>>(a);
   else
-    knn_tile_kernel<false><<<(unsigned)(qblocks * eff_splits), 256, tile_lds_bytes(k), st>>>(a);
+    knn_tile_kernel<false, false><<<(unsigned)(qblocks * eff_splits), 256, tile_lds_bytes(k), st>>>(a);
   if (hipError_t err = hipGetLastError(); err != hipSuccess) return err;
   knn_merge_kernel<<<(unsigned)(((long long)q + 3) / 4), 256, 0, st>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_knn_segmented(const float* x, long long ldx, const float* y, long long ldy, int q, int n, int d, int k,
+                                int self_offset, float radius2, const int* ptr_x, const int* ptr_y, int segments, int* out_idx,
+                                float* out_dist2, hipStream_t st) {
+  KnnArgs a{x, y, ldx, ldy, q, n, d, k, self_offset, 1, nullptr, nullptr, out_idx, out_dist2, nullptr, radius2, ptr_x, ptr_y, segments};
+  if (hipError_t err = raise_tile_lds(); err != hipSuccess) return err;
+  const long long qblocks = ((long long)q + kKnnTileQ - 1) / kKnnTileQ;
+  knn_tile_kernel<false, true><<<(unsigned)qblocks, 256, tile_lds_bytes(k, true), st>>>(a);
   return hipGetLastError();
 }
 

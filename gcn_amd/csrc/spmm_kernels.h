@@ -319,6 +319,22 @@ int knn_effective_splits(int q, int n, int splits, int cus);
 size_t knn_workspace_bytes(int q, int k, int eff_splits);
 hipError_t launch_knn(const float* x, long long ldx, const float* y, long long ldy, int q, int n, int d, int k, int self_offset,
                       int eff_splits, int* out_idx, float* out_dist2, double* out_sum, void* ws, hipStream_t st);
+// the same tile kernel with a candidate window per query (the segment of ptr_y that the query's segment of ptr_x names) and
+// a radius; no splits and no merge kernel: the tile kernel writes the result itself.
+constexpr size_t kKnnSegmentedWsBytes = 16;
+hipError_t launch_knn_segmented(const float* x, long long ldx, const float* y, long long ldy, int q, int n, int d, int k,
+                                int self_offset, float radius2, const int* ptr_x, const int* ptr_y, int segments, int* out_idx,
+                                float* out_dist2, hipStream_t st);
+
+// fps.hip — farthest point sampling of clouds stored back to back, one workgroup per cloud (plan-free, no atomics: see the
+// file's header and include/gcn_spmm.h).  Clouds of at most fps_resident_points(d) rows stay on chip (registers for d <= 4,
+// kFpsLdsFloats of LDS above); larger ones keep dmin in the workspace.  ws: fps_workspace_bytes(n, d).
+constexpr int kFpsResidentMax = 8192;
+constexpr int kFpsLdsFloats = 32768;
+int fps_resident_points(int d);
+size_t fps_workspace_bytes(int n, int d);
+hipError_t launch_fps(const float* x, long long ldx, int n, int d, const int* seg_ptr, const int* out_ptr, const int* start,
+                      int segments, int* out_idx, float* out_dist2, void* ws, hipStream_t st);
 
 // slicing.hip — mutable values.  vsrc[s*m + r] = CSR position of the first entry of row r in slice s (from the sliced
 // row pointer; column-sorted rows make every (row, slice) part one contiguous run of the CSR row).

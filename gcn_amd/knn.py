@@ -4,6 +4,7 @@
     adj = gcn_amd.knn_graph(x, 16)                         # CsrAdjacency [n x n]: row i holds its 16 nearest other rows
     H = gcn_amd.knn_hypergraph(x, 10)                      # incidence matrix [n x n] of the HGNN construction
     G = gcn_amd.hypergraph_laplacian(H)
+    idx, dist2 = gcn_amd.knn(x, 16, ptr_x=ptr)             # a batch of clouds back to back: neighbours within a cloud only
 
 The primitive is an exact contract written out in include/gcn_spmm.h (``gcn_knn_f32``) and runs on gcn_amd/csrc/knn.hip;
 tests/knn_ref.py is its numpy twin.  The q x n distance matrix is never formed.  There is no CPU path: CPU operands raise.
@@ -69,7 +70,86 @@ def _check_k(what, k, top=KNN_K_MAX):
         raise ValueError(f"{what}: k must be an int in [1, {top}], not {k!r}")
 
 
-def knn(x, k, y=None, exclude_self=False, splits=0, self_offset=None):
+def _check_ptr(what, name, ptr, rows):
+    """a host segment pointer as a list of ints: ascending from >= 0 to exactly `rows`"""
+    try:
+        out = [int(v) for v in ptr]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: {name} must be a sequence of ints or an int32 device tensor, not {ptr!r}") from None
+    if len(out) < 1 or out[0] < 0 or any(b < a for a, b in zip(out, out[1:])):
+        raise ValueError(f"{what}: {name} must hold at least one entry, start at >= 0 and ascend")
+    if out[-1] != rows:
+        raise ValueError(f"{what}: {name} ends at {out[-1]} but there are {rows} rows")
+    return out
+
+
+def _upload(dev, lists):
+    """int32 device tensors of the host lists, sent up in one copy"""
+    flat = torch.tensor([v for lst in lists for v in lst], dtype=torch.int32).to(dev)
+    return list(flat.split([len(lst) for lst in lists]))
+
+
+def _device_ptrs(what, dev, named):
+    """[(name, ptr, rows)] -> int32 device tensors: host sequences are checked and go up in one copy; an int32 device tensor
+    passes as it is (its contents are the kernel's to clamp)"""
+    host, out = {}, {}
+    for name, ptr, rows in named:
+        if isinstance(ptr, torch.Tensor):
+            if ptr.dtype != torch.int32 or ptr.dim() != 1 or ptr.numel() < 1 or ptr.device != dev:
+                raise ValueError(f"{what}: a tensor {name} must be int32, 1-D, not empty and on {dev}")
+            out[name] = ptr.contiguous()
+        else:
+            host[name] = _check_ptr(what, name, ptr, rows)
+    if host:
+        out.update(zip(host, _upload(dev, list(host.values()))))
+    return [out[name] for name, _, _ in named]
+
+
+def _pair_ptrs(what, y, ptr_x, ptr_y):
+    """the (ptr_x, ptr_y) a call works with: ptr_y defaults to ptr_x when the candidates are the queries"""
+    if ptr_x is None or (ptr_y is None and y is not None):
+        raise ValueError(f"{what}: ptr_y needs ptr_x, and with y given ptr_x needs ptr_y")
+    return ptr_x, ptr_x if ptr_y is None else ptr_y
+
+
+def _knn_segmented(what, x, y, k, self_offset, radius2, ptr_x, ptr_y, want_dist2=True):
+    """(idx int32 [q, k], dist2 fp32 [q, k] or None) of one gcn_knn_segmented_f32 call on checked points; the pointers are
+    checked here"""
+    dev = x.device
+    q, d, n = int(x.shape[0]), int(x.shape[1]), int(y.shape[0])
+    px, py = _device_ptrs(what, dev, [("ptr_x", ptr_x, q), ("ptr_y", ptr_y, n)])
+    if px.numel() != py.numel():
+        raise ValueError(f"{what}: ptr_x names {px.numel() - 1} segments and ptr_y {py.numel() - 1}")
+    idx = torch.empty((q, k), dtype=torch.int32, device=dev)
+    dist2 = torch.empty((q, k), dtype=torch.float32, device=dev) if want_dist2 else None
+    if q == 0:
+        return idx, dist2
+    x, ldx = _rows(x.detach(), d)
+    y, ldy = _rows(y.detach(), d)
+    nbytes = ctypes.c_size_t(0)
+    call("gcn_knn_segmented_ws_bytes", q, n, k, ctypes.byref(nbytes))
+    ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+    call("gcn_knn_segmented_f32", x, ldx, y, ldy, q, n, d, k, self_offset, float(radius2), px, py, px.numel() - 1, idx,
+         dist2, ws, ws.numel(), device=dev)
+    return idx, dist2
+
+
+def _csr_of_neighbours(idx, dist2, n, values):
+    """CsrAdjacency [n x n] of the entries >= 0 of idx [n, k], columns ascending within a row; values: None = ones,
+    "distance" = sqrt(dist2).  Row lengths vary: the row pointer is a device cumsum of the counts, and picking the entries out
+    reads their number back (one host synchronisation)."""
+    dev = idx.device
+    none = torch.iinfo(torch.int32).max
+    col, order = torch.where(idx >= 0, idx, torch.full_like(idx, none)).sort(dim=1)
+    keep = col != none
+    rowptr = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    rowptr[1:] = keep.sum(dim=1).cumsum(0)
+    col = col[keep]
+    val = torch.ones(col.numel(), dtype=torch.float32, device=dev) if values is None else dist2.gather(1, order)[keep].sqrt()
+    return CsrAdjacency(rowptr, col, val, (n, n), symmetric=False)
+
+
+def knn(x, k, y=None, exclude_self=False, splits=0, self_offset=None, ptr_x=None, ptr_y=None):
     """The k nearest rows of ``y`` for every row of ``x`` by squared Euclidean distance, brute force on the device: returns
     ``(idx int32 [q, k], dist2 fp32 [q, k])``.
 
@@ -82,11 +162,16 @@ def knn(x, k, y=None, exclude_self=False, splits=0, self_offset=None):
     (the queries are rows [self_offset, self_offset + q) of y).
     splits: parts the candidate range is cut into so that few queries still fill the chip; 0 lets the library choose, and
     ``idx`` / ``dist2`` do not depend on it.
+    ptr_x, ptr_y: segment pointers of a batch of point sets stored back to back (B + 1 ascending ints each, ending at q and at
+    n): a query of segment s sees only the candidates of segment s of ``y`` (``gcn_knn_segmented_f32``); indices stay global.
+    Host sequences (checked, sent up in one copy) or int32 device tensors (taken as they are).  With y=None, ptr_y defaults
+    to ptr_x.  With both None nothing changes: the same call, the same bits.  The candidate range is not split in this mode:
+    splits other than 0 together with pointers is a ValueError.
     Rows with unit column stride are passed by their row stride; anything else is made contiguous.  Not differentiable.
     No host synchronisation.
     The checks, in this order: TypeError for a non-tensor or a dtype other than fp32; GcnAmdError for CPU tensors or two
-    devices; ValueError for shapes (2-D, equal d >= 1), for k outside [1, KNN_K_MAX], and for exclude_self / self_offset /
-    splits that make no sense."""
+    devices; ValueError for shapes (2-D, equal d >= 1), for k outside [1, KNN_K_MAX], for exclude_self / self_offset /
+    splits that make no sense, and for pointers that do not ascend, do not end at the row count or do not pair up."""
     what = "knn"
     _check_points(what, x, y)
     _check_k(what, k)
@@ -99,11 +184,16 @@ def knn(x, k, y=None, exclude_self=False, splits=0, self_offset=None):
     if isinstance(splits, bool) or not isinstance(splits, int) or splits < 0:
         raise ValueError(f"{what}: splits must be an int >= 0, not {splits!r}")
     off = -1 if not exclude_self else (0 if self_offset is None else self_offset)
-    idx, dist2, _ = _knn(x, x if y is None else y, k, off, splits)
-    return idx, dist2
+    if ptr_x is None and ptr_y is None:
+        idx, dist2, _ = _knn(x, x if y is None else y, k, off, splits)
+        return idx, dist2
+    if splits != 0:
+        raise ValueError(f"{what}: splits must be 0 with ptr_x / ptr_y (the candidate range is not split in this mode)")
+    ptr_x, ptr_y = _pair_ptrs(what, y, ptr_x, ptr_y)
+    return _knn_segmented(what, x, x if y is None else y, k, off, float("inf"), ptr_x, ptr_y)
 
 
-def knn_graph(x, k, loop=False, values=None):
+def knn_graph(x, k, loop=False, values=None, ptr=None):
     """The k-nearest-neighbour graph of the rows of ``x`` (fp32 [n, d]) on the device: returns a CsrAdjacency [n x n] whose
     row i holds the k nearest rows of i, columns ascending, flagged ``symmetric=False``.
 
@@ -113,6 +203,9 @@ def knn_graph(x, k, loop=False, values=None):
     values: None = ones; "distance" = the fp32 square roots of the squared distances ``knn`` returns.
     The way on to a normalised Â is the existing merge: ``normalize_csr(symmetrize(knn_graph(x, k)), "sym")`` — the
     neighbour relation is not symmetric, ``symmetrize`` adds the missing directions.
+    ptr: segment pointers of a batch of clouds (as ``knn``'s ptr_x): neighbours come from the row's own cloud only, a row of
+    cloud b has ``min(k, n_b - 1)`` (loop: ``min(k, n_b)``) entries.  Row lengths then vary: the row pointer is a device
+    cumsum and the entry count is read back, ONE host synchronisation.
     The checks are those of ``knn``, then ValueError for unknown ``values``."""
     what = "knn_graph"
     _check_points(what, x)
@@ -120,6 +213,11 @@ def knn_graph(x, k, loop=False, values=None):
     if values is not None and values != "distance":
         raise ValueError(f"{what}: values must be None or \"distance\", not {values!r}")
     dev, n = x.device, int(x.shape[0])
+    if ptr is not None:
+        if n * k >= 2 ** 31:
+            raise ValueError(f"{what}: n * k must stay below 2^31")
+        idx, dist2 = _knn_segmented(what, x, x, k, -1 if loop else 0, float("inf"), ptr, ptr, want_dist2=values is not None)
+        return _csr_of_neighbours(idx, dist2, n, values)
     kk = min(k, n if loop else n - 1)
     if n * max(kk, 0) >= 2 ** 31:
         raise ValueError(f"{what}: n * k must stay below 2^31")

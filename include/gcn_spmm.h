@@ -983,6 +983,61 @@ int gcn_knn_f32(const float* x_dev, int64_t ldx, const float* y_dev, int64_t ldy
                 int32_t self_offset, int32_t splits, int32_t* out_idx_dev, float* out_dist2_dev /* may be NULL */,
                 double* out_sum_dev /* may be NULL */, void* ws, size_t ws_bytes, void* stream);
 
+/* The same search over a batch of point sets stored back to back, with an optional radius.  It is gcn_knn_f32's contract word
+ * for word (DISTANCE, ORDER, SELF EXCLUSION, the -1 / +inf tail; no row sums), with two changes to what is admissible:
+ *   WINDOW.  ptr_x_dev and ptr_y_dev (int32 [segments + 1]) cut the queries and the candidates into segments; query i with
+ *   ptr_x[s] <= i < ptr_x[s + 1] sees only the candidates j in [ptr_y[s], ptr_y[s + 1]).  Indices stay global.  A query before
+ *   ptr_x[0] or behind ptr_x[segments] sees nothing: its row is all -1 / +inf.  ptr_x is expected to ascend (the segment is
+ *   found by bisection); whatever the two arrays hold, a window is clamped to [0, n], a decreasing pair is empty and nothing
+ *   outside the operands is read or written.
+ *   RADIUS.  Only candidates with d2 <= radius2 are admissible (inclusive); radius2 = +inf turns the test off.  A NaN
+ *   distance is never admissible under a finite radius.  With more than k admissible candidates the k nearest by (distance,
+ *   index) are kept, not the first k met.
+ * With one segment covering everything and radius2 = +inf the outputs are gcn_knn_f32's, bit for bit.
+ * One kernel: the tile kernel of gcn_knn_f32 with one thread per query finding its window at the start; the workgroup walks
+ * the candidate tiles from its smallest window start to its largest window end only.  The candidate range is not split (a
+ * batch has enough queries to fill the chip) and no merge kernel runs.  ws: gcn_knn_segmented_ws_bytes = 16 bytes, owned by
+ * the call until it has run (nothing is kept there today).
+ * GCN_ERR_INVALID_ARG, before any GPU work: what gcn_knn_f32 refuses, segments < 0, a NaN or negative radius2, and (with
+ * q > 0) a null ptr_x or ptr_y.  q == 0: GCN_OK, nothing launched. */
+int gcn_knn_segmented_ws_bytes(int32_t q, int32_t n, int32_t k, size_t* bytes);
+int gcn_knn_segmented_f32(const float* x_dev, int64_t ldx, const float* y_dev, int64_t ldy, int32_t q, int32_t n, int32_t d,
+                          int32_t k, int32_t self_offset, float radius2 /* +inf = none */, const int32_t* ptr_x_dev,
+                          const int32_t* ptr_y_dev, int32_t segments, int32_t* idx_dev, float* dist2_dev /* may be NULL */,
+                          void* ws_dev, size_t ws_bytes, void* stream);
+
+/* Farthest point sampling of a batch of point clouds stored back to back: x is fp32 [n x d] with row stride ldx >= d, cloud b
+ * is the rows [seg_ptr[b], seg_ptr[b + 1]) and gets m_b = out_ptr[b + 1] - out_ptr[b] picks, written at out_ptr[b].  Plan-free:
+ * the caller's arrays and workspace, at most three kernels enqueued on the stream, no allocation, no host read of device
+ * data, no synchronisation, no atomic; the same bits at every call.  The contract, exact and meant to be re-implemented:
+ *   DISTANCE.  d2(p, w) is gcn_knn_f32's: one fp32 accumulator from 0, columns ascending, diff = fl32(x_pc - x_wc), acc =
+ *   fmaf(diff, diff, acc).  A NaN d2 counts as 0: a row with a NaN coordinate is as close as can be to everything.
+ *   PICKS.  For segment b with rows [lo, hi) and m_b picks (clamped in the kernel to hi - lo): pick 0 is the start row,
+ *   start[b] (a global row, clamped into the segment) or lo when start is NULL.  Every unpicked row p keeps dmin_p, the
+ *   minimum over the picks so far of d2(p, pick).  The next pick is the unpicked row of largest dmin; on equal dmin the
+ *   smaller index wins.  A picked row leaves the candidates, so a segment's picks are distinct and with m_b = hi - lo they are
+ *   a permutation of the segment.
+ *   OUTPUT.  out_idx_dev: global row indices in pick order; out_dist2_dev (NULL skips it): the pick's dmin at the moment it
+ *   was chosen, +inf for pick 0.
+ *   BOUNDS.  Entries of seg_ptr and out_ptr are clamped to [0, n] in the kernel and a decreasing pair is an empty segment, so
+ *   no content of a device array makes a kernel read or write outside x, the workspace and the first n entries of the
+ *   outputs: outputs of min(n, the largest entry of out_ptr) elements are always enough.  Segments that overlap are not an
+ *   error but share scratch: their picks are then unspecified.  Rows are addressed in 64 bits (row * ldx).
+ * HOW THE WORK IS SPREAD.  One workgroup owns one cloud (the picks are a serial chain; a cloud is never spread over
+ * workgroups).  A cloud of at most gcn_fps_resident_points(d) rows stays on chip between picks: coordinates in registers for
+ * d <= 4 and in LDS above, dmin in registers, 256 threads up to 1024 rows and 1024 threads above.  A larger cloud keeps dmin
+ * in the workspace and re-reads its coordinates at every pick.  The routes give identical results.
+ *   gcn_fps_resident_points(d) = min(8192, 32768 / d) for d >= 1 (0 when nothing fits, and for d < 1).
+ * ws: device scratch owned by the call until it has run, 4-byte aligned; gcn_fps_ws_bytes(n, d, segments) = 16, plus 4 n
+ * rounded up to a multiple of 16 when n > gcn_fps_resident_points(d) (a cloud can then be on the streamed route).
+ * GCN_ERR_INVALID_ARG, before any GPU work: negative n or segments, d < 1, ldx < d, and (with n > 0 and segments > 0) a null
+ * x, seg_ptr, out_ptr, out_idx or ws, or a short workspace.  n == 0 or segments == 0: GCN_OK, nothing launched. */
+int gcn_fps_resident_points(int32_t d);
+int gcn_fps_ws_bytes(int32_t n, int32_t d, int32_t segments, size_t* bytes);
+int gcn_fps_f32(const float* x_dev, int64_t ldx, int32_t n, int32_t d, const int32_t* seg_ptr_dev, const int32_t* out_ptr_dev,
+                const int32_t* start_dev /* may be NULL */, int32_t segments, int32_t* out_idx_dev,
+                float* out_dist2_dev /* may be NULL */, void* ws_dev, size_t ws_bytes, void* stream);
+
 /* LDS-staged row panels (optional): for matrices whose non-zeros sit near the diagonal (community
  * graphs after Rabbit / RCM / Gorder renumbering) a workgroup stages the feature rows of its panel's
  * column window (512 rows x 64 columns = 128 KiB of LDS) once and sums the in-window non-zeros
